@@ -1,6 +1,23 @@
 """bench.py — Mray/s (primary+shadow) of the MI355X voxel ray-trace path.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config C1] [--no-cpu] [--no-extra]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config C1] [--dump-outputs DIR]
+                  [--full [--no-cpu] [--no-extra]]
+
+A plain run does what the headline figure needs and no more: it loads the config, runs W
+warm-up steps, times K steps, writes the outputs of the last timed step if --dump-outputs is
+given, and prints the result line.  --full adds every other measurement described below
+(serial frames, other_arithmetic, extra_configs, weak_scaling, cpu_baseline), each a run of its
+own after the headline; --no-cpu / --no-extra leave parts of them out again.  Beside a long
+headline run the serial frames and the extra configs stop at FULL_MAX_STEPS steps.  The HIP
+events of the roofline cover the first PROFILE_MAX_LAUNCHES launches of a timed region.
+
+--dump-outputs DIR: what the timed path left in the caller's buffers after the last timed step,
+as float32 DIR/<name>.npy (rank 0): `accumulator` (H, W, 4), the running average the render call
+writes, and `screen_rgb8` (H, W, 3), the packed RGB8 screen split into its R, G, B bytes.  With
+N > 1 ranks: rank 0's gathered `screen_rgb8` and its own accumulator shard `accumulator_rank0`
+(packed tile order, dist.py).  Scenes, camera, lights and per-frame seeds are fixed by the
+config, so the same arguments give the same inputs in every run.  Above 64 MB in all (the 4K
+configs) a fixed seeded sample of the pixels is written instead, its indices as `pixel_index`.
 
 A step = one image of the workload: spp accumulated frames (C1-C3: 1, C4: 16), each one
 vpx_render call (primary rays, Trace(ray, max_bounces) flattened, the light samples with
@@ -23,7 +40,7 @@ frame to rank 0's screen, overlapped with the next step's renders.  Timed region
 that time.  Weak scaling (about N x the pixels at the same field of view, weak_size) is the extra key
 `weak_scaling`.
 
-Extra keys: `extra_configs` C2 / C3 / C4 (same N, their stated sizes, fewer steps), each
+Extra keys (--full): `extra_configs` C2 / C3 / C4 / Z1 (same N, their stated sizes), each
 with ms/step, Mray/s (primary+shadow), total Mray/s (incl. bounce rays) and its own
 dominant-stage roofline.
 
@@ -34,7 +51,7 @@ DESIGN.md §4, divided by its average launch duration measured with HIP events o
 library's stream over the timed region (only that stage is timed there).  traffic: HBM
 bytes per launch from the rocprofv3 PMC summary committed for THIS library build
 (profiles/*_pmc_traffic.json, matched by the library's sha256), else null.
-cpu_baseline (rank 0, N = 1): the CPU restatement (oracle/liboracle_perf.so, -O3
+cpu_baseline (--full; rank 0, N = 1): the CPU restatement (oracle/liboracle_perf.so, -O3
 x86-64-v3, bit-identical to the checker) on a bounded row sample of the C1 frame with every
 thread of the box's CPU share, plus BASELINE.md §3's C0 / C0' frames (640x360, 1 thread and
 all threads, median of 20 after 3 warm-ups).
@@ -210,10 +227,49 @@ class Env:
         return f"tile-shard x{self.n}, accumulator sharded, RCCL gather of RGB8 to rank 0 (overlapped)"
 
 
-def run_config(pkg, env, cfg, steps, warmup, weak=False, sha=None, pipeline=None, serial_frames=0, arith=0):
+PROFILE_MAX_LAUNCHES = 1 << 16  # vpx_profile_enable's limit
+# --full: the legs beside the headline time at most this many steps (serial legs: frames), so a
+# long headline run (--steps in the thousands) keeps them to about a minute in all
+FULL_MAX_STEPS = 1000
+DUMP_BUDGET = 64 * 1000 * 1000  # bytes --dump-outputs may write in all
+DUMP_SEED = 20240611
+
+
+def dump_outputs(out_dir, acc, rgb, width, height, sharded_acc=False):
+    """--dump-outputs: the caller's buffers after the last timed step as float32 .npy files.
+    acc: the float32 accumulator (4 per pixel; the whole frame, or rank 0's packed shard when
+    `sharded_acc`), rgb: the packed RGB8 screen (one int32 per pixel, (r << 16) + (g << 8) + b).
+    Over DUMP_BUDGET bytes in all, the same seeded pixel sample of every array is written with
+    its sorted indices (`pixel_index`, float64; `pixel_index_rank0` for a packed shard)."""
+    os.makedirs(out_dir, exist_ok=True)
+    p = rgb.reshape(-1).view(np.uint32)
+    screen = np.stack([p >> 16, (p >> 8) & 255, p & 255], axis=1).astype(np.float32)
+    acc = np.ascontiguousarray(acc, np.float32).reshape(-1, 4)
+    acc_name = "accumulator_rank0" if sharded_acc else "accumulator"
+    arrays = {acc_name: acc, "screen_rgb8": screen}
+    if acc.nbytes + screen.nbytes <= DUMP_BUDGET:
+        if not sharded_acc:
+            arrays[acc_name] = acc.reshape(height, width, 4)
+        arrays["screen_rgb8"] = screen.reshape(height, width, 3)
+    else:
+        rng = np.random.default_rng(DUMP_SEED)
+        frac = DUMP_BUDGET / float(acc.nbytes + screen.nbytes + 8 * (len(acc) + len(screen)))
+        idx = np.sort(rng.choice(len(screen), int(len(screen) * frac), replace=False))
+        arrays.update(screen_rgb8=screen[idx], pixel_index=idx.astype(np.float64))
+        if sharded_acc:  # the shard's pixels are in packed tile order: a sample of its own
+            idx = np.sort(rng.choice(len(acc), int(len(acc) * frac), replace=False))
+            arrays["pixel_index_rank0"] = idx.astype(np.float64)
+        arrays[acc_name] = acc[idx]
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
+def run_config(pkg, env, cfg, steps, warmup, weak=False, sha=None, pipeline=None, serial_frames=0, arith=0,
+               dump=None):
     """Load `cfg` on this rank, run warmup + `steps` timed steps, return the result dict
     (rank 0; None elsewhere).  Frees the world before returning.  arith: vpx_set_arithmetic
-    mode (0 exact, the default; 1 the reference's x86 rcpps / rsqrtps from this host)."""
+    mode (0 exact, the default; 1 the reference's x86 rcpps / rsqrtps from this host).
+    dump: directory for the outputs of the last timed step (dump_outputs; rank 0 writes)."""
     desc = pkg.scene.CONFIGS[cfg]()
     if weak:  # N x the pixels at the same field of view (the base frame's camera)
         desc = desc.with_resolution(*weak_size(env.n, (desc.width, desc.height)))
@@ -267,7 +323,10 @@ def run_config(pkg, env, cfg, steps, warmup, weak=False, sha=None, pipeline=None
     timed_stages = [max(warm, key=lambda k: warm[k][3])] if warmup > 0 else None  # by busy time
     ctx.counters(reset=True)
     ctx.profile_select(timed_stages)
-    ctx.profile_enable(steps * launches)
+    # the library's event pool holds PROFILE_MAX_LAUNCHES launches: a longer timed region records
+    # its first launches only (the later marks are dropped, vpx_kernels.hip prof_mark)
+    capped = steps * launches > PROFILE_MAX_LAUNCHES
+    ctx.profile_enable(min(steps * launches, PROFILE_MAX_LAUNCHES))
     ctx.profile_read(reset=True)
     if env.dist:
         env.dist.barrier()
@@ -297,12 +356,24 @@ def run_config(pkg, env, cfg, steps, warmup, weak=False, sha=None, pipeline=None
         prim, shad, bounce, cells = float(st.primary_rays), float(st.shadow_rays), float(st.bounce_rays), \
             float(st.dda_cells)
     out = None
+    prof = ctx.profile_read()
+    one_step = warm  # every stage's launches in one step (steps are identical)
+    if capped and not timed_stages:  # no warmup step counted them: one step more, after the timed region
+        ctx.profile_select(None)
+        ctx.profile_enable(launches)
+        step()
+        if sharded is not None:
+            sharded.flush()
+        torch.cuda.synchronize()
+        one_step = ctx.profile_read()
     if env.rank == 0:
         K = steps
         ms_step = elapsed * 1000.0 / K
-        prof = ctx.profile_read()
         dom = max(prof, key=lambda k: prof[k][3])
         dom_ms, dom_launches, dom_cells, dom_busy = prof[dom]
+        # the times are per recorded launch; the cell counters run over the whole timed region, so
+        # the bytes per launch divide by every launch of it
+        all_launches = one_step[dom][1] * K if capped else dom_launches
         split = warm if timed_stages else prof
         # a launch's duration = the stage's busy time (the union of its launch intervals) per
         # launch: with frames in flight consecutive frames' launches overlap, and summing their
@@ -326,17 +397,18 @@ def run_config(pkg, env, cfg, steps, warmup, weak=False, sha=None, pipeline=None
         if dom == "finish":
             alg_bytes = local_pix / K / spp * 36.0
         elif dom == "frame":  # k_frame0: the whole depth-0 frame (every stage's cells + the finish)
-            alg_bytes = (sum(float(v[2]) for v in prof.values()) + local_pix * 36.0) / max(dom_launches, 1)
+            alg_bytes = (sum(float(v[2]) for v in prof.values()) + local_pix * 36.0) / max(all_launches, 1)
         else:
-            alg_bytes = float(dom_cells) / max(dom_launches, 1)
+            alg_bytes = float(dom_cells) / max(all_launches, 1)
             if dom == "shadow" and fused:
-                alg_bytes += local_pix * 36.0 / max(dom_launches, 1)
+                alg_bytes += local_pix * 36.0 / max(all_launches, 1)
         achieved = alg_bytes / (kernel_ms * 1e-3) / 1e9
         frame_bytes = (cells + prim * 36.0) / K
         pmc, pmc_src = pmc_summary(kernels[dom], cfg, W, H, sha) if env.n == 1 else (None, None)
         traffic = pmc["hbm_bytes_per_launch"] if pmc else None
         out = {
             "config": cfg, "value": round((prim + shad) / elapsed / 1e6, 3), "ms_per_step": round(ms_step, 4),
+            "steps": K,
             "total_mray_s": round((prim + shad + bounce) / elapsed / 1e6, 3),
             "workload": f"{cfg}: {W}x{H}, {max(g.n for g in desc.grids)}^3 {desc.name}, {spp} spp, Trace depth "
                         f"{desc.max_bounces}"
@@ -366,6 +438,11 @@ def run_config(pkg, env, cfg, steps, warmup, weak=False, sha=None, pipeline=None
         }
         if ranks is not None:
             out["ranks"] = ranks
+        if dump:  # the buffers as the last timed step left them (synchronised above)
+            if sharded is None:
+                dump_outputs(dump, acc.cpu().numpy(), rgb.cpu().numpy(), W, H)
+            else:
+                dump_outputs(dump, sharded.accum.cpu().numpy(), sharded.screen.cpu().numpy(), W, H, sharded_acc=True)
     if env.n == 1 and serial_frames:
         # what a per-frame-synchronous host (the tmpl8 loop: Tick, then present, every frame,
         # template.cpp:300-305) sees: one frame at a time, no lanes, the host waits for each
@@ -499,8 +576,14 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", default="C1")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip extra_configs / weak_scaling")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also measure the serial frames, other_arithmetic, extra_configs, "
+                         "weak_scaling and cpu_baseline (off by default: a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as float32 DIR/<name>.npy (dump_outputs)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip cpu_baseline")
+    ap.add_argument("--no-extra", action="store_true",
+                    help="with --full: skip other_arithmetic / extra_configs / weak_scaling")
     ap.add_argument("--cpu-budget", type=float, default=12.0)
     ap.add_argument("--arith", choices=("exact", "x86"), default="x86" if X86_HOST else "exact",
                     help="vpx_set_arithmetic of every config (x86, the default on x86 hosts: the reference's "
@@ -510,6 +593,9 @@ def main():
                     help="frames in flight per GPU (vpx_set_pipeline lanes; 0 = serial frames); default: "
                          "per config, PIPELINE")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    extras = args.full and not args.no_extra
     if needs_launch(args.gpus):
         # `python bench.py --gpus N` without torchrun: start the N ranks as child processes
         # before this process touches the GPU (no HIP call has been made yet), relay their
@@ -527,9 +613,10 @@ def main():
     sha = lib_sha256(pkg)
     arith = 1 if args.arith == "x86" else 0
     head = run_config(pkg, env, args.config, args.steps, args.warmup, sha=sha, pipeline=args.pipeline,
-                      serial_frames=args.steps, arith=arith)
+                      serial_frames=min(args.steps, FULL_MAX_STEPS) if args.full else 0, arith=arith,
+                      dump=args.dump_outputs)
     other_arith = None
-    if env.n == 1 and not args.no_extra and X86_HOST:
+    if env.n == 1 and extras and X86_HOST:
         # the same workload in the other arithmetic mode: with the reference's arithmetic as the
         # headline (VPX_ARITH_X86_HOST: FindNearest's FastReciprocal and the primary rsqrtps as this
         # host computes them, bit-identical to the oracle's x86 mode, tests/test_x86_arith.py), the
@@ -542,11 +629,12 @@ def main():
                            "x86_cost": round((head["ms_per_step"] / r["ms_per_step"] if arith else
                                               r["ms_per_step"] / head["ms_per_step"]) - 1.0, 4)}
     extra, weak = {}, None
-    if not args.no_extra:
-        # the extras time as many steps as the headline: with frames in flight the timed region
+    if extras:
+        # the extras time as many steps as the headline (FULL_MAX_STEPS at the most; each states its
+        # own `steps`): with frames in flight the timed region
         # includes one pipeline fill and drain, which 5 steps (the earlier K / 4) charged at
         # ~0.2 ms per step to C2 (2.70 vs 2.50 ms per step at 10 steps, same build and box)
-        xs = max(3, args.steps)
+        xs = max(3, min(args.steps, FULL_MAX_STEPS))
         for cfg in EXTRA_CONFIGS:
             if cfg != args.config:
                 r = run_config(pkg, env, cfg, xs, min(args.warmup, 2), sha=sha, pipeline=args.pipeline,
@@ -582,7 +670,7 @@ def main():
             out["extra_configs"] = extra
         if weak is not None:
             out["weak_scaling"] = weak
-        if env.n == 1 and not args.no_cpu:
+        if env.n == 1 and args.full and not args.no_cpu:
             out["cpu_baseline"] = cpu_baseline(pkg, pkg.scene.CONFIGS[args.config](), args.cpu_budget, arith)
         print(json.dumps(out), flush=True)
     if env.dist:

@@ -104,6 +104,51 @@ def test_combine_pmc_two_launch_stage():
     assert "l2_hit_rate" not in c  # missing in a part -> left out
 
 
+def _frame(width, height, seed=3):
+    import numpy as np
+    rng = np.random.default_rng(seed)
+    acc = rng.random(width * height * 4, dtype=np.float32)
+    r, g, b = (rng.integers(0, 256, width * height, dtype=np.int64) for _ in range(3))
+    return acc, ((r << 16) + (g << 8) + b).astype(np.int32), np.stack([r, g, b], axis=1)
+
+
+def test_dump_outputs_whole_frame(tmp_path):
+    """--dump-outputs: the accumulator as it is and the packed screen split into R, G, B, float32."""
+    import numpy as np
+    b = _bench()
+    acc, rgb, chans = _frame(7, 5)
+    b.dump_outputs(str(tmp_path / "d"), acc, rgb, 7, 5)
+    assert sorted(os.listdir(tmp_path / "d")) == ["accumulator.npy", "screen_rgb8.npy"]
+    a, s = np.load(tmp_path / "d" / "accumulator.npy"), np.load(tmp_path / "d" / "screen_rgb8.npy")
+    assert a.dtype == np.float32 and a.shape == (5, 7, 4) and np.array_equal(a.reshape(-1), acc)
+    assert s.dtype == np.float32 and s.shape == (5, 7, 3) and np.array_equal(s.reshape(-1, 3), chans)
+
+
+def test_dump_outputs_samples_above_the_budget(tmp_path, monkeypatch):
+    """Over the byte budget: one seeded pixel sample of both arrays, the same in every run,
+    within the budget, with its indices beside it."""
+    import numpy as np
+    b = _bench()
+    acc, rgb, chans = _frame(64, 48)
+    monkeypatch.setattr(b, "DUMP_BUDGET", 20000)
+    for d in ("one", "two"):
+        b.dump_outputs(str(tmp_path / d), acc, rgb, 64, 48)
+    files = sorted(os.listdir(tmp_path / "one"))
+    assert files == ["accumulator.npy", "pixel_index.npy", "screen_rgb8.npy"]
+    got = {f: np.load(tmp_path / "one" / f) for f in files}
+    assert all(np.array_equal(got[f], np.load(tmp_path / "two" / f)) for f in files)
+    assert sum(a.nbytes for a in got.values()) <= 20000
+    idx = got["pixel_index.npy"]
+    assert idx.dtype == np.float64 and 400 < len(idx) == len(np.unique(idx)) and idx.max() < 64 * 48
+    i = idx.astype(np.int64)
+    assert np.array_equal(got["accumulator.npy"], acc.reshape(-1, 4)[i])
+    assert np.array_equal(got["screen_rgb8.npy"], chans[i])
+    # a rank's packed accumulator shard has its own pixel order and sample
+    b.dump_outputs(str(tmp_path / "s"), acc[:4 * 1024], rgb, 64, 48, sharded_acc=True)
+    shard, sidx = np.load(tmp_path / "s" / "accumulator_rank0.npy"), np.load(tmp_path / "s" / "pixel_index_rank0.npy")
+    assert np.array_equal(shard, acc[:4 * 1024].reshape(-1, 4)[sidx.astype(np.int64)]) and sidx.max() < 1024
+
+
 def _rank_summary_worker(rank, world, port, q):
     import torch.distributed as dist
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))

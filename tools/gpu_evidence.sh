@@ -39,8 +39,8 @@ else
     steps=10; [ $c = C4 ] && steps=3
     step prof_$c 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$GRAFT_REPO_ROOT/$O/prof_$c" -o run -- python bench.py --config $c --steps $steps --warmup 2 --no-cpu --no-extra
   done
-  step bench 600 python bench.py
+  step bench 600 python bench.py --full
   for n in ${REHEARSE:-2 4}; do
-    step rehearse$n 300 env VPX_BENCH_SHARED_DEVICE=1 python bench.py --gpus $n --steps 10 --warmup 2
+    step rehearse$n 300 env VPX_BENCH_SHARED_DEVICE=1 python bench.py --full --gpus $n --steps 10 --warmup 2
   done
 fi
