@@ -123,6 +123,14 @@ class Context:
         self._chk(self.lib.vpx_grid_checksum(self.h, grid_id, C.byref(out)), "vpx_grid_checksum")
         return out.value
 
+    def grid_axis_planes(self, grid_id, n):
+        """The 24 distance-field axis planes of an n^3 grid (debug read-back): uint16 (24, words per plane)."""
+        nb2 = ((n + 3) // 4 + 3) // 4
+        out = np.zeros((24, 64 * nb2 ** 3), np.uint16)
+        self._chk(self.lib.vpx_grid_axis_planes(self.h, grid_id, out.ctypes.data_as(C.c_void_p), out.size),
+                  "vpx_grid_axis_planes")
+        return out
+
     # ---------------------------------------------------------------- hot path
     def render(self, params, accum_ptr, rgb_ptr=None, stats=False):
         st = abi.Stats() if stats else None

@@ -242,6 +242,13 @@ namespace skip {
 // dfp (optional): the distance field again as 8 octant planes of one byte per brick (plane
 // o at dfp + o * plane, brick at blk_index), 0 for an occupied brick — a walk reads only
 // its own octant's plane, 1 byte per brick instead of an 8-byte word (classify_dfp).
+// dfa (optional): 24 planes, one per (octant o, axis a) at plane index o * 3 + a, of one
+// 16-bit word per brick at blk_index: the cube k again in the low byte (0 for an occupied
+// brick) and in the high byte the length L >= k, in bricks, of the empty k x k x L box that
+// starts at the brick, keeps the cube's cross-section and runs along axis a toward the octant
+// (capped at 255; 255 too when the run of cubes leaves the grid).  A walk reads the plane of
+// its octant and its dominant axis (dom_axis): rays along a street or a wall cross their long
+// empty boxes in one skip where the cubes are 1 or 2 bricks.
 struct GridView {
     const uint8_t* cells;
     const uint64_t* l1;
@@ -249,6 +256,7 @@ struct GridView {
     uint32_t n, nb1, nb2, nb3;
     const uint8_t* dfp;
     uint64_t plane;
+    const uint16_t* dfa;  // (optional) the axis planes, see classify_axis_o
 };
 
 struct Walk {
@@ -367,6 +375,38 @@ VPX_HD int classify_dfp_o(Walk& w, const GridView& g, uint32_t opar) {
 }
 // The first parent of octant o's plane (classify_dfp_o).
 VPX_HD uint32_t plane_parent(const GridView& g, uint32_t o) { return o * (g.nb2 * g.nb2 * g.nb2); }
+// The axis a walk takes its boxes along: the one with the smallest tdelta (the ray advances
+// fastest along it).  Fixed per ray; ties, infinities and NaNs take whatever the compares
+// give — every (octant, axis) box is empty, the choice only decides how far a skip reaches.
+VPX_HD uint32_t dom_axis(const Walk& w) {
+    return w.dx <= w.dy ? (w.dx <= w.dz ? 0u : 2u) : (w.dy <= w.dz ? 1u : 2u);
+}
+// classify_dfp_o on the axis planes: apar = (octant * 3 + axis) * nb2^3 (plane_parent of the
+// plane's index), one 16-bit load per step.  An empty brick skips (class 2) when its cube
+// reaches MINC or its box's length MINL; m1 gets the word (cube_dfp / len_dfa read it back).
+template <uint32_t MINC = kMinCube, uint32_t MINL = 2>
+VPX_HD int classify_axis_o(Walk& w, const GridView& g, uint32_t apar) {
+    const uint32_t bx = w.X >> 2, by = w.Y >> 2, bz = w.Z >> 2, np = g.nb2;
+#if defined(__HIP_DEVICE_COMPILE__)
+    const uint32_t parent = apar + __umul24(bz >> 2, __umul24(np, np)) + __umul24(by >> 2, np) + (bx >> 2);
+#else
+    const uint32_t parent = apar + (bz >> 2) * np * np + (by >> 2) * np + (bx >> 2);
+#endif
+    const uint64_t i = (uint64_t)parent << 6 | ((bx & 3u) | ((by & 3u) << 2) | ((bz & 3u) << 4));
+#if defined(__HIP_DEVICE_COMPILE__)
+    const uint32_t kl = ((const __attribute__((address_space(1))) uint16_t*)g.dfa)[i];
+#else
+    const uint32_t kl = g.dfa[i];
+#endif
+    if (kl == 0u) {
+        w.m1 = load_mask(g.l1, blk_index(bx, by, bz, np));
+        const uint32_t cb = (w.X & 3u) | ((w.Y & 3u) << 2) | ((w.Z & 3u) << 4);
+        return ((w.m1 >> cb) & 1ull) ? 0 : 1;
+    }
+    w.m1 = kl;
+    return (((kl & 255u) >= MINC) | ((kl >> 8) >= MINL)) ? 2 : 3;
+}
+VPX_HD uint32_t len_dfa(const Walk& w) { return ((uint32_t)w.m1 >> 8) & 255u; }
 // The distance-field cube (in bricks) of an empty brick from m1: after classify (the l1
 // word, byte at the octant's shift) / after classify_dfp (the plane byte itself).
 VPX_HD uint32_t cube_l1(const Walk& w) { return (uint32_t)(w.m1 >> w.osh) & 255u; }
@@ -383,6 +423,19 @@ VPX_HD void df_box(const Walk& w, uint32_t n, uint32_t k, uint32_t lo[3], uint32
         const uint32_t up = b + k4 - 1u, dn = b + 4u > k4 ? b + 4u - k4 : 0u;
         lo[k] = sg[k] > 0 ? c[k] : dn;
         hi[k] = sg[k] > 0 ? (up < n - 1u ? up : n - 1u) : c[k];
+    }
+}
+
+// df_box for an axis-plane word: the cube's k x k cross-section, L bricks along `axis`.
+VPX_HD void df_box_axis(const Walk& w, uint32_t n, uint32_t k, uint32_t L, uint32_t axis, uint32_t lo[3], uint32_t hi[3]) {
+    const uint32_t c[3] = {w.X, w.Y, w.Z};
+    const int32_t sg[3] = {w.sx, w.sy, w.sz};
+    for (uint32_t q = 0; q < 3; ++q) {
+        const uint32_t e4 = (q == axis ? L : k) * 4u;
+        const uint32_t b = c[q] & ~3u;
+        const uint32_t up = b + e4 - 1u, dn = b + 4u > e4 ? b + 4u - e4 : 0u;
+        lo[q] = sg[q] > 0 ? c[q] : dn;
+        hi[q] = sg[q] > 0 ? (up < n - 1u ? up : n - 1u) : c[q];
     }
 }
 
@@ -739,17 +792,22 @@ VPX_HD int skip_box_lean(Walk& w, uint32_t lo[3], uint32_t hi[3], float bound, u
 // Scene::FindNearest (MODE nearest) / Scene::IsOccluded walk from an initialised state.
 // Returns true at the first solid cell (w.t / w.X,Y,Z describe it).  Exact.  The device
 // walker (walk_wave, vpx_trace.hpp) runs the same per-lane sequence.
+// With the axis planes (g.dfa) the boxes are theirs, along the ray's dominant axis.
 VPX_HD bool walk_skip(const GridView& g, Walk& w, float bound, uint32_t& cells) {
+    const bool axes = g.dfa != nullptr;
+    const uint32_t axis = dom_axis(w);
+    const uint32_t apar = plane_parent(g, (w.osh >> 3) * 3u + axis);
     for (;;) {
         if (!(w.t < bound)) return false;
-        const int cls = classify(w, g);
+        const int cls = axes ? classify_axis_o(w, g, apar) : classify(w, g);
         if (cls == 0) {
             ++cells;
             return true;
         }
         if (cls == 2) {
             uint32_t lo[3], hi[3];
-            df_box(w, g.n, cube_l1(w), lo, hi);
+            if (axes) df_box_axis(w, g.n, cube_dfp(w), len_dfa(w), axis, lo, hi);
+            else df_box(w, g.n, cube_l1(w), lo, hi);
             if (skip_box_lean(w, lo, hi, bound, cells) == 1) return false;
         }
         ++cells;  // visit the (empty) current cell
@@ -772,6 +830,24 @@ VPX_HD uint8_t df_value(uint32_t x, uint32_t y, uint32_t z, uint32_t o, uint32_t
         mn = v < mn ? v : mn;
     }
     return (uint8_t)(mn < 255u ? mn + 1u : 255u);
+}
+
+// The length byte of an axis-plane word (GridView::dfa) from the cubes ahead: k + the run
+// of bricks b + i e_a, i >= 1, whose cube toward the octant is at least k (`cube(x, y, z)`:
+// 0 for an occupied brick); 255 when the run leaves the grid or grows past the cap.  The box
+// is empty because the k^3 cubes at offsets 0 .. L - k along the axis cover it.
+template <class Cube>
+VPX_HD uint32_t axis_len(uint32_t x, uint32_t y, uint32_t z, uint32_t o, uint32_t a, uint32_t k, uint32_t nb1, Cube cube) {
+    const uint32_t e = ((o >> a) & 1u) ? ~0u : 1u;
+    uint32_t p[3] = {x, y, z};
+    uint32_t L = k;
+    while (L < 255u) {
+        p[a] += e;
+        if (p[a] >= nb1) return 255u;
+        if (cube(p[0], p[1], p[2]) < k) break;
+        ++L;
+    }
+    return L;
 }
 
 #if !defined(__HIP_DEVICE_COMPILE__)
@@ -821,6 +897,25 @@ inline void build_planes_host(const uint64_t* l1, const uint64_t* l2, uint32_t n
                 const uint32_t b = blk_index(x, y, z, nb2);
                 for (uint32_t o = 0; o < 8; ++o) dfp[o * plane + b] = (uint8_t)(l1[b] >> (8 * o));
             }
+}
+
+// The axis planes from the octant planes (as build_axis_k): dfa holds 24 * nb2^3 * 64 words.
+inline void build_axis_planes_host(const uint8_t* dfp, uint32_t n, uint16_t* dfa) {
+    const uint32_t nb1 = (n + 3) / 4, nb2 = (nb1 + 3) / 4;
+    const uint64_t plane = 64ull * nb2 * nb2 * nb2;
+    std::memset(dfa, 0, 2 * 24 * plane);
+    for (uint32_t o = 0; o < 8; ++o) {
+        const uint8_t* pl = dfp + o * plane;
+        auto cube = [&](uint32_t x, uint32_t y, uint32_t z) -> uint32_t { return pl[blk_index(x, y, z, nb2)]; };
+        for (uint32_t z = 0; z < nb1; ++z)
+            for (uint32_t y = 0; y < nb1; ++y)
+                for (uint32_t x = 0; x < nb1; ++x) {
+                    const uint32_t b = blk_index(x, y, z, nb2), k = pl[b];
+                    if (!k) continue;
+                    for (uint32_t a = 0; a < 3; ++a)
+                        dfa[(o * 3 + a) * plane + b] = (uint16_t)(k | axis_len(x, y, z, o, a, k, nb1, cube) << 8);
+                }
+    }
 }
 #endif
 

@@ -429,8 +429,10 @@ __device__ __forceinline__ T* uni_ptr(T* p) {
     return (T*)(((uint64_t)uni((uint32_t)(v >> 32)) << 32) | uni((uint32_t)v));
 }
 __device__ __forceinline__ skip::GridView grid_view(const DevGrid& g) {
+    // the axis planes follow the 8 octant planes in the same buffer (build_df)
+    const uint8_t* dfp = uni_ptr(g.dfp);
     return skip::GridView{uni_ptr(g.cells), uni_ptr(g.l1), uni_ptr(g.l2), uni(g.n), uni(g.nb1), uni(g.nb2),
-                          uni(g.nb3),       uni_ptr(g.dfp), g.plane};
+                          uni(g.nb3),       dfp,            g.plane,        (const uint16_t*)(dfp + 8u * g.plane)};
 }
 __device__ __forceinline__ skip::Walk to_walk(const Dda& s) {
     skip::Walk w;
@@ -457,7 +459,8 @@ constexpr uint32_t kSkipwNearest = 1, kSkipwBounce = 2, kSkipwShadow = 4;
 #define VPX_MINC_NEAREST 2
 #endif
 constexpr uint32_t kMincNearest = VPX_MINC_NEAREST, kMincBounce = 2, kMincShadow = 1;
-// Brick runs per walk kind, the RUN word: cap | passes << 8 | seg2 << 17 | min2 << 18.
+// Brick runs per walk kind, the RUN word: cap | passes << 8 | seg2 << 17 | min2 << 18 |
+// axis << 19 | minlen << 20.
 // After its octant-plane byte (and, in an occupied brick, its cell mask) loads, a lane
 // steps up to `cap` cells inside its 4^3 brick on the register copy; `passes` brick loads
 // per step-phase iteration.  Measured (ms, one box): primary C1 0.432 -> 0.402 with 3|2<<8;
@@ -472,17 +475,36 @@ constexpr uint32_t kMincNearest = VPX_MINC_NEAREST, kMincBounce = 2, kMincShadow
 // interleaved runs, vs the three-compare form): C1 0.678 vs 0.687; the shadow walkers (72
 // VGPRs, 7 waves/SIMD) spilled two more VGPRs with it and C3 went 5.26 -> 5.53, so they keep
 // the three-compare form.
+// axis (bit 19): the walk's boxes come from the axis planes (skip::GridView::dfa): the brick's
+// cube extended along the ray's dominant axis, one 16-bit load per step instead of the octant
+// plane's byte.  minlen (bits 20-23): an empty brick whose cube is below the skip minimum
+// still skips when its box is at least this many bricks long.  VPX_AXIS_BOXES sets the bit for
+// every walk kind that has no word of its own on the command line.  Measured (ms per step, one
+// box, three interleaved runs each of the build before the planes and this one, every kind on):
+// C1 0.5424-0.5484 -> 0.4737-0.4789, C2 2.292-2.323 -> 2.051-2.058, C3 3.594-3.599 ->
+// 3.363-3.377, C4 26.39-26.63 -> 25.40-25.56, Z1 (tiny grids, little to extend) 1.491-1.514 ->
+// 1.470-1.510; k_frame0 spills 27 VGPRs with it instead of 19 (DESIGN.md §4 has the table).
 // Rejected walk variants (DESIGN.md §4 keeps the measurements): classifying from the l1 + l2
 // words instead of the octant plane, a branch-free select-committed step, loading two
 // cells' words per round trip, prefetching the exit brick's byte, speculative cell-mask
 // loads after an occupied brick, walk continuations with a step budget.
+#ifndef VPX_AXIS_BOXES
+#define VPX_AXIS_BOXES 1
+#endif
+#ifndef VPX_AXIS_MINLEN
+#define VPX_AXIS_MINLEN 2u
+#endif
+#define VPX_RUN_AXIS ((VPX_AXIS_BOXES ? 1u : 0u) << 19 | VPX_AXIS_MINLEN << 20)
 #ifndef VPX_RUN_NEAREST
-#define VPX_RUN_NEAREST (3u | 3u << 8 | 1u << 17 | 1u << 18)
+#define VPX_RUN_NEAREST (3u | 3u << 8 | 1u << 17 | 1u << 18 | VPX_RUN_AXIS)
 #endif
 constexpr uint32_t kRunNearest = VPX_RUN_NEAREST;
-constexpr uint32_t kRunBounce = 4u | 1u << 8 | 0u << 17 | 1u << 18;
+#ifndef VPX_RUN_BOUNCE
+#define VPX_RUN_BOUNCE (4u | 1u << 8 | 0u << 17 | 1u << 18 | VPX_RUN_AXIS)
+#endif
+constexpr uint32_t kRunBounce = VPX_RUN_BOUNCE;
 #ifndef VPX_RUN_SHADOW
-#define VPX_RUN_SHADOW (3u | 1u << 8 | 1u << 17 | 0u << 18)
+#define VPX_RUN_SHADOW (3u | 1u << 8 | 1u << 17 | 0u << 18 | VPX_RUN_AXIS)
 #endif
 constexpr uint32_t kRunShadow = VPX_RUN_SHADOW;
 // Round 5 (ms per step, three interleaved runs, tools/gpu_ab.sh): FindNearest runs of 3 cells in
@@ -494,13 +516,13 @@ constexpr uint32_t kRunShadow = VPX_RUN_SHADOW;
 // 0.5433-0.5444 vs 0.5456-0.5482 ms in three, then 0.5427-0.5457 vs 0.5447-0.5484 (two boxes,
 // three interleaved runs each); five passes 0.5464-0.5474, runs of 2 in four 0.5428-0.5472.
 #ifndef VPX_RUN_FRAME_NEAREST
-#define VPX_RUN_FRAME_NEAREST (3u | 4u << 8 | 1u << 17 | 1u << 18)
+#define VPX_RUN_FRAME_NEAREST (3u | 4u << 8 | 1u << 17 | 1u << 18 | VPX_RUN_AXIS)
 #endif
 constexpr uint32_t kRunFrameNearest = VPX_RUN_FRAME_NEAREST;
 // At 7 waves/SIMD the frame's shadow walks take the two-compare step too: C1 0.5418-0.5489 vs
 // 0.5456-0.5539 ms (seven interleaved runs, all won; three passes 0.5479-0.5591).
 #ifndef VPX_RUN_FRAME_SHADOW
-#define VPX_RUN_FRAME_SHADOW (3u | 2u << 8 | 1u << 17 | 1u << 18)
+#define VPX_RUN_FRAME_SHADOW (3u | 2u << 8 | 1u << 17 | 1u << 18 | VPX_RUN_AXIS)
 #endif
 constexpr uint32_t kRunFrameShadow = VPX_RUN_FRAME_SHADOW;
 // The pools' walks (k_nearest_pool, k_shadow_pool: 96 VGPRs at 5 waves/SIMD) have their own
@@ -511,7 +533,7 @@ constexpr uint32_t kRunFrameShadow = VPX_RUN_FRAME_SHADOW;
 // weight 1 / 4, runs of 3 cells in two passes measured C2 2.63-2.66 / 2.60-2.64 / 2.66-2.75 /
 // 2.65-2.71 vs 2.59-2.65 ms, and re-checked at three lanes in round 5 (within noise).
 #ifndef VPX_RUN_SHADOW_POOL
-#define VPX_RUN_SHADOW_POOL (3u | 1u << 8 | 1u << 17 | 1u << 18)
+#define VPX_RUN_SHADOW_POOL (3u | 1u << 8 | 1u << 17 | 1u << 18 | VPX_RUN_AXIS)
 #endif
 #ifndef VPX_SKIPW_SHADOW_POOL
 #define VPX_SKIPW_SHADOW_POOL 4u
@@ -553,8 +575,12 @@ __device__ __forceinline__ bool walk_wave(const skip::GridView& g, skip::Walk& w
     constexpr int kPasses = (int)((RUN >> 8) & 255u);
     constexpr bool kSeg2Branch = (RUN >> 17) & 1u;
     constexpr bool kMin2 = (RUN >> 18) & 1u;  // step1's two-compare axis choice (vpx_skip.hpp)
+    constexpr bool kAxis = (RUN >> 19) & 1u;  // boxes from the axis planes (skip::classify_axis_o)
+    constexpr uint32_t kMinLen = (RUN >> 20) & 15u;
     static_assert(SKIPW > 0 && kRun > 0 && kPasses > 0, "walk_wave: skip weight, run cap and passes");
-    const uint32_t opar = skip::plane_parent(g, w.osh >> 3);  // the ray's octant plane
+    static_assert(!kAxis || kMinLen > 0, "walk_wave: the axis boxes' minimum length");
+    // the ray's plane: its octant's, or its (octant, dominant axis)'s
+    const uint32_t opar = skip::plane_parent(g, kAxis ? (w.osh >> 3) * 3u + skip::dom_axis(w) : w.osh >> 3);
     int mode = POOL ? *pmode : kStep;
     VPX_PH(uint64_t cs = 0, ck = 0, ns = 0, nk = 0, ls = 0, lk = 0, fb = 0, cf = 0;)
     for (;;) {
@@ -580,7 +606,8 @@ __device__ __forceinline__ bool walk_wave(const skip::GridView& g, skip::Walk& w
                     if (!(w.t < bound)) {
                         mode = kMiss;
                     } else {
-                        const int cls = skip::classify_dfp_o<MINC>(w, g, opar);
+                        const int cls = kAxis ? skip::classify_axis_o<MINC, kAxis ? kMinLen : 1u>(w, g, opar)
+                                              : skip::classify_dfp_o<MINC>(w, g, opar);
                         // the class's outcome by selects: 0 = the solid cell (visited, hit), 2 =
                         // skip; 1 / 3 visit the cell and run on in the brick
                         cells += cls != 2 ? 1u : 0u;
@@ -620,7 +647,8 @@ __device__ __forceinline__ bool walk_wave(const skip::GridView& g, skip::Walk& w
         VPX_MARK("skip phase");
         if (mode == kSkip) {
             uint32_t lo[3], hi[3];
-            skip::df_box(w, g.n, skip::cube_dfp(w), lo, hi);
+            if (kAxis) skip::df_box_axis(w, g.n, skip::cube_dfp(w), skip::len_dfa(w), skip::dom_axis(w), lo, hi);
+            else skip::df_box(w, g.n, skip::cube_dfp(w), lo, hi);
             const int sr = skip::skip_box_lean<kSeg2Branch>(w, lo, hi, bound, cells);  // 2 (refused): a plain step
             VPX_MARK("skip end");
             VPX_PH(fb += __popcll(__ballot(sr == 2));)

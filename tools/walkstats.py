@@ -1,4 +1,5 @@
-"""Per-ray walk statistics of the skipping walker on the C1 world (CPU model)."""
+"""Per-ray walk statistics of the skipping walker on a config's world (CPU model):
+python tools/walkstats.py [C1|C2|C3], MODES="0 -2" (cubes, then axis boxes of minimum length 2)."""
 import ctypes as C, os, subprocess, sys
 import numpy as np
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -88,16 +89,22 @@ lib.build_slabs.argtypes = [V, C.c_uint32]
 lib.build_slabs(bocc.ctypes.data, nbk)
 lib.set_mode.argtypes = [C.c_int]
 lib.slab_out.restype = C.c_uint64
-modes = [int(x) for x in os.environ.get("MODES", "0").split()]
+lib.build_axis.argtypes = [V, V, C.c_uint32]
+lib.build_axis(l1.ctypes.data, l2.ctypes.data, n)
+lib.set_axis.argtypes = [C.c_int]
+# MODES: 0 cubes, n > 0 the slab experiment, -n axis boxes with minimum length n (AXIS model)
+modes = [int(x) for x in os.environ.get("MODES", "0 -2").split()]
 lib.set_full.argtypes = [C.c_int]
 lib.set_full(int(os.environ.get("FULL", "0")))  # 1: whole boxes (the exact multi-binade tier)
 for name, (a, b, bnd), mode in [(nm_, v, md) for nm_, v in sets.items() for md in modes]:
-    lib.set_mode(mode)
+    lib.set_mode(max(mode, 0))
+    lib.set_axis(max(-mode, 0))
     R = len(a)
     o = sim(a, b, bnd)
     print(f"mode {mode}: slab skips {lib.slab_out() / R:.1f} per ray")
     print(f"{name} ({R} rays): cells {o[0]/R:.0f} steps {o[1]/R:.1f} skips {o[2]/R:.1f} (max {o[7]}) "
-          f"lean-clipped {o[6]/max(o[2],1):.4f} cost {(o[1] + 5.8 * o[2]) / R:.0f}")
+          f"lean-clipped {o[6]/max(o[2],1):.4f} cost {(o[1] + 5.8 * o[2]) / R:.0f} "
+          f"hits {o[3]} end {o[4]} tbits {o[5]}")
     lib.small_out.restype = C.c_uint64
     print(f"   steps in empty bricks with a cube below the skip minimum: {lib.small_out() / R:.1f} per ray")
     cr = np.zeros(16, np.uint64); lib.cross_out.argtypes = [V]; lib.cross_out(cr.ctypes.data)
