@@ -247,9 +247,9 @@ int vpx_set_pipeline(vpx_ctx* ctx, uint32_t depth);
 /* Upload a dense N^3 grid of MatType bytes, index x + y*N + z*N*N (scene.h:241-248).
    Device memory per grid: N^3 bytes + the walkers' levels built from them, about N^3 / 4
    bytes (l1 cell masks N^3/8, distance-field octant planes N^3/8, l2 N^3/512), and the
-   distance field's 24 axis planes, 48 bytes per 4^3 brick where the octant planes take 8:
-   3 N^3 / 4 bytes, 0.75 GiB at N = 1024 and 6 GiB at 2048.  In all 2 GiB at N = 1024,
-   16 GiB at 2048, 128 GiB at 4096 (the maximum).  An allocation that fails returns
+   distance field's 24 axis planes of 32-bit words, 96 bytes per 4^3 brick where the octant
+   planes take 8: 3 N^3 / 2 bytes, 1.5 GiB at N = 1024 and 12 GiB at 2048.  In all 2.75 GiB
+   at N = 1024, 22 GiB at 2048, 176 GiB at 4096 (the maximum).  An allocation that fails returns
    VPX_E_NOMEM. */
 int vpx_upload_grid(vpx_ctx* ctx, uint32_t grid_id, const uint8_t* cells, uint32_t n);
 /* Build-defined world generator on device: a grid-oriented model
@@ -273,8 +273,10 @@ int vpx_grid_emissive_sphere(vpx_ctx* ctx, uint32_t grid_id, uint8_t mat, float 
 /* FNV-1a-style 64-bit checksum of a device grid (for size-independent parity checks). */
 int vpx_grid_checksum(vpx_ctx* ctx, uint32_t grid_id, uint64_t* out);
 /* Debug read-back of a grid's 24 distance-field axis planes as the walkers read them
-   (vpx_skip.hpp GridView::dfa): `count` 16-bit words from the first plane on, at most
-   24 * 64 * ceil(ceil(N / 4) / 4)^3. */
+   (vpx_skip.hpp GridView::dfw): `count` 32-bit words k | L << 8 | Mb << 16 | Mc << 24 from the
+   first plane on, at most 24 * 64 * ceil(ceil(N / 4) / 4)^3. */
+int vpx_grid_wide_planes(vpx_ctx* ctx, uint32_t grid_id, uint32_t* out, uint64_t count);
+/* The same words' low halves, k | L << 8 (GridView::dfa). */
 int vpx_grid_axis_planes(vpx_ctx* ctx, uint32_t grid_id, uint16_t* out, uint64_t count);
 int vpx_set_volumes(vpx_ctx* ctx, const vpx_volume* volumes, uint32_t count);
 int vpx_set_materials(vpx_ctx* ctx, const vpx_material* materials, uint32_t count);

@@ -147,6 +147,7 @@ SIGNATURES = {
     "vpx_generate_tiled_grid": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p] + [C.c_uint32] * 7),
     "vpx_grid_checksum": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64)]),
     "vpx_grid_axis_planes": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64]),
+    "vpx_grid_wide_planes": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64]),
     "vpx_set_volumes": (C.c_int, [C.c_void_p, C.POINTER(Volume), C.c_uint32]),
     "vpx_set_materials": (C.c_int, [C.c_void_p, C.POINTER(Material), C.c_uint32]),
     "vpx_set_lights": (C.c_int, [C.c_void_p, C.POINTER(PointLight), C.c_uint32, C.POINTER(SpotLight), C.c_uint32,

@@ -131,6 +131,14 @@ class Context:
                   "vpx_grid_axis_planes")
         return out
 
+    def grid_wide_planes(self, grid_id, n):
+        """The same planes' whole words, k | L << 8 | Mb << 16 | Mc << 24: uint32 (24, words per plane)."""
+        nb2 = ((n + 3) // 4 + 3) // 4
+        out = np.zeros((24, 64 * nb2 ** 3), np.uint32)
+        self._chk(self.lib.vpx_grid_wide_planes(self.h, grid_id, out.ctypes.data_as(C.c_void_p), out.size),
+                  "vpx_grid_wide_planes")
+        return out
+
     # ---------------------------------------------------------------- hot path
     def render(self, params, accum_ptr, rgb_ptr=None, stats=False):
         st = abi.Stats() if stats else None

@@ -418,9 +418,10 @@ __global__ void build_planes_k(const uint64_t* __restrict__ l1, const uint64_t* 
 }
 
 // The axis planes from the octant planes (after build_planes_k): thread = (brick, octant,
-// axis), scanning at most 255 bricks ahead along the axis (skip::axis_len).  Same words as
-// skip::build_axis_planes_host.  dfa follows the octant planes in dfp's buffer.
-__global__ void build_axis_k(const uint8_t* __restrict__ dfp, uint32_t nb1, uint32_t nb2, uint16_t* __restrict__ dfa) {
+// axis), scanning at most 255 bricks ahead along the axis (skip::axis_len).  Writes the words'
+// k | L << 8 halves, as skip::build_wide_planes_host's first pass; the widths are build_wide_k's.
+// dfw follows the octant planes in dfp's buffer.
+__global__ void build_axis_k(const uint8_t* __restrict__ dfp, uint32_t nb1, uint32_t nb2, uint32_t* __restrict__ dfw) {
     const uint64_t plane = (uint64_t)nb2 * nb2 * nb2 * 64;
     const uint64_t total = plane * 24;
     for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (uint64_t)gridDim.x * blockDim.x) {
@@ -435,7 +436,30 @@ __global__ void build_axis_k(const uint8_t* __restrict__ dfp, uint32_t nb1, uint
         const uint8_t* pl = dfp + (uint64_t)o * plane;
         const uint32_t k = pl[s];  // 0: occupied, or a padding brick (bx, by or bz >= nb1), never walked
         auto cube = [&](uint32_t x, uint32_t y, uint32_t z) -> uint32_t { return pl[skip::blk_index(x, y, z, nb2)]; };
-        dfa[t] = k ? (uint16_t)(k | skip::axis_len(bx, by, bz, o, a, k, nb1, cube) << 8) : (uint16_t)0;
+        dfw[t] = k ? k | skip::axis_len(bx, by, bz, o, a, k, nb1, cube) << 8 : 0u;
+    }
+}
+
+// The widths Mb | Mc << 8 into the words' high halves (after build_axis_k; skip::axis_wids,
+// the same words as skip::build_wide_planes_host).  A thread reads other bricks' low halves
+// while their threads write the high ones, so both sides go through 16-bit accesses.
+__global__ void build_wide_k(uint16_t* dfh, uint32_t nb1, uint32_t nb2) {
+    const uint64_t plane = (uint64_t)nb2 * nb2 * nb2 * 64;
+    const uint64_t total = plane * 24;
+    for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (uint64_t)gridDim.x * blockDim.x) {
+        const uint32_t oa = (uint32_t)(t / plane);
+        const uint64_t s = t - (uint64_t)oa * plane;
+        const uint32_t o = oa / 3u, a = oa - o * 3u;
+        const uint64_t parent = s >> 6;
+        const uint32_t j = (uint32_t)(s & 63u);
+        const uint32_t bx = (uint32_t)(parent % nb2) * 4 + (j & 3u);
+        const uint32_t by = (uint32_t)((parent / nb2) % nb2) * 4 + ((j >> 2) & 3u);
+        const uint32_t bz = (uint32_t)(parent / ((uint64_t)nb2 * nb2)) * 4 + (j >> 4);
+        const uint16_t* pl = dfh + 2 * (uint64_t)oa * plane;
+        const uint32_t kl = pl[2 * s];
+        if (!kl || bx >= nb1 || by >= nb1 || bz >= nb1) continue;  // the high half is build_axis_k's 0
+        auto word = [&](uint32_t x, uint32_t y, uint32_t z) -> uint32_t { return pl[2 * (uint64_t)skip::blk_index(x, y, z, nb2)]; };
+        dfh[2 * t + 1] = (uint16_t)skip::axis_wids(bx, by, bz, o, a, kl & 255u, kl >> 8, nb1, word);
     }
 }
 
@@ -1458,7 +1482,7 @@ static int alloc_grid(vpx_ctx* c, uint32_t id, uint32_t n) {
         VPX_HIP(c, hipMalloc(&g.ptr, bytes));
         VPX_HIP(c, hipMalloc(&g.l1, sizeof(uint64_t) * (size_t)g.nb2 * g.nb2 * g.nb2 * 64));
         VPX_HIP(c, hipMalloc(&g.l2, sizeof(uint64_t) * (size_t)g.nb3 * g.nb3 * g.nb3 * 64));
-        VPX_HIP(c, hipMalloc(&g.dfp, (8 + 2 * 24) * g.plane()));  // 8 octant planes of bytes, 24 axis planes of words
+        VPX_HIP(c, hipMalloc(&g.dfp, (8 + 4 * 24) * g.plane()));  // 8 octant planes of bytes, 24 axis planes of 32-bit words
     }
     return sync_grids(c);
 }
@@ -1475,7 +1499,9 @@ static int build_df(vpx_ctx* c, const vpx_ctx::GridBuf& g) {
     }
     hipLaunchKernelGGL(build_planes_k, dim3(2048), dim3(256), 0, c->stream, g.l1, g.l2, g.nb2, g.nb3, g.dfp);
     VPX_HIP(c, hipGetLastError());
-    hipLaunchKernelGGL(build_axis_k, dim3(8192), dim3(256), 0, c->stream, g.dfp, g.nb1, g.nb2, (uint16_t*)(g.dfp + 8 * g.plane()));
+    hipLaunchKernelGGL(build_axis_k, dim3(8192), dim3(256), 0, c->stream, g.dfp, g.nb1, g.nb2, (uint32_t*)(g.dfp + 8 * g.plane()));
+    VPX_HIP(c, hipGetLastError());
+    hipLaunchKernelGGL(build_wide_k, dim3(8192), dim3(256), 0, c->stream, (uint16_t*)(g.dfp + 8 * g.plane()), g.nb1, g.nb2);
     VPX_HIP(c, hipGetLastError());
     return VPX_OK;
 }
@@ -1616,14 +1642,25 @@ int vpx_grid_checksum(vpx_ctx* c, uint32_t id, uint64_t* out) {
     return VPX_OK;
 }
 
-int vpx_grid_axis_planes(vpx_ctx* c, uint32_t id, uint16_t* out, uint64_t count) {
-    VPX_GROUP_FIRST(c, vpx_grid_axis_planes(m_, id, out, count));
+int vpx_grid_wide_planes(vpx_ctx* c, uint32_t id, uint32_t* out, uint64_t count) {
+    VPX_GROUP_FIRST(c, vpx_grid_wide_planes(m_, id, out, count));
     if (!c || !out) return fail(c, VPX_E_INVALID, "null argument");
     if (id >= c->grids.size() || !c->grids[id].ptr) return fail(c, VPX_E_INVALID, "unknown grid");
     const auto& g = c->grids[id];
     if (count > 24 * g.plane()) return fail(c, VPX_E_INVALID, "more words than the axis planes hold");
-    VPX_HIP(c, hipMemcpyAsync(out, g.dfp + 8 * g.plane(), count * sizeof(uint16_t), hipMemcpyDeviceToHost, c->stream));
+    VPX_HIP(c, hipMemcpyAsync(out, g.dfp + 8 * g.plane(), count * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     VPX_HIP(c, sync_all(c));
+    return VPX_OK;
+}
+
+int vpx_grid_axis_planes(vpx_ctx* c, uint32_t id, uint16_t* out, uint64_t count) {
+    VPX_GROUP_FIRST(c, vpx_grid_axis_planes(m_, id, out, count));
+    if (!c || !out) return fail(c, VPX_E_INVALID, "null argument");
+    if (id >= c->grids.size() || !c->grids[id].ptr) return fail(c, VPX_E_INVALID, "unknown grid");
+    if (count > 24 * c->grids[id].plane()) return fail(c, VPX_E_INVALID, "more words than the axis planes hold");
+    std::vector<uint32_t> words(count);
+    if (int r = vpx_grid_wide_planes(c, id, words.data(), count)) return r;
+    for (uint64_t i = 0; i < count; ++i) out[i] = (uint16_t)words[i];
     return VPX_OK;
 }
 

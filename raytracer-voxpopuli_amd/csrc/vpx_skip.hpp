@@ -249,6 +249,13 @@ namespace skip {
 // (capped at 255; 255 too when the run of cubes leaves the grid).  A walk reads the plane of
 // its octant and its dominant axis (dom_axis): rays along a street or a wall cross their long
 // empty boxes in one skip where the cubes are 1 or 2 bricks.
+// dfw (optional, instead of dfa): the same 24 planes with 32-bit words, k | L << 8 | Mb << 16 |
+// Mc << 24.  With the other two axes numbered b < c, Mb >= k is the largest width along b,
+// toward the octant, for which the box L (along a) x Mb (along b) x k (along c) holds only
+// empty bricks, and Mc the same along c with b kept at k (bricks outside the grid count as
+// empty; capped at 255, and 255 when the box reaches the grid's face).  A walk widens its box
+// along its second axis (sec_axis): above a street the space is much deeper than the street
+// is wide, and a ray drifts out of the thin box through that side first.
 struct GridView {
     const uint8_t* cells;
     const uint64_t* l1;
@@ -257,6 +264,7 @@ struct GridView {
     const uint8_t* dfp;
     uint64_t plane;
     const uint16_t* dfa;  // (optional) the axis planes, see classify_axis_o
+    const uint32_t* dfw;  // (optional) the axis planes with the widths; the device has only these
 };
 
 struct Walk {
@@ -378,11 +386,16 @@ VPX_HD uint32_t plane_parent(const GridView& g, uint32_t o) { return o * (g.nb2 
 // The axis a walk takes its boxes along: the one with the smallest tdelta (the ray advances
 // fastest along it).  Fixed per ray; ties, infinities and NaNs take whatever the compares
 // give — every (octant, axis) box is empty, the choice only decides how far a skip reaches.
-VPX_HD uint32_t dom_axis(const Walk& w) {
-    return w.dx <= w.dy ? (w.dx <= w.dz ? 0u : 2u) : (w.dy <= w.dz ? 1u : 2u);
+VPX_HD uint32_t dom_axis(float dx, float dy, float dz) { return dx <= dy ? (dx <= dz ? 0u : 2u) : (dy <= dz ? 1u : 2u); }
+VPX_HD uint32_t dom_axis(const Walk& w) { return dom_axis(w.dx, w.dy, w.dz); }
+// The axis a walk widens its boxes along: of the two that are not dom_axis, the one with the
+// smaller tdelta.  Fixed per ray like dom_axis, and like it any choice is a valid box.
+VPX_HD uint32_t sec_axis(uint32_t a, float dx, float dy, float dz) {
+    return a == 0u ? (dy <= dz ? 1u : 2u) : (a == 1u ? (dx <= dz ? 0u : 2u) : (dx <= dy ? 0u : 1u));
 }
+VPX_HD uint32_t sec_axis(const Walk& w) { return sec_axis(dom_axis(w), w.dx, w.dy, w.dz); }
 // classify_dfp_o on the axis planes: apar = (octant * 3 + axis) * nb2^3 (plane_parent of the
-// plane's index), one 16-bit load per step.  An empty brick skips (class 2) when its cube
+// plane's index), one load per step: the 32-bit word of dfw, or on the host dfa's 16 bits.  An empty brick skips (class 2) when its cube
 // reaches MINC or its box's length MINL; m1 gets the word (cube_dfp / len_dfa read it back).
 template <uint32_t MINC = kMinCube, uint32_t MINL = 2>
 VPX_HD int classify_axis_o(Walk& w, const GridView& g, uint32_t apar) {
@@ -394,9 +407,9 @@ VPX_HD int classify_axis_o(Walk& w, const GridView& g, uint32_t apar) {
 #endif
     const uint64_t i = (uint64_t)parent << 6 | ((bx & 3u) | ((by & 3u) << 2) | ((bz & 3u) << 4));
 #if defined(__HIP_DEVICE_COMPILE__)
-    const uint32_t kl = ((const __attribute__((address_space(1))) uint16_t*)g.dfa)[i];
+    const uint32_t kl = ((const __attribute__((address_space(1))) uint32_t*)g.dfw)[i];
 #else
-    const uint32_t kl = g.dfa[i];
+    const uint32_t kl = g.dfw ? g.dfw[i] : g.dfa[i];
 #endif
     if (kl == 0u) {
         w.m1 = load_mask(g.l1, blk_index(bx, by, bz, np));
@@ -404,9 +417,13 @@ VPX_HD int classify_axis_o(Walk& w, const GridView& g, uint32_t apar) {
         return ((w.m1 >> cb) & 1ull) ? 0 : 1;
     }
     w.m1 = kl;
-    return (((kl & 255u) >= MINC) | ((kl >> 8) >= MINL)) ? 2 : 3;
+    return (((kl & 255u) >= MINC) | (((kl >> 8) & 255u) >= MINL)) ? 2 : 3;
 }
 VPX_HD uint32_t len_dfa(const Walk& w) { return ((uint32_t)w.m1 >> 8) & 255u; }
+// The width of a dfw word's box along `sec`, one of the two axes that are not `axis`.
+VPX_HD uint32_t wid_dfw(const Walk& w, uint32_t axis, uint32_t sec) {
+    return ((uint32_t)w.m1 >> (sec < 3u - axis - sec ? 16u : 24u)) & 255u;
+}
 // The distance-field cube (in bricks) of an empty brick from m1: after classify (the l1
 // word, byte at the octant's shift) / after classify_dfp (the plane byte itself).
 VPX_HD uint32_t cube_l1(const Walk& w) { return (uint32_t)(w.m1 >> w.osh) & 255u; }
@@ -426,12 +443,14 @@ VPX_HD void df_box(const Walk& w, uint32_t n, uint32_t k, uint32_t lo[3], uint32
     }
 }
 
-// df_box for an axis-plane word: the cube's k x k cross-section, L bricks along `axis`.
-VPX_HD void df_box_axis(const Walk& w, uint32_t n, uint32_t k, uint32_t L, uint32_t axis, uint32_t lo[3], uint32_t hi[3]) {
+// df_box for an axis-plane word: L bricks along `axis`, M along `sec` and the cube's k along
+// the third (sec = axis and any M: the cube's k x k cross-section, a dfa word's box).
+VPX_HD void df_box_axis(const Walk& w, uint32_t n, uint32_t k, uint32_t L, uint32_t axis, uint32_t lo[3], uint32_t hi[3],
+                        uint32_t sec = 3u, uint32_t M = 0u) {
     const uint32_t c[3] = {w.X, w.Y, w.Z};
     const int32_t sg[3] = {w.sx, w.sy, w.sz};
     for (uint32_t q = 0; q < 3; ++q) {
-        const uint32_t e4 = (q == axis ? L : k) * 4u;
+        const uint32_t e4 = (q == axis ? L : (q == sec ? M : k)) * 4u;
         const uint32_t b = c[q] & ~3u;
         const uint32_t up = b + e4 - 1u, dn = b + 4u > e4 ? b + 4u - e4 : 0u;
         lo[q] = sg[q] > 0 ? c[q] : dn;
@@ -792,10 +811,11 @@ VPX_HD int skip_box_lean(Walk& w, uint32_t lo[3], uint32_t hi[3], float bound, u
 // Scene::FindNearest (MODE nearest) / Scene::IsOccluded walk from an initialised state.
 // Returns true at the first solid cell (w.t / w.X,Y,Z describe it).  Exact.  The device
 // walker (walk_wave, vpx_trace.hpp) runs the same per-lane sequence.
-// With the axis planes (g.dfa) the boxes are theirs, along the ray's dominant axis.
+// With the axis planes (g.dfa / g.dfw) the boxes are theirs, along the ray's dominant axis, and
+// with g.dfw widened along its second.
 VPX_HD bool walk_skip(const GridView& g, Walk& w, float bound, uint32_t& cells) {
-    const bool axes = g.dfa != nullptr;
-    const uint32_t axis = dom_axis(w);
+    const bool wide = g.dfw != nullptr, axes = wide || g.dfa != nullptr;
+    const uint32_t axis = dom_axis(w), sec = wide ? sec_axis(w) : 3u;
     const uint32_t apar = plane_parent(g, (w.osh >> 3) * 3u + axis);
     for (;;) {
         if (!(w.t < bound)) return false;
@@ -806,7 +826,7 @@ VPX_HD bool walk_skip(const GridView& g, Walk& w, float bound, uint32_t& cells) 
         }
         if (cls == 2) {
             uint32_t lo[3], hi[3];
-            if (axes) df_box_axis(w, g.n, cube_dfp(w), len_dfa(w), axis, lo, hi);
+            if (axes) df_box_axis(w, g.n, cube_dfp(w), len_dfa(w), axis, lo, hi, sec, wide ? wid_dfw(w, axis, sec) : 0u);
             else df_box(w, g.n, cube_l1(w), lo, hi);
             if (skip_box_lean(w, lo, hi, bound, cells) == 1) return false;
         }
@@ -848,6 +868,57 @@ VPX_HD uint32_t axis_len(uint32_t x, uint32_t y, uint32_t z, uint32_t o, uint32_
         ++L;
     }
     return L;
+}
+
+// A width byte of a dfw word (GridView::dfw) from the k | L << 8 halves of its plane's words
+// (`word(x, y, z)`: 0 for an occupied brick): the box of brick p with length L along a and k
+// along c is k wide along b, and grows layer by layer (L x k bricks each) along b toward the
+// octant until a layer holds an occupied brick; 255 when it reaches the grid's face or the cap.
+// A row of a layer is read through its bricks' own boxes: a word whose L covers the rest of
+// the row ends it, and one that starts a row covers its k rows as well, and from the layer's
+// first brick its k layers, so open space costs a few reads per layer.
+#ifndef VPX_WID_CAP
+#define VPX_WID_CAP 255u  // a smaller box is still empty: tests lower the cap to reach it on small grids
+#endif
+template <class Word>
+VPX_HD uint32_t axis_wid(const uint32_t p[3], uint32_t o, uint32_t a, uint32_t b, uint32_t c, uint32_t k, uint32_t L, uint32_t nb1,
+                         Word word) {
+    const uint32_t ea = ((o >> a) & 1u) ? ~0u : 1u, eb = ((o >> b) & 1u) ? ~0u : 1u, ec = ((o >> c) & 1u) ? ~0u : 1u;
+    const uint32_t top = k > VPX_WID_CAP ? k : VPX_WID_CAP;
+    uint32_t q[3];
+    uint32_t M = k;
+    while (M < top) {
+        q[b] = p[b] + eb * M;
+        if (q[b] >= nb1) return top;
+        uint32_t layers = 1u;
+        for (uint32_t m = 0; m < k;) {
+            q[c] = p[c] + ec * m;
+            if (q[c] >= nb1) break;  // the rest of the layer lies outside the grid
+            uint32_t rows = 1u;
+            for (uint32_t i = 0; i < L;) {
+                q[a] = p[a] + ea * i;
+                if (q[a] >= nb1) break;
+                const uint32_t w = word(q[0], q[1], q[2]);
+                if (!w) return M;
+                const uint32_t k2 = w & 255u, L2 = (w >> 8) & 255u;
+                if (i == 0u && L2 >= L) {
+                    rows = k2;
+                    if (m == 0u && k2 >= k) layers = k2;
+                }
+                i += L2;
+            }
+            m += rows;
+        }
+        M += layers;
+    }
+    return top;
+}
+// Both width bytes of brick (x, y, z)'s word in plane (o, a), as the word's high half.
+template <class Word>
+VPX_HD uint32_t axis_wids(uint32_t x, uint32_t y, uint32_t z, uint32_t o, uint32_t a, uint32_t k, uint32_t L, uint32_t nb1, Word word) {
+    const uint32_t p[3] = {x, y, z};
+    const uint32_t b = a == 0u ? 1u : 0u, c = a == 2u ? 1u : 2u;
+    return axis_wid(p, o, a, b, c, k, L, nb1, word) | axis_wid(p, o, a, c, b, k, L, nb1, word) << 8;
 }
 
 #if !defined(__HIP_DEVICE_COMPILE__)
@@ -914,6 +985,34 @@ inline void build_axis_planes_host(const uint8_t* dfp, uint32_t n, uint16_t* dfa
                     if (!k) continue;
                     for (uint32_t a = 0; a < 3; ++a)
                         dfa[(o * 3 + a) * plane + b] = (uint16_t)(k | axis_len(x, y, z, o, a, k, nb1, cube) << 8);
+                }
+    }
+}
+
+// The axis planes with the widths (as build_axis_k, then build_wide_k): dfw holds
+// 24 * nb2^3 * 64 words.
+inline void build_wide_planes_host(const uint8_t* dfp, uint32_t n, uint32_t* dfw) {
+    const uint32_t nb1 = (n + 3) / 4, nb2 = (nb1 + 3) / 4;
+    const uint64_t plane = 64ull * nb2 * nb2 * nb2;
+    std::memset(dfw, 0, 4 * 24 * plane);
+    for (uint32_t oa = 0; oa < 24; ++oa) {  // the low halves first: the widths read them
+        const uint8_t* pl = dfp + (oa / 3u) * plane;
+        auto cube = [&](uint32_t x, uint32_t y, uint32_t z) -> uint32_t { return pl[blk_index(x, y, z, nb2)]; };
+        for (uint32_t z = 0; z < nb1; ++z)
+            for (uint32_t y = 0; y < nb1; ++y)
+                for (uint32_t x = 0; x < nb1; ++x) {
+                    const uint32_t b = blk_index(x, y, z, nb2), k = pl[b];
+                    if (k) dfw[oa * plane + b] = k | axis_len(x, y, z, oa / 3u, oa % 3u, k, nb1, cube) << 8;
+                }
+    }
+    for (uint32_t oa = 0; oa < 24; ++oa) {
+        uint32_t* pl = dfw + oa * plane;
+        auto word = [&](uint32_t x, uint32_t y, uint32_t z) -> uint32_t { return pl[blk_index(x, y, z, nb2)] & 0xffffu; };
+        for (uint32_t z = 0; z < nb1; ++z)
+            for (uint32_t y = 0; y < nb1; ++y)
+                for (uint32_t x = 0; x < nb1; ++x) {
+                    const uint32_t b = blk_index(x, y, z, nb2), kl = pl[b] & 0xffffu;
+                    if (kl) pl[b] = kl | axis_wids(x, y, z, oa / 3u, oa % 3u, kl & 255u, kl >> 8, nb1, word) << 16;
                 }
     }
 }

@@ -429,10 +429,10 @@ __device__ __forceinline__ T* uni_ptr(T* p) {
     return (T*)(((uint64_t)uni((uint32_t)(v >> 32)) << 32) | uni((uint32_t)v));
 }
 __device__ __forceinline__ skip::GridView grid_view(const DevGrid& g) {
-    // the axis planes follow the 8 octant planes in the same buffer (build_df)
+    // the axis planes (32-bit words, skip::GridView::dfw) follow the 8 octant planes in the same buffer (build_df)
     const uint8_t* dfp = uni_ptr(g.dfp);
     return skip::GridView{uni_ptr(g.cells), uni_ptr(g.l1), uni_ptr(g.l2), uni(g.n), uni(g.nb1), uni(g.nb2),
-                          uni(g.nb3),       dfp,            g.plane,        (const uint16_t*)(dfp + 8u * g.plane)};
+                          uni(g.nb3),       dfp,            g.plane,        nullptr,  (const uint32_t*)(dfp + 8u * g.plane)};
 }
 __device__ __forceinline__ skip::Walk to_walk(const Dda& s) {
     skip::Walk w;
@@ -460,7 +460,7 @@ constexpr uint32_t kSkipwNearest = 1, kSkipwBounce = 2, kSkipwShadow = 4;
 #endif
 constexpr uint32_t kMincNearest = VPX_MINC_NEAREST, kMincBounce = 2, kMincShadow = 1;
 // Brick runs per walk kind, the RUN word: cap | passes << 8 | seg2 << 17 | min2 << 18 |
-// axis << 19 | minlen << 20.
+// axis << 19 | minlen << 20 | wide << 24 | local << 25.
 // After its octant-plane byte (and, in an occupied brick, its cell mask) loads, a lane
 // steps up to `cap` cells inside its 4^3 brick on the register copy; `passes` brick loads
 // per step-phase iteration.  Measured (ms, one box): primary C1 0.432 -> 0.402 with 3|2<<8;
@@ -475,8 +475,8 @@ constexpr uint32_t kMincNearest = VPX_MINC_NEAREST, kMincBounce = 2, kMincShadow
 // interleaved runs, vs the three-compare form): C1 0.678 vs 0.687; the shadow walkers (72
 // VGPRs, 7 waves/SIMD) spilled two more VGPRs with it and C3 went 5.26 -> 5.53, so they keep
 // the three-compare form.
-// axis (bit 19): the walk's boxes come from the axis planes (skip::GridView::dfa): the brick's
-// cube extended along the ray's dominant axis, one 16-bit load per step instead of the octant
+// axis (bit 19): the walk's boxes come from the axis planes (skip::GridView::dfw): the brick's
+// cube extended along the ray's dominant axis, one 32-bit load per step instead of the octant
 // plane's byte.  minlen (bits 20-23): an empty brick whose cube is below the skip minimum
 // still skips when its box is at least this many bricks long.  VPX_AXIS_BOXES sets the bit for
 // every walk kind that has no word of its own on the command line.  Measured (ms per step, one
@@ -494,17 +494,37 @@ constexpr uint32_t kMincNearest = VPX_MINC_NEAREST, kMincBounce = 2, kMincShadow
 #ifndef VPX_AXIS_MINLEN
 #define VPX_AXIS_MINLEN 2u
 #endif
-#define VPX_RUN_AXIS ((VPX_AXIS_BOXES ? 1u : 0u) << 19 | VPX_AXIS_MINLEN << 20)
+// wide (bit 24, with axis): the box is also widened along the ray's second axis (skip::sec_axis)
+// to the word's Mb or Mc, from the same load.  VPX_WIDE_BOXES sets it like VPX_AXIS_BOXES.
+// Measured (ms per step, three interleaved runs each of the build on the 16-bit planes and this
+// one): C1 0.4644-0.4729 -> 0.4436-0.4457, C3 3.352-3.376 -> 3.212-3.227, C4 25.41-25.57 ->
+// 24.84-25.22; C2 2.043-2.076 -> 2.005-2.057 and Z1 1.480-1.498 -> 1.496-1.522 count as unchanged.
+// local (bit 25, with axis): the skip phase works its axes out from the tdeltas each time, behind
+// a barrier.  The compares are the same all walk long, and the compiler hoists them out of the
+// loop: in the 72- and 80-VGPR kernels (k_frame0, the shadow walkers, k_primary) their results then
+// sat in scratch and were reloaded in every skip phase.  The bounce walks (k_tail, k_nearest_tile,
+// k_nearest_pool) have the registers to keep them and Z1 lost 2 % with the bit in every kind, so
+// every kind but the bounce one has it.  VPX_LOCAL_AXES=1 sets it
+// for every kind, 0 for none.
+#ifndef VPX_WIDE_BOXES
+#define VPX_WIDE_BOXES 1
+#endif
+#ifdef VPX_LOCAL_AXES
+#define VPX_RUN_LOCAL(on) ((VPX_LOCAL_AXES ? 1u : 0u) << 25)
+#else
+#define VPX_RUN_LOCAL(on) ((on) << 25)
+#endif
+#define VPX_RUN_AXIS ((VPX_AXIS_BOXES ? 1u : 0u) << 19 | VPX_AXIS_MINLEN << 20 | (VPX_AXIS_BOXES && VPX_WIDE_BOXES ? 1u : 0u) << 24)
 #ifndef VPX_RUN_NEAREST
-#define VPX_RUN_NEAREST (3u | 3u << 8 | 1u << 17 | 1u << 18 | VPX_RUN_AXIS)
+#define VPX_RUN_NEAREST (3u | 3u << 8 | 1u << 17 | 1u << 18 | VPX_RUN_AXIS | VPX_RUN_LOCAL(1u))
 #endif
 constexpr uint32_t kRunNearest = VPX_RUN_NEAREST;
 #ifndef VPX_RUN_BOUNCE
-#define VPX_RUN_BOUNCE (4u | 1u << 8 | 0u << 17 | 1u << 18 | VPX_RUN_AXIS)
+#define VPX_RUN_BOUNCE (4u | 1u << 8 | 0u << 17 | 1u << 18 | VPX_RUN_AXIS | VPX_RUN_LOCAL(0u))
 #endif
 constexpr uint32_t kRunBounce = VPX_RUN_BOUNCE;
 #ifndef VPX_RUN_SHADOW
-#define VPX_RUN_SHADOW (3u | 1u << 8 | 1u << 17 | 0u << 18 | VPX_RUN_AXIS)
+#define VPX_RUN_SHADOW (3u | 1u << 8 | 1u << 17 | 0u << 18 | VPX_RUN_AXIS | VPX_RUN_LOCAL(1u))
 #endif
 constexpr uint32_t kRunShadow = VPX_RUN_SHADOW;
 // Round 5 (ms per step, three interleaved runs, tools/gpu_ab.sh): FindNearest runs of 3 cells in
@@ -516,13 +536,13 @@ constexpr uint32_t kRunShadow = VPX_RUN_SHADOW;
 // 0.5433-0.5444 vs 0.5456-0.5482 ms in three, then 0.5427-0.5457 vs 0.5447-0.5484 (two boxes,
 // three interleaved runs each); five passes 0.5464-0.5474, runs of 2 in four 0.5428-0.5472.
 #ifndef VPX_RUN_FRAME_NEAREST
-#define VPX_RUN_FRAME_NEAREST (3u | 4u << 8 | 1u << 17 | 1u << 18 | VPX_RUN_AXIS)
+#define VPX_RUN_FRAME_NEAREST (3u | 4u << 8 | 1u << 17 | 1u << 18 | VPX_RUN_AXIS | VPX_RUN_LOCAL(1u))
 #endif
 constexpr uint32_t kRunFrameNearest = VPX_RUN_FRAME_NEAREST;
 // At 7 waves/SIMD the frame's shadow walks take the two-compare step too: C1 0.5418-0.5489 vs
 // 0.5456-0.5539 ms (seven interleaved runs, all won; three passes 0.5479-0.5591).
 #ifndef VPX_RUN_FRAME_SHADOW
-#define VPX_RUN_FRAME_SHADOW (3u | 2u << 8 | 1u << 17 | 1u << 18 | VPX_RUN_AXIS)
+#define VPX_RUN_FRAME_SHADOW (3u | 2u << 8 | 1u << 17 | 1u << 18 | VPX_RUN_AXIS | VPX_RUN_LOCAL(1u))
 #endif
 constexpr uint32_t kRunFrameShadow = VPX_RUN_FRAME_SHADOW;
 // The pools' walks (k_nearest_pool, k_shadow_pool: 96 VGPRs at 5 waves/SIMD) have their own
@@ -533,7 +553,7 @@ constexpr uint32_t kRunFrameShadow = VPX_RUN_FRAME_SHADOW;
 // weight 1 / 4, runs of 3 cells in two passes measured C2 2.63-2.66 / 2.60-2.64 / 2.66-2.75 /
 // 2.65-2.71 vs 2.59-2.65 ms, and re-checked at three lanes in round 5 (within noise).
 #ifndef VPX_RUN_SHADOW_POOL
-#define VPX_RUN_SHADOW_POOL (3u | 1u << 8 | 1u << 17 | 1u << 18 | VPX_RUN_AXIS)
+#define VPX_RUN_SHADOW_POOL (3u | 1u << 8 | 1u << 17 | 1u << 18 | VPX_RUN_AXIS | VPX_RUN_LOCAL(1u))
 #endif
 #ifndef VPX_SKIPW_SHADOW_POOL
 #define VPX_SKIPW_SHADOW_POOL 4u
@@ -577,6 +597,9 @@ __device__ __forceinline__ bool walk_wave(const skip::GridView& g, skip::Walk& w
     constexpr bool kMin2 = (RUN >> 18) & 1u;  // step1's two-compare axis choice (vpx_skip.hpp)
     constexpr bool kAxis = (RUN >> 19) & 1u;  // boxes from the axis planes (skip::classify_axis_o)
     constexpr uint32_t kMinLen = (RUN >> 20) & 15u;
+    constexpr bool kWide = (RUN >> 24) & 1u;  // ... widened along the second axis (skip::wid_dfw)
+    constexpr bool kLocal = (RUN >> 25) & 1u;  // the skip phase's axes behind a barrier
+    static_assert(!kWide || kAxis, "walk_wave: wide boxes are axis boxes");
     static_assert(SKIPW > 0 && kRun > 0 && kPasses > 0, "walk_wave: skip weight, run cap and passes");
     static_assert(!kAxis || kMinLen > 0, "walk_wave: the axis boxes' minimum length");
     // the ray's plane: its octant's, or its (octant, dominant axis)'s
@@ -647,8 +670,14 @@ __device__ __forceinline__ bool walk_wave(const skip::GridView& g, skip::Walk& w
         VPX_MARK("skip phase");
         if (mode == kSkip) {
             uint32_t lo[3], hi[3];
-            if (kAxis) skip::df_box_axis(w, g.n, skip::cube_dfp(w), skip::len_dfa(w), skip::dom_axis(w), lo, hi);
-            else skip::df_box(w, g.n, skip::cube_dfp(w), lo, hi);
+            if (kAxis) {
+                float dx = w.dx, dy = w.dy, dz = w.dz;
+                if (kLocal) asm volatile("" : "+v"(dx), "+v"(dy), "+v"(dz));  // not hoisted (the RUN word's local)
+                const uint32_t axis = skip::dom_axis(dx, dy, dz), sec = kWide ? skip::sec_axis(axis, dx, dy, dz) : 3u;
+                skip::df_box_axis(w, g.n, skip::cube_dfp(w), skip::len_dfa(w), axis, lo, hi, sec, kWide ? skip::wid_dfw(w, axis, sec) : 0u);
+            } else {
+                skip::df_box(w, g.n, skip::cube_dfp(w), lo, hi);
+            }
             const int sr = skip::skip_box_lean<kSeg2Branch>(w, lo, hi, bound, cells);  // 2 (refused): a plain step
             VPX_MARK("skip end");
             VPX_PH(fb += __popcll(__ballot(sr == 2));)

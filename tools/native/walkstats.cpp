@@ -58,9 +58,13 @@ extern "C" void build_slabs(const uint8_t* bocc, uint32_t nb) {  // bocc[z][y][x
 // axis planes (vpx_skip.hpp GridView::dfa) of its octant and dominant axis — the cube's
 // cross-section, extended along that axis.  This is the model of the walkers' axis switch.
 static std::vector<uint8_t> g_dfp;
+// Wide boxes (set_wide(1) on top of set_axis): the words of GridView::dfw, the box widened along
+// the walk's second axis (sec_axis) to Mb or Mc — the model of the walkers' wide switch.
 static std::vector<uint16_t> g_dfa;
-static int g_axis = 0;
+static std::vector<uint32_t> g_dfw;
+static int g_axis = 0, g_wide = 0;
 extern "C" void set_axis(int minl) { g_axis = minl; }
+extern "C" void set_wide(int on) { g_wide = on; }
 extern "C" void build_axis(const uint64_t* l1, const uint64_t* l2, uint32_t n) {
     const uint32_t nb1 = (n + 3) / 4, nb2 = (nb1 + 3) / 4;
     const size_t plane = 64ull * nb2 * nb2 * nb2;
@@ -68,6 +72,8 @@ extern "C" void build_axis(const uint64_t* l1, const uint64_t* l2, uint32_t n) {
     g_dfa.assign(24 * plane, 0);
     build_planes_host(l1, l2, n, g_dfp.data());
     build_axis_planes_host(g_dfp.data(), n, g_dfa.data());
+    g_dfw.assign(24 * plane, 0);
+    build_wide_planes_host(g_dfp.data(), n, g_dfw.data());
 }
 static uint64_t g_slabskips;
 static uint64_t g_seg2[4];  // skips by the number of axes that need the second closed-form segment
@@ -100,10 +106,12 @@ extern "C" void walk_sim(const uint8_t* cells, const uint64_t* l1, const uint64_
             bool slab = false;
             if (g_axis && cls >= 2) {
                 const uint32_t a = dom_axis(w);
-                const uint32_t kl = g_dfa[(size_t)plane_parent(g, (w.osh >> 3) * 3u + a) * 64 + blk_index(w.X >> 2, w.Y >> 2, w.Z >> 2, nb2)];
-                const uint32_t k = kl & 255u, L = kl >> 8;
+                const size_t wi = (size_t)plane_parent(g, (w.osh >> 3) * 3u + a) * 64 + blk_index(w.X >> 2, w.Y >> 2, w.Z >> 2, nb2);
+                const uint32_t kl = g_wide ? g_dfw[wi] : g_dfa[wi];
+                const uint32_t k = kl & 255u, L = (kl >> 8) & 255u;
+                const uint32_t sec = g_wide ? sec_axis(w) : 3u, M = (kl >> (sec < 3u - a - sec ? 16u : 24u)) & 255u;
                 cls = (k >= kMinCube || L >= (uint32_t)g_axis) ? 2 : 3;
-                if (cls == 2) df_box_axis(w, n, k, L, a, slo, shi), slab = true;
+                if (cls == 2) df_box_axis(w, n, k, L, a, slo, shi, sec, M), slab = true;
             }
             if (g_mode && cls != 0) {
                 const uint32_t bb = ((w.X >> 2) & 3u) | (((w.Y >> 2) & 3u) << 2) | (((w.Z >> 2) & 3u) << 4);

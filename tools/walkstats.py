@@ -1,5 +1,6 @@
 """Per-ray walk statistics of the skipping walker on a config's world (CPU model):
-python tools/walkstats.py [C1|C2|C3], MODES="0 -2" (cubes, then axis boxes of minimum length 2)."""
+python tools/walkstats.py [C1|C2|C3], MODES="0 -2 -102" (cubes, axis boxes of minimum length 2, then
+the same boxes widened along the second axis)."""
 import ctypes as C, os, subprocess, sys
 import numpy as np
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -92,13 +93,16 @@ lib.slab_out.restype = C.c_uint64
 lib.build_axis.argtypes = [V, V, C.c_uint32]
 lib.build_axis(l1.ctypes.data, l2.ctypes.data, n)
 lib.set_axis.argtypes = [C.c_int]
-# MODES: 0 cubes, n > 0 the slab experiment, -n axis boxes with minimum length n (AXIS model)
-modes = [int(x) for x in os.environ.get("MODES", "0 -2").split()]
+lib.set_wide.argtypes = [C.c_int]
+# MODES: 0 cubes, n > 0 the slab experiment, -n axis boxes with minimum length n (AXIS model),
+# -100 - n the same widened along the second axis (WIDE model)
+modes = [int(x) for x in os.environ.get("MODES", "0 -2 -102").split()]
 lib.set_full.argtypes = [C.c_int]
 lib.set_full(int(os.environ.get("FULL", "0")))  # 1: whole boxes (the exact multi-binade tier)
 for name, (a, b, bnd), mode in [(nm_, v, md) for nm_, v in sets.items() for md in modes]:
     lib.set_mode(max(mode, 0))
-    lib.set_axis(max(-mode, 0))
+    lib.set_axis(max(-mode, 0) % 100)
+    lib.set_wide(1 if mode <= -100 else 0)
     R = len(a)
     o = sim(a, b, bnd)
     print(f"mode {mode}: slab skips {lib.slab_out() / R:.1f} per ray")

@@ -1,6 +1,9 @@
 """Wave-cost model of the primary walk: per-ray (steps, skips) from the CPU walker on whole
 16x16 tiles, then the cost of 64-lane waves (max over lanes) without and with compacting
-the unfinished rays of a tile after a budget.  Usage: python tools/wavecost.py [C1]"""
+the unfinished rays of a tile after a budget.  Then the wave cost of the primary walks and of the
+shadow walks toward the first point light, for the walkers' three box kinds (cubes, axis boxes,
+wide boxes), lanes in the kernel's 8x8-per-wave order and each tile's shadow rays compacted.
+Usage: [TILES=400] python tools/wavecost.py [C1]"""
 import ctypes as C, os, subprocess, sys
 import numpy as np
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -22,7 +25,7 @@ lib.build_masks.argtypes = [V, C.c_uint32, V, V]
 lib.build_masks(cells.ctypes.data, n, l1.ctypes.data, l2.ctypes.data)
 W, H = d.width, d.height
 rng = np.random.default_rng(1)
-T = 200
+T = int(os.environ.get("TILES", "200"))
 tx, ty = rng.integers(0, W // 16, T), rng.integers(0, H // 16, T)
 xs = (tx[:, None] * 16 + np.arange(256)[None, :] % 16).reshape(-1)
 ys = (ty[:, None] * 16 + np.arange(256)[None, :] // 16).reshape(-1)
@@ -90,3 +93,51 @@ for q in (4, 8, 16):  # coarse buckets of the cost (what a counting sort on a qu
         key = np.minimum((c * q / max(c.max() if len(c) else 1, 1)).astype(int), q - 1)
         tot += waves(c[np.argsort(key, kind="stable")])
     print(f"  {q} cost buckets: {tot:.0f} ({tot / base:.2f})")
+
+# ---- the box kinds: primary + shadow wave cost (DESIGN.md section 4's model tables)
+lib.build_axis.argtypes = [V, V, C.c_uint32]
+lib.build_axis(l1.ctypes.data, l2.ctypes.data, n)
+lib.set_mode.argtypes = lib.set_axis.argtypes = lib.set_wide.argtypes = [C.c_int]
+lib.set_mode(0)
+lane = np.arange(256)
+w8 = lane // 64
+perm = ((w8 // 2) * 8 + (lane % 64) // 8) * 16 + (w8 % 2) * 8 + lane % 8  # pixel (row-major in the tile) of lane i
+light = np.float32(d.points[0].position[:]) if len(d.points) else np.float32([0.5, 1.5, 0.5])
+def run(st_, si_, bnd_):
+    per_, out_, th_ = np.zeros((len(st_), 2), np.uint32), np.zeros(8, np.uint64), np.zeros(len(st_), np.float32)
+    lib.walk_sim(cells.ctypes.data, l1.ctypes.data, l2.ctypes.data, n, np.ascontiguousarray(st_).ctypes.data,
+                 np.ascontiguousarray(si_).ctypes.data, np.ascontiguousarray(bnd_, np.float32).ctypes.data, len(st_),
+                 out_.ctypes.data, th_.ctypes.data, per_.ctypes.data)
+    return per_, out_, th_
+first = None
+for name, axis, wide in (("cubes", 0, 0), ("axis boxes", 2, 0), ("wide boxes", 2, 1)):
+    lib.set_axis(axis); lib.set_wide(wide)
+    per, out, th = run(st, si, bnd)
+    hit = ok & (th > 0)
+    cp_ = np.where(ok, per[:, 0] + per[:, 1] + 1 + SKIP * per[:, 1], 0).reshape(T, 256)[:, perm]
+    okp = ok.reshape(T, 256)[:, perm]
+    prim = sum(waves(cp_[t][okp[t]]) for t in range(T))
+    # shadow rays from every hit toward the light (no facing test), DDA state as the primary's
+    org = ((cp + D * th[:, None]) - D * np.float32(2e-4)).astype(np.float32)
+    dl = light - org
+    dist = np.sqrt((dl * dl).sum(1)).astype(np.float32)
+    sd = (dl / dist[:, None]).astype(np.float32)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        srD = (np.float32(1) / sd).astype(np.float32)
+    sds = (sd < 0).astype(np.float32)
+    spos = (org + sd * np.float32(5e-5)) * np.float32(n)
+    sP0 = np.clip(np.nan_to_num(spos).astype(np.int64), 0, n - 1)
+    sstep = (1 - 2 * sds).astype(np.int32)
+    sst = np.concatenate([np.zeros((len(org), 1), np.float32), ((np.ceil(spos) - sds) * cell - org) * srD,
+                          (cell * sstep.astype(np.float32)) * srD], 1).astype(np.float32)
+    ssi = np.concatenate([sP0, sstep], 1).astype(np.int32)
+    sper, sout, _ = run(sst[hit], ssi[hit], dist[hit])
+    cs_ = np.zeros(len(st)); cs_[hit] = sper[:, 0] + sper[:, 1] + 1 + SKIP * sper[:, 1]
+    cs_ = cs_.reshape(T, 256)[:, perm]; hp = hit.reshape(T, 256)[:, perm]
+    shad = sum(waves(cs_[t][hp[t]]) for t in range(T))
+    tot = prim + shad
+    first = first or tot
+    print(f"  {name:10s}: primary skips/ray {per[ok, 1].mean():.2f} (max {per[ok, 1].max()}) steps {per[ok, 0].mean():.2f}, "
+          f"shadow skips/ray {sper[:, 1].mean():.2f} (max {sper[:, 1].max()}) steps {sper[:, 0].mean():.2f}; mean cost "
+          f"{cp_[okp].mean():.1f} / {cs_[hp].mean():.1f}; wave cost {prim:.0f} + {shad:.0f} = {tot:.0f} ({tot / first - 1:+.1%}); "
+          f"hits {int(hit.sum())} occluded {int(sout[3])} sum of hit t bits {int(out[5])}")
