@@ -25,6 +25,9 @@
  *                         Scene::IsOccluded           template/scene.cpp:1009-1047
  *   vpx_trace             Renderer::Trace(Ray&, int)  renderer.cpp:1076
  *   vpx_focus_distance    focus ray in Renderer::Tick renderer.cpp:1987-1991
+ *   vpx_get_player_light  Renderer::inLight           renderer.h:231; set renderer.cpp:1228-1240,
+ *                                                     1438-1450; read :2112-2118, cleared :2206
+ *   vpx_trace_probe       Trace's smoke-branch probe  renderer.cpp:1228-1240 (per ray)
  *   vpx_upload_grid       Scene::grid (owned by host) template/scene.h:258
  *   vpx_set_volumes       Renderer::voxelVolumes      renderer.h:211
  *   vpx_set_materials     Renderer::materials         renderer.h:190, MaterialSetUp renderer.cpp:357-443
@@ -412,6 +415,26 @@ int vpx_render_reproject(vpx_ctx* ctx, const vpx_frame_params* params, const vpx
    (no per-frame synchronisation); kernel_ms/total_ms are not filled here.            */
 int vpx_get_counters(vpx_ctx* ctx, vpx_stats* out, int reset);
 
+/* ---- the player light probe (Renderer::inLight, renderer.h:231) ---------------------- */
+/* A path that reaches smoke (materials 9..14) in volume 0, the player, runs
+   Illumination(ray, incLight) and sets Renderer::inLight when sqrLength(incLight) exceeds
+   sqrThreshold (Trace renderer.cpp:1228-1240, TraceSmoke :1438-1450).  Renderer::Tick reads
+   the flag (:2112-2118) and clears it (:2206).  The record accumulates on the device over
+   every render call since the last reset (vpx_render, vpx_render_tiles[_accum], the window
+   entries, vpx_render_reproject; a device set sums its members and takes the largest
+   max_sqr), with no per-frame synchronisation; the read synchronises like
+   vpx_get_counters.  Counts and maximum do not depend on execution order.  The unit
+   entries (vpx_trace, vpx_trace_probe) do not add to it; vpx_get_counters' reset does not
+   clear it, and this reset leaves the work counters alone. */
+#define VPX_PLAYER_LIGHT_SQR 16.0f            /* sqrThreshold, renderer.cpp:1233, 1443 */
+typedef struct vpx_player_light {             /* 24 bytes */
+    uint64_t probes;    /* probe Illumination calls: paths that reached smoke in volume 0 */
+    uint64_t lit;       /* of them, sqrLength(incLight) > VPX_PLAYER_LIGHT_SQR (a NaN is not) */
+    float    max_sqr;   /* largest sqrLength(incLight) seen (NaNs apart), 0 when none */
+    uint32_t in_light;  /* lit != 0: Renderer::inLight */
+} vpx_player_light;
+int vpx_get_player_light(vpx_ctx* ctx, vpx_player_light* out, int reset);
+
 /* ---- per-stage profile (measurement; off by default) ------------------------------ */
 /* Stages of one vpx_render / vpx_render_tiles call. */
 #define VPX_STAGE_PRIMARY 0  /* primary rays + Renderer::FindNearest                   */
@@ -456,6 +479,14 @@ int vpx_is_occluded(vpx_ctx* ctx, const vpx_ray* rays, uint32_t n, uint8_t* occl
    sky: the constant SampleSky colour (activateSky == false), or NULL for the texture. */
 int vpx_trace(vpx_ctx* ctx, const vpx_ray* rays, const uint32_t* seeds, uint32_t n,
               int32_t depth, const float sky[3], int32_t area_samples, float* radiance);
+/* vpx_trace plus each ray's player light probes (the smoke branch's Illumination call in
+   volume 0, renderer.cpp:1228-1240; a path can probe once per level): their number, how many
+   exceeded VPX_PLAYER_LIGHT_SQR and the largest sqrLength(incLight).  radiance (may be NULL)
+   is bit-identical to vpx_trace's; probes = vpx_ray_probe[n], host. */
+typedef struct vpx_ray_probe { uint32_t probes, lit; float max_sqr; uint32_t reserved; } vpx_ray_probe; /* 16 */
+int vpx_trace_probe(vpx_ctx* ctx, const vpx_ray* rays, const uint32_t* seeds, uint32_t n, int32_t depth,
+                    const float sky[3], int32_t area_samples, float* radiance /* may be NULL */,
+                    vpx_ray_probe* probes /* n, host */);
 /* Focus ray of Renderer::Tick (world-space ray against every Scene::FindNearest). */
 int vpx_focus_distance(vpx_ctx* ctx, uint32_t width, uint32_t height, float* focal_distance);
 

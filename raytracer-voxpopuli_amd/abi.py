@@ -88,6 +88,20 @@ class Stats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class PlayerLight(C.Structure):  # vpx_player_light: Renderer::inLight (renderer.h:231) and what is behind it
+    _fields_ = [("probes", C.c_uint64), ("lit", C.c_uint64), ("max_sqr", C.c_float), ("in_light", C.c_uint32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class RayProbe(C.Structure):  # vpx_ray_probe: one ray's player light probes (vpx_trace_probe)
+    _fields_ = [("probes", C.c_uint32), ("lit", C.c_uint32), ("max_sqr", C.c_float), ("reserved", C.c_uint32)]
+
+
+PLAYER_LIGHT_SQR = 16.0  # VPX_PLAYER_LIGHT_SQR: sqrThreshold, renderer.cpp:1233, 1443
+
+
 class PrevCamera(C.Structure):
     _fields_ = [("cam_pos", f3), ("left_normal", f3), ("right_normal", f3), ("top_normal", f3),
                 ("bottom_normal", f3), ("pad", C.c_float)]
@@ -114,7 +128,7 @@ STAGES = ("primary", "shade", "shadow", "resolve", "bounce", "finish", "frame", 
 
 STRUCT_SIZES = {PrevCamera: 64, Profile: 160, Volume: 160, Material: 32, PointLight: 24, SpotLight: 40, AreaLight: 32, DirLight: 24,
                 Sphere: 32, Triangle: 64, Camera: 80, FrameParams: 48, Ray: 32, Hit: 32, Stats: 40,
-                BvhTri: 36, BvhNode: 32}
+                BvhTri: 36, BvhNode: 32, PlayerLight: 24, RayProbe: 16}
 
 
 def np_dtype(struct):
@@ -184,6 +198,9 @@ SIGNATURES = {
     "vpx_is_occluded": (C.c_int, [C.c_void_p, C.POINTER(Ray), C.c_uint32, C.c_void_p]),
     "vpx_trace": (C.c_int, [C.c_void_p, C.POINTER(Ray), C.c_void_p, C.c_uint32, C.c_int32, C.POINTER(C.c_float),
                             C.c_int32, C.c_void_p]),
+    "vpx_trace_probe": (C.c_int, [C.c_void_p, C.POINTER(Ray), C.c_void_p, C.c_uint32, C.c_int32, C.POINTER(C.c_float),
+                                  C.c_int32, C.c_void_p, C.POINTER(RayProbe)]),
+    "vpx_get_player_light": (C.c_int, [C.c_void_p, C.POINTER(PlayerLight), C.c_int]),
     "vpx_focus_distance": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_float)]),
     "vpx_camera_look_at": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_uint32, C.c_uint32,
                                      C.POINTER(Camera)]),

@@ -227,6 +227,13 @@ class Context:
         self._chk(self.lib.vpx_get_counters(self.h, C.byref(st), 1 if reset else 0), "vpx_get_counters")
         return st
 
+    def player_light(self, reset=False):
+        """The player light record since the last reset (vpx_get_player_light): abi.PlayerLight
+        with probes, lit, max_sqr and in_light = Renderer::inLight (renderer.h:231).  Synchronises."""
+        pl = abi.PlayerLight()
+        self._chk(self.lib.vpx_get_player_light(self.h, C.byref(pl), 1 if reset else 0), "vpx_get_player_light")
+        return pl
+
     # ------------------------------------------------------------- unit entries
     def find_nearest(self, rays):
         n = len(rays)
@@ -248,6 +255,18 @@ class Context:
         self._chk(self.lib.vpx_trace(self.h, rays, seeds.ctypes.data_as(C.c_void_p), n, depth, abi.sky_arg(sky),
                                      area_samples, out.ctypes.data_as(C.c_void_p)), "vpx_trace")
         return out[:n]
+
+    def trace_probe(self, rays, seeds, depth, sky=abi.SKY_DEFAULT, area_samples=3, radiance=True):
+        """trace() plus each ray's player light probes (vpx_trace_probe): (radiance or None,
+        record array with probes, lit, max_sqr, reserved)."""
+        n = len(rays)
+        seeds = np.ascontiguousarray(seeds, np.uint32)
+        out = np.zeros((max(1, n), 3), np.float32) if radiance else None
+        pr = np.zeros(max(1, n), abi.np_dtype(abi.RayProbe))
+        self._chk(self.lib.vpx_trace_probe(self.h, rays, seeds.ctypes.data_as(C.c_void_p), n, depth, abi.sky_arg(sky),
+                                           area_samples, out.ctypes.data_as(C.c_void_p) if radiance else None,
+                                           abi.as_ptr(pr, abi.RayProbe)), "vpx_trace_probe")
+        return (out[:n] if radiance else None), pr[:n]
 
     def focus_distance(self, width, height):
         f = C.c_float()

@@ -232,6 +232,20 @@ __global__ __launch_bounds__(256) void trace_k(SceneView sv, const vpx_ray* rays
     out[3 * i] = v.x, out[3 * i + 1] = v.y, out[3 * i + 2] = v.z;
 }
 
+// vpx_trace_probe: trace_k plus the ray's player light probes (out may be null).
+template <int LEVELS>
+__global__ __launch_bounds__(256) void trace_probe_k(SceneView sv, const vpx_ray* rays, const uint32_t* seeds, uint32_t n,
+                                                     int32_t depth, float* out, vpx_ray_probe* probes) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    Rng g{seeds[i]};
+    Counters k{0u, 0u, 0u};
+    PathProbe pp{0u, 0u, 0u};
+    const f3 v = trace_path<LEVELS, true>(sv, ray_from(rays[i]), depth, g, k, &pp);
+    if (out) out[3 * i] = v.x, out[3 * i + 1] = v.y, out[3 * i + 2] = v.z;
+    probes[i] = vpx_ray_probe{pp.probes, pp.lit, __uint_as_float(pp.max_bits), 0u};
+}
+
 __global__ void focus_k(SceneView sv, FrameArgs f, float* out) {
     // Renderer::Tick focus ray (renderer.cpp:1987-1991): integer screen centre, no lens
     // jitter, tested against each Scene in WORLD space (no instance transform).
@@ -1850,8 +1864,14 @@ int vpx_set_materials(vpx_ctx* c, const vpx_material* m, uint32_t count) {
     for (auto& e : full) e = vpx_material{{1, 1, 1}, 1.0f, 0.0f, 1.5f, {0, 0}};
     std::memcpy(full, m, sizeof(vpx_material) * count);
     VPX_HIP(c, sync_all(c));
-    int rc = upload_table(c, c->d_materials, full, VPX_NUM_MATERIALS);
-    if (rc) return rc;
+    // the table's allocation is made once and ends in the player light record (probe_record):
+    // a new table leaves what the record has accumulated
+    if (!c->d_materials) {
+        static_assert(sizeof(full) == kProbeOffset, "the table's size is the record's offset");
+        VPX_HIP(c, hipMalloc(&c->d_materials, kMaterialTableBytes));
+        VPX_HIP(c, hipMemsetAsync(probe_record_of(c->d_materials), 0, kProbeBytes, c->stream));
+    }
+    VPX_HIP(c, hipMemcpyAsync(c->d_materials, full, sizeof(full), hipMemcpyHostToDevice, c->stream));
     VPX_HIP(c, sync_all(c));
     c->have_materials = true;
     return VPX_OK;
@@ -2291,6 +2311,44 @@ int vpx_get_counters(vpx_ctx* c, vpx_stats* out, int reset) {
     return VPX_OK;
 }
 
+int vpx_get_player_light(vpx_ctx* c, vpx_player_light* out, int reset) {
+    if (!c || !out) return fail(c, VPX_E_INVALID, "null argument");
+    std::memset(out, 0, sizeof(*out));
+    if (!c->members.empty()) {  // sums over the devices, the largest maximum
+        const int rc = group_all(c, [&](vpx_ctx* m) {
+            vpx_player_light one;
+            const int r = vpx_get_player_light(m, &one, reset);
+            out->probes += one.probes, out->lit += one.lit;
+            out->max_sqr = std::max(out->max_sqr, one.max_sqr);
+            return r;
+        });
+        out->in_light = out->lit ? 1u : 0u;
+        return rc;
+    }
+    if (!c->d_materials) {  // no table yet, so no render yet: the stream's order still holds
+        VPX_HIP(c, sync_all(c));
+        return VPX_OK;
+    }
+    unsigned long long all[kProbeWords * kProbeStripes];
+    static_assert(sizeof(all) == kProbeBytes, "the whole record");
+    unsigned long long* rec = probe_record_of(c->d_materials);
+    VPX_HIP(c, sync_all(c));  // frames in flight on lanes (their level forks join them) included
+    VPX_HIP(c, hipMemcpyAsync(all, rec, sizeof(all), hipMemcpyDeviceToHost, c->stream));
+    VPX_HIP(c, hipStreamSynchronize(c->stream));
+    uint32_t bits = 0u;
+    for (uint32_t s = 0; s < kProbeStripes; ++s) {
+        out->probes += all[kProbeWords * s], out->lit += all[kProbeWords * s + 1];
+        bits = std::max(bits, (uint32_t)all[kProbeWords * s + 2]);
+    }
+    std::memcpy(&out->max_sqr, &bits, sizeof(bits));
+    out->in_light = out->lit ? 1u : 0u;
+    if (reset) {
+        VPX_HIP(c, hipMemsetAsync(rec, 0, kProbeBytes, c->stream));
+        VPX_HIP(c, sync_all(c));
+    }
+    return VPX_OK;
+}
+
 int vpx_find_nearest(vpx_ctx* c, const vpx_ray* rays, uint32_t n, vpx_hit* hits) {
     VPX_GROUP_FIRST(c, vpx_find_nearest(m_, rays, n, hits));
     if (!c || (n && (!rays || !hits))) return fail(c, VPX_E_INVALID, "null argument");
@@ -2329,10 +2387,10 @@ int vpx_is_occluded(vpx_ctx* c, const vpx_ray* rays, uint32_t n, uint8_t* occ) {
     return VPX_OK;
 }
 
-int vpx_trace(vpx_ctx* c, const vpx_ray* rays, const uint32_t* seeds, uint32_t n, int32_t depth, const float sky[3],
-              int32_t area_samples, float* radiance) {
-    VPX_GROUP_FIRST(c, vpx_trace(m_, rays, seeds, n, depth, sky, area_samples, radiance));
-    if (!c || (n && (!rays || !seeds || !radiance))) return fail(c, VPX_E_INVALID, "null argument");
+// vpx_trace (probes == nullptr: trace_k, as before) and vpx_trace_probe (trace_probe_k; radiance
+// may be null).
+static int trace_rays(vpx_ctx* c, const vpx_ray* rays, const uint32_t* seeds, uint32_t n, int32_t depth,
+                      const float sky[3], int32_t area_samples, float* radiance, vpx_ray_probe* probes) {
     if (depth < -1 || depth > kMaxLevels - 2) return fail(c, VPX_E_INVALID, "depth must be in [-1, 14]");
     if (!sky && !c->d_sky) return fail(c, VPX_E_STATE, "sky == NULL (textured sky) without vpx_set_sky");
     int rc = check_ready(c);
@@ -2340,24 +2398,50 @@ int vpx_trace(vpx_ctx* c, const vpx_ray* rays, const uint32_t* seeds, uint32_t n
     static const float kNoSky[3] = {0.f, 0.f, 0.f};
     if (n == 0) return VPX_OK;
     const size_t rb = sizeof(vpx_ray) * n, sb = 4ull * n, ob = 12ull * n;
-    if ((rc = ensure_scratch(c, rb + sb + ob))) return rc;
+    const size_t pb = probes ? sizeof(vpx_ray_probe) * n : 0;
+    if ((rc = ensure_scratch(c, rb + sb + ob + pb + 16))) return rc;
     vpx_ray* dr = (vpx_ray*)c->d_scratch;
     uint32_t* ds = (uint32_t*)((char*)c->d_scratch + rb);
     float* dout = (float*)((char*)c->d_scratch + rb + sb);
+    // (16-byte records: rb and sb + ob are multiples of 16 only together with the padding)
+    vpx_ray_probe* dp = (vpx_ray_probe*)((char*)c->d_scratch + ((rb + sb + ob + 15) & ~(size_t)15));
     VPX_HIP(c, hipMemcpyAsync(dr, rays, rb, hipMemcpyHostToDevice, c->stream));
     VPX_HIP(c, hipMemcpyAsync(ds, seeds, sb, hipMemcpyHostToDevice, c->stream));
     const SceneView sv = view_of(c, sky ? sky : kNoSky, area_samples, sky == nullptr);
     const dim3 g((n + 255) / 256), b(256);
-    if (depth <= 0)
+    if (probes) {
+        float* po = radiance ? dout : nullptr;
+        if (depth <= 0)
+            hipLaunchKernelGGL(trace_probe_k<1>, g, b, 0, c->stream, sv, dr, ds, n, depth, po, dp);
+        else if (depth <= 4)
+            hipLaunchKernelGGL(trace_probe_k<5>, g, b, 0, c->stream, sv, dr, ds, n, depth, po, dp);
+        else
+            hipLaunchKernelGGL(trace_probe_k<kMaxLevels>, g, b, 0, c->stream, sv, dr, ds, n, depth, po, dp);
+    } else if (depth <= 0)
         hipLaunchKernelGGL(trace_k<1>, g, b, 0, c->stream, sv, dr, ds, n, depth, dout);
     else if (depth <= 4)
         hipLaunchKernelGGL(trace_k<5>, g, b, 0, c->stream, sv, dr, ds, n, depth, dout);
     else
         hipLaunchKernelGGL(trace_k<kMaxLevels>, g, b, 0, c->stream, sv, dr, ds, n, depth, dout);
     VPX_HIP(c, hipGetLastError());
-    VPX_HIP(c, hipMemcpyAsync(radiance, dout, ob, hipMemcpyDeviceToHost, c->stream));
+    if (radiance) VPX_HIP(c, hipMemcpyAsync(radiance, dout, ob, hipMemcpyDeviceToHost, c->stream));
+    if (probes) VPX_HIP(c, hipMemcpyAsync(probes, dp, pb, hipMemcpyDeviceToHost, c->stream));
     VPX_HIP(c, sync_all(c));
     return VPX_OK;
+}
+
+int vpx_trace(vpx_ctx* c, const vpx_ray* rays, const uint32_t* seeds, uint32_t n, int32_t depth, const float sky[3],
+              int32_t area_samples, float* radiance) {
+    VPX_GROUP_FIRST(c, vpx_trace(m_, rays, seeds, n, depth, sky, area_samples, radiance));
+    if (!c || (n && (!rays || !seeds || !radiance))) return fail(c, VPX_E_INVALID, "null argument");
+    return trace_rays(c, rays, seeds, n, depth, sky, area_samples, radiance, nullptr);
+}
+
+int vpx_trace_probe(vpx_ctx* c, const vpx_ray* rays, const uint32_t* seeds, uint32_t n, int32_t depth,
+                    const float sky[3], int32_t area_samples, float* radiance, vpx_ray_probe* probes) {
+    VPX_GROUP_FIRST(c, vpx_trace_probe(m_, rays, seeds, n, depth, sky, area_samples, radiance, probes));
+    if (!c || (n && (!rays || !seeds || !probes))) return fail(c, VPX_E_INVALID, "null argument");
+    return trace_rays(c, rays, seeds, n, depth, sky, area_samples, radiance, probes);
 }
 
 int vpx_bvh_set(vpx_ctx* c, const vpx_bvh_tri* tris, uint32_t n) {

@@ -1411,8 +1411,15 @@ struct Level {
 };
 
 // Renderer::Trace(ray, depth) — renderer.cpp:1076-1328, recursion unrolled to a loop.
-template <int LEVELS>
-__device__ __forceinline__ f3 trace_path(const SceneView& sv, Ray ray, int depth, Rng& g, Counters& k) {
+// PROBE: the path's player light probes (the smoke branch's Illumination in volume 0,
+// :1228-1240) go to *probe: their number, how many had sqrLength(incLight) > 16 (a NaN does
+// not), and the largest sqrLength's bit pattern (non-negative, so it orders as the value).
+struct PathProbe {
+    uint32_t probes, lit, max_bits;
+};
+template <int LEVELS, bool PROBE = false>
+__device__ __forceinline__ f3 trace_path(const SceneView& sv, Ray ray, int depth, Rng& g, Counters& k,
+                                         PathProbe* probe = nullptr) {
     Level lv[LEVELS];
     uint32_t forms = 0;
     int nl = 0;
@@ -1481,7 +1488,15 @@ __device__ __forceinline__ f3 trace_path(const SceneView& sv, Ray ray, int depth
             bool in_glass = ray.inside;
             bool inside_volume = true;
             float intensity = 0.f, dist = 0.f;
-            if (vox == 0) (void)illumination(sv, ray, g, k);  // player light probe :1228-1240
+            if (vox == 0) {  // player light probe :1228-1240
+                const f3 inc = illumination(sv, ray, g, k);
+                if (PROBE) {
+                    const float v = inc.x * inc.x + inc.y * inc.y + inc.z * inc.z;  // sqrLength
+                    ++probe->probes;
+                    if (v > VPX_PLAYER_LIGHT_SQR) ++probe->lit;
+                    if (v == v) probe->max_bits = max(probe->max_bits, __float_as_uint(v));
+                }
+            }
             if (in_glass) {
                 intensity = mat.emissive;
                 color = albedo(sv, m);

@@ -30,7 +30,7 @@ constexpr uint32_t kInside = 2u;
 
 // shadow-slot flags (stored in SH_D.w)
 constexpr uint32_t kSlotValid = 1u;
-constexpr uint32_t kSlotDiscard = 2u;  // smoke player probe: traced for the count, result unused
+constexpr uint32_t kSlotDiscard = 2u;  // smoke player probe: its light sum goes to the player light record, not the path
 
 // internal frame flag: the static-camera path (Renderer::TraceReproject + reprojection)
 constexpr uint32_t kFlagReproject = 0x80000000u;
@@ -300,6 +300,58 @@ __device__ __forceinline__ void flush_counters(const Counters& k, uint32_t prima
     }
 }
 
+// The player light record (Renderer::inLight; vpx_get_player_light): kProbeStripes stripes of
+// kProbeWords 64-bit words — [0] probes, [1] lit, [2] the largest sqrLength's bit pattern (its low
+// 32 bits) — summed / maximised on readout.  It lives right behind the context's material table,
+// so every kernel that resolves a light sum reaches it through the SceneView it already holds:
+// a pointer of its own would grow the kernels' argument blocks (slot_list, above), and the
+// resolvers after the shadow pool (k_resolve, k_resolve_finish, k_finish_window) take no counter
+// pointer.  The context owns it: lanes, level forks and window chains all add to the one record.
+// One layout for both sides: the host allocates kMaterialTableBytes for the table
+// (vpx_set_materials, the only place that allocates it) and reads / clears the record through
+// probe_record_of, the same accessor the kernels use — whoever moves or reallocates the table
+// has to go through these.
+constexpr uint32_t kProbeStripes = 16;
+constexpr uint32_t kProbeWords = 4;
+constexpr size_t kProbeOffset = sizeof(vpx_material) * VPX_NUM_MATERIALS;  // the table itself
+constexpr size_t kProbeBytes = sizeof(unsigned long long) * kProbeWords * kProbeStripes;
+constexpr size_t kMaterialTableBytes = kProbeOffset + kProbeBytes;
+static_assert(kProbeOffset % 8 == 0, "the record is 8-byte aligned behind the table");
+__host__ __device__ __forceinline__ unsigned long long* probe_record_of(const vpx_material* table) {
+    return reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(const_cast<vpx_material*>(table)) + kProbeOffset);
+}
+__device__ __forceinline__ unsigned long long* probe_record(const SceneView& sv) {
+    return probe_record_of(sv.materials);
+}
+// probe_note adds to the record, so it relies on every pending-light word being resolved exactly
+// once (writing LB never needed that: a second resolve rewrote the same value).  That holds
+// because a level's resolve runs over the paths its shade just wrote SM for, every shade
+// rewrites SM (zero when nothing is pending) before the next resolve reads it, and the last
+// level's all-path resolvers (k_resolve_finish, k_shadow_finish, k_frame0, and k_finish_window's
+// loop over its chain's frames, p = p0 + b * stride: each path of the chain once) meet either
+// the last level's word or the zero a path's final (leaf) shade left.
+// One probe's incLight (renderer.cpp:1228-1240: Illumination, then sqrLength(incLight) > 16).
+// Called from divergent code (a lane per probing path): the lanes that are here reduce among
+// themselves — two ballots for the counts, the maximum by reading the active lanes in turn — and
+// the first of them adds the wave's sums.  Integer sums and a maximum: the same record whatever
+// the order of the waves.  sqrLength as tmpl8 sums it, left to right; a NaN is not lit (the
+// reference's compare) and is left out of the maximum; v >= 0, so its bit pattern orders as v.
+__device__ __forceinline__ void probe_note(const SceneView& sv, f3 inc) {
+    const float v = inc.x * inc.x + inc.y * inc.y + inc.z * inc.z;
+    const uint64_t here = __ballot(true);
+    const uint64_t lit = __ballot(v > VPX_PLAYER_LIGHT_SQR);
+    const uint32_t bits = v == v ? __float_as_uint(v) : 0u;
+    uint32_t mx = 0u;
+    for (uint64_t r = here; r; r &= r - 1ull)
+        mx = max(mx, (uint32_t)__builtin_amdgcn_readlane((int)bits, __ffsll((unsigned long long)r) - 1));
+    if ((threadIdx.x & 63u) == (uint32_t)__ffsll((unsigned long long)here) - 1u) {
+        unsigned long long* rec = probe_record(sv) + kProbeWords * (blockIdx.x & (kProbeStripes - 1u));
+        atomicAdd(&rec[0], (unsigned long long)__popcll(here));
+        if (lit) atomicAdd(&rec[1], (unsigned long long)__popcll(lit));
+        if (mx) atomicMax(reinterpret_cast<uint32_t*>(&rec[2]), mx);
+    }
+}
+
 // The tile (logical block) a workgroup of the walking kernels takes.  Workgroups are dealt
 // round-robin to the 8 XCDs (blocks b and b + 8 share one, MI355X_MICROARCH.md "Workgroup
 // dispatch"), so consecutive tiles land in 8 different L2s.  Launches of more than
@@ -346,7 +398,8 @@ constexpr uint32_t kSlotBits = 0x7fffu;  // smask: slots 0..14 (area_samples <= 
 // Renderer::Illumination (renderer.cpp:738-764) up to the IsOccluded calls: draws the
 // light index (and the area-light sample directions), computes each shadow ray exactly as
 // the evaluators build it, and the contribution it adds when unoccluded.  Returns the
-// pending-light word; discard = the smoke player probe (result thrown away).
+// pending-light word; discard = the smoke player probe (resolve_path_by records its sum
+// with probe_note and keeps it out of the path's radiance).
 __device__ __forceinline__ uint32_t emit_illumination(const SceneView& sv, const Ray& r, Rng& g, const WaveBufs& w,
                                                       uint32_t p, bool discard, f3& kd_out, uint32_t& slots) {
     const uint64_t pc = sv.num_points, scn = sv.num_spots, ac = sv.num_areas;
@@ -570,7 +623,7 @@ __device__ __forceinline__ bool shade_path(const SceneView& sv, const FrameArgs&
                     const bool in_glass = ray.inside;
                     bool inside_volume = true;
                     float intensity = 0.f, dist = 0.f;
-                    if (vox == 0) {  // player light probe :1228-1240 (rays cast, result unused)
+                    if (vox == 0) {  // player light probe :1228-1240 (its sum: probe_note)
                         pending = emit_illumination(sv, ray, g, w, p, true, kd, slots);
                     }
                     if (in_glass) {
@@ -687,7 +740,6 @@ __device__ __forceinline__ void resolve_path_by(const SceneView& sv, const WaveB
     const uint32_t pend = __float_as_uint(sm.w);
     if (!pend) return;
     const uint32_t kind = pend & 7u, count = (pend >> 4) & 15u, lvl = (pend >> 8) & 31u, lc = pend >> 16;
-    if (pend & 8u) return;  // discarded probe
     const uint32_t valid = w.smask[p];
     f3 acc = mk(0.f, 0.f, 0.f);
     for (uint32_t s = 0; s < count; ++s) {
@@ -703,6 +755,10 @@ __device__ __forceinline__ void resolve_path_by(const SceneView& sv, const WaveB
     f3 inc = acc;
     if (kind == kLightArea) inc = (acc / (float)sv.area_samples) * mk(sm.x, sm.y, sm.z);
     inc = inc * (float)lc;
+    if (pend & 8u) {  // the player light probe: the same sum, recorded; the level gets no light (no LB, no out)
+        probe_note(sv, inc);
+        return;
+    }
     if (pend & kPendZeroAdd) inc = mk(0.f, 0.f, 0.f) + inc;
     if (out) {
         out->lvl = lvl;

@@ -242,3 +242,28 @@ class ShardedAccumFrame:
         """Complete the last publish (its gather and rank 0's scatter)."""
         if self.pending is not None:
             self._finish()
+
+    def player_light(self, reset=True):
+        """The frame's player light record over every rank's tiles (Renderer::inLight,
+        renderer.h:231): each rank reads its context's record (ctx.player_light) and one
+        all-reduce combines them — probes and lit summed, max_sqr the largest — so every rank
+        sees the flag.  Each rank writes its three words (max_sqr as its bit pattern: the value
+        is never negative, so the patterns order as the values) into its own row of an
+        [n_ranks, 3] int64 tensor of zeros, and the SUM of those tensors is every rank's row,
+        exact.  The tensor lives on the host when `host_gather` is set (gloo), else on the
+        context's device (RCCL).  Returns abi.PlayerLight's fields as a dict."""
+        import torch
+        import torch.distributed as dist
+
+        pl = self.ctx.player_light(reset=reset)
+        bits = int(np.float32(pl.max_sqr).view(np.uint32))
+        rows = torch.zeros((self.n, 3), dtype=torch.int64)
+        rows[self.rank] = torch.tensor([int(pl.probes), int(pl.lit), bits], dtype=torch.int64)
+        if self.n > 1:
+            if not self.host:
+                rows = rows.to(self.accum.device)
+            dist.all_reduce(rows, op=dist.ReduceOp.SUM)
+            rows = rows.cpu()
+        probes, lit = int(rows[:, 0].sum()), int(rows[:, 1].sum())
+        max_sqr = float(np.uint32(int(rows[:, 2].max())).view(np.float32))
+        return {"probes": probes, "lit": lit, "max_sqr": max_sqr, "in_light": 1 if lit else 0}

@@ -9,7 +9,11 @@
 //
 // usage: vpx_demo [n] [width] [height] [frames] [max_bounces] [out.rgb8] [mode] [devices]
 //   mode: letters — 's' staticCamera (the reprojection branch of Tick), 'k' activateSky
-//   with the demo sky texture (demo_sky below; tests rebuild it with numpy); '-' none.
+//   with the demo sky texture (demo_sky below; tests rebuild it with numpy); 'p' puts a block
+//   of player smoke (SMOKE_PLAYER, cells x in [3n/4, 7n/8), y in [2, 2 + n/4), z in [n/4, 3n/8),
+//   albedo (0.8, 0.75, 0.7)) into the world under a point light of colour 8, tracks the player
+//   light (Renderer::trackPlayerLight: every Tick reads and clears the record, as the game's
+//   Tick does with inLight) and prints the run's sums as a second JSON line; '-' none.
 //   devices: comma-separated HIP devices, e.g. 0,1,2,3 — a device set (vpx_create_multi:
 //   tiles over the devices, RCCL gather to the first); default: device 0 alone.
 #include <chrono>
@@ -66,8 +70,8 @@ int main(int argc, char** argv) {
     const int bounces = argc > 5 ? atoi(argv[5]) : 0;
     const char* out = argc > 6 && argv[6][0] != '-' ? argv[6] : nullptr;
     const char* mode = argc > 7 ? argv[7] : "";
-    bool is_static = false, sky = false;
-    for (const char* m = mode; *m; ++m) is_static |= *m == 's', sky |= *m == 'k';
+    bool is_static = false, sky = false, player_light = false;
+    for (const char* m = mode; *m; ++m) is_static |= *m == 's', sky |= *m == 'k', player_light |= *m == 'p';
     std::vector<int> devices;
     if (argc > 8)
         for (const char* d = argv[8]; *d;) {
@@ -78,7 +82,11 @@ int main(int argc, char** argv) {
 
     vpxhost::Renderer r = devices.empty() ? vpxhost::Renderer(0) : vpxhost::Renderer(devices);
     CHECK(r.Init(W, H));
-    const std::vector<uint8_t> grid = pillars(n);
+    std::vector<uint8_t> grid = pillars(n);
+    if (player_light)  // the player: a block of smoke in the world, which is volume 0
+        for (uint32_t z = n / 4; z < 3 * n / 8; ++z)
+            for (uint32_t y = 2; y < 2 + n / 4; ++y)
+                for (uint32_t x = 3 * n / 4; x < 7 * n / 8; ++x) grid[x + (size_t)y * n + (size_t)z * n * n] = VPX_MAT_SMOKE_PLAYER;
     CHECK(r.UploadGrid(0, grid.data(), n));
     vpx_volume vol{};
     const float zero[3] = {0, 0, 0}, one[3] = {1, 1, 1};
@@ -86,8 +94,11 @@ int main(int argc, char** argv) {
     CHECK(r.SetVolumes({vol}));
     std::vector<vpx_material> mats(VPX_NUM_MATERIALS);
     CHECK(vpx_default_materials(mats.data()));
+    if (player_light) mats[VPX_MAT_SMOKE_PLAYER].albedo[0] = 0.8f, mats[VPX_MAT_SMOKE_PLAYER].albedo[1] = 0.75f,
+                      mats[VPX_MAT_SMOKE_PLAYER].albedo[2] = 0.7f;
     CHECK(r.SetMaterials(mats));
-    const vpx_point_light pl{{0.5f, 1.5f, 0.5f}, {1.0f, 1.0f, 1.0f}};
+    const float pc = player_light ? 8.0f : 1.0f;
+    const vpx_point_light pl{{0.5f, 1.5f, 0.5f}, {pc, pc, pc}};
     const vpx_dir_light dl{{-0.3f, -1.0f, -0.2f}, {1.0f, 1.0f, 1.0f}};
     CHECK(r.SetLights({pl}, {}, {}, dl));
     CHECK(r.SetShapes({}, {}));
@@ -100,13 +111,23 @@ int main(int argc, char** argv) {
         r.activateSky = true;
     }
     r.staticCamera = is_static;
+    r.trackPlayerLight = player_light;
+    vpx_player_light run{};  // the Ticks' records, summed
+    uint32_t ticks_in_light = 0;
+    auto note = [&] {
+        run.probes += r.playerLight.probes, run.lit += r.playerLight.lit;
+        if (r.playerLight.max_sqr > run.max_sqr) run.max_sqr = r.playerLight.max_sqr;
+        ticks_in_light += r.inLight ? 1u : 0u;
+    };
 
     vpx_stats st{};
     CHECK(r.Tick(0.0f, &st));  // warm-up frame (also frame 0 of the accumulation)
+    note();
     double primary = 0, shadow = 0;
     const auto t0 = std::chrono::steady_clock::now();
     for (int f = 1; f < frames; ++f) {
         CHECK(r.Tick(0.0f, &st));
+        note();
         primary += (double)st.primary_rays;
         shadow += (double)st.shadow_rays;
     }
@@ -124,5 +145,13 @@ int main(int argc, char** argv) {
     std::printf("{\"n\": %u, \"width\": %u, \"height\": %u, \"frames\": %d, \"ms_per_frame\": %.4f, "
                 "\"mray_s\": %.2f, \"nonzero_pixels\": %zu}\n",
                 n, W, H, r.numRenderedFrames, 1e3 * s / timed, (primary + shadow) / s / 1e6, lit);
+    if (player_light) {
+        vpx_player_light left{};  // every Tick cleared the record after reading it
+        CHECK(vpx_get_player_light(r.Context(), &left, 0));
+        std::printf("{\"player_light\": {\"probes\": %llu, \"lit\": %llu, \"max_sqr\": %.9g, \"ticks_in_light\": %u, "
+                    "\"left_after_ticks\": %llu}}\n",
+                    (unsigned long long)run.probes, (unsigned long long)run.lit, run.max_sqr, ticks_in_light,
+                    (unsigned long long)left.probes);
+    }
     return 0;
 }

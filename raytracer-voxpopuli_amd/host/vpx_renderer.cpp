@@ -152,14 +152,21 @@ int Renderer::CopyHistory(float* host_rgba) const {
 
 int Renderer::Tick(float /*deltaTime*/, vpx_stats* stats) {
     if (status_) return status_;
-    if (staticCamera) return UpdateStatic(stats);
+    if (staticCamera) return ReadPlayerLight(UpdateStatic(stats));
     if (flags & VPX_FLAG_DOF) {  // focus ray of Renderer::Tick (renderer.cpp:1987-1991)
         int rc = vpx_focus_distance(ctx_, width_, height_, &camera.focal_distance);
         if (rc) return rc;
         rc = vpx_set_camera(ctx_, &camera);
         if (rc) return rc;
     }
-    return Update(stats);
+    return ReadPlayerLight(Update(stats));
+}
+
+int Renderer::ReadPlayerLight(int rc) {
+    if (rc || !trackPlayerLight) return rc;
+    rc = vpx_get_player_light(ctx_, &playerLight, 1);
+    if (!rc) inLight = playerLight.in_light != 0;
+    return rc;
 }
 
 int Renderer::UseGLBuffer(unsigned int pbo) {

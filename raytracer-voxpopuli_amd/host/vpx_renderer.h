@@ -82,9 +82,18 @@ public:
     float sky[3] = {0.392f, 0.584f, 0.829f};  // SampleSky, activateSky == false (renderer.cpp:2310-2313)
     vpx_camera camera{};
     vpx_prev_camera prevCamera{};  // renderer.h:182
+    // renderer.h:231: a path reached the player's smoke (volume 0) and found more light there
+    // than VPX_PLAYER_LIGHT_SQR.  Tick keeps it up to date only while trackPlayerLight is set
+    // (off by default: the read synchronises once per Tick, which frames in flight exist to
+    // avoid): it reads and resets the record after the render on both branches, as the
+    // reference's Tick reads the flag (renderer.cpp:2112-2118) and clears it (:2206).
+    bool inLight = false;
+    bool trackPlayerLight = false;
+    vpx_player_light playerLight{};  // the last tracked Tick's record
 
 private:
     int UpdateStatic(vpx_stats* stats);
+    int ReadPlayerLight(int rc);  // after a Tick's render (rc: its status)
     int MapScreen(uint32_t** out) const;  // the frame's RGB8 target: the GL buffer or screen_
     int UnmapScreen(int rc) const;
     bool glBuffer_ = false;

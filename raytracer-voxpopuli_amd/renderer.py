@@ -31,6 +31,13 @@ class Renderer:
         self.accumulator = None
         self.screen = None
         self.last_stats = None
+        # Renderer::inLight (renderer.h:231): a path reached the player's smoke and found more
+        # light there than VPX_PLAYER_LIGHT_SQR.  Kept up to date by Tick only while
+        # trackPlayerLight is set: reading the record synchronises once per Tick, which frames
+        # in flight exist to avoid.
+        self.inLight = False
+        self.trackPlayerLight = False
+        self.last_player_light = None  # abi.PlayerLight of the last tracked Tick
 
     def Init(self):
         """Renderer::Init minus window/asset/game setup (renderer.cpp:688-736)."""
@@ -82,7 +89,9 @@ class Renderer:
             if self.scene.flags & abi.VPX_FLAG_DOF:  # focus ray, renderer.cpp:1987-1991
                 self.scene.camera.focal_distance = self.ctx.focus_distance(self.scene.width, self.scene.height)
                 self.ctx.set_camera(self.scene.camera)
-            return self.Update(stats=stats)
+            st = self.Update(stats=stats)
+            self._read_player_light()
+            return st
         # static branch (renderer.cpp:1996-2101): TraceReproject + history reprojection
         if self.prevCamera is None:
             self.CopyToPrevCamera()
@@ -94,7 +103,15 @@ class Renderer:
         st = self.ctx.render_reproject(p, self.prevCamera, self.illuminationHistory.data_ptr(), self.screen.data_ptr(),
                                        stats=stats)
         self.numRenderedFrames += 1
+        self._read_player_light()
         return st
+
+    def _read_player_light(self):
+        """The frame's flag, read and cleared after the render on both branches: the reference's
+        Tick reads inLight (renderer.cpp:2112-2118) and clears it (:2206)."""
+        if self.trackPlayerLight:
+            self.last_player_light = self.ctx.player_light(reset=True)
+            self.inLight = bool(self.last_player_light.in_light)
 
     def history_host(self):
         self.synchronize()
