@@ -696,6 +696,36 @@ VPX_HD void axis_clip(Axis& a, uint32_t l, bool ok1, uint32_t reach, uint32_t fi
     a.l = l < lim ? l : lim;
     a.m1 = a.l < fit1 ? a.l : fit1;
 }
+// More segments, by rebasing: an axis clipped at the end of its second segment (l = reach past
+// m1 = fit1, fewer than the `want` events of the box) drops its first segment and takes the
+// binade after the second instead.  The axis then describes A(off + i'), off = fit1 + 1: the new
+// head is A(off), the second segment's first value (closed form from j = 0, so it serves as a
+// first segment), the new second segment starts after one more plain IEEE step, and l becomes
+// the events wanted past off, clipped to what the two reach.  Indices below off are no longer
+// described, so the caller rebases only where every value it will compare against lies above
+// A(off) (axis_head2 < T): then every dropped term is below it and counts as passed, and the
+// rebased count is at least 1.  Returns off, the events passed (0: nothing changed — `on` false,
+// not clipped in this way, or the next binade has no closed form from its first value, a tie),
+// for the caller to move the cell and the visit count by; a rebased axis can be rebased again.
+VPX_HD float axis_head2(const Axis& a) { return bitsf((a.e2 << 23) | (a.b2 & 0x7fffffu)); }
+VPX_HD bool axis_outrun(const Axis& a, uint32_t want) { return (want > a.l) & (a.l > a.m1); }
+VPX_HD uint32_t axis_rebase(float& h, float d, Axis& a, uint32_t want, bool on) {
+    const uint32_t fit1 = a.m1, fit2 = a.l - fit1 - 1u;  // (when outrun: l = fit1 + 1 + fit2)
+    const float A = bitsf((a.e2 << 23) | (mad24(fit2, a.c2, a.b2) & 0x7fffffu)) + d;  // the plain step out of it
+    uint32_t b3, c3, e3;
+    const bool ok3 = seg_params_nb(A, d, b3, c3, e3);
+    const bool exact3 = b3 == ((fbits(A) & 0x7fffffu) | 0x800000u);
+    const uint32_t room3 = b3 <= 0xffffffu ? 0xffffffu - b3 : 0u;
+    const uint32_t fit3 = floor_div_cap(room3, c3 ? c3 : 1u);
+    const bool go = on & axis_outrun(a, want) & ok3 & exact3;
+    const uint32_t off = fit1 + 1u, l = want - off, lim = fit2 + 1u + fit3;
+    h = go ? axis_head2(a) : h;
+    a.b1 = go ? a.b2 : a.b1, a.c1 = go ? a.c2 : a.c1, a.e1 = go ? a.e2 : a.e1;
+    a.b2 = go ? b3 : a.b2, a.c2 = go ? c3 : a.c2, a.e2 = go ? e3 : a.e2;
+    a.l = go ? (l < lim ? l : lim) : a.l;
+    a.m1 = go ? (a.l < fit2 ? a.l : fit2) : a.m1;
+    return go ? off : 0u;
+}
 // True when any lane of the wave (calling it together) passes true; the host: this call's.
 VPX_HD bool any_lane(bool b) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -745,8 +775,13 @@ VPX_HD uint32_t axis_count(const Axis& a, float h, float T, bool strict, uint32_
 // receive the clipped box).  0: landed just before the event that leaves the clipped box
 // (cells += skipped visits); 1: the walk ends inside it (cells += visits); 2: refused.
 // SEG2_BRANCH: the second closed-form segment only when a lane of the wave needs it.
-template <bool SEG2_BRANCH = true>
+// MORE (with SEG2_BRANCH): up to MORE times, while a lane's box outruns its two segments, its
+// clipped axes are rebased onto the next binade (axis_rebase), so the lane crosses up to 1 + MORE
+// binade boundaries per axis in one skip instead of landing inside the box and skipping the
+// rest after another load.
+template <bool SEG2_BRANCH = true, int MORE = 0>
 VPX_HD int skip_box_lean(Walk& w, uint32_t lo[3], uint32_t hi[3], float bound, uint32_t& cells) {
+    static_assert(MORE == 0 || SEG2_BRANCH, "skip_box_lean: further segments build on the branch form");
     if (!((w.tx > 0.0f) & (w.ty > 0.0f) & (w.tz > 0.0f))) return 2;
     Axis ax, ay, az;
     if (SEG2_BRANCH) {
@@ -768,6 +803,25 @@ VPX_HD int skip_box_lean(Walk& w, uint32_t lo[3], uint32_t hi[3], float bound, u
     axis_setup(w.tx, w.dx, w.sx > 0 ? hi[0] - w.X : w.X - lo[0], ax);
     axis_setup(w.ty, w.dy, w.sy > 0 ? hi[1] - w.Y : w.Y - lo[1], ay);
     axis_setup(w.tz, w.dz, w.sz > 0 ? hi[2] - w.Z : w.Z - lo[2], az);
+    }
+    // The events a rebase passes are taken at once (cell, head and visit count move to A(off)),
+    // so nothing but the axes themselves is kept for the rest; w.t follows at the landing, where
+    // a rebased axis has moved again.
+    for (int more = 0; more < MORE; ++more) {
+        const uint32_t wx = w.sx > 0 ? hi[0] - w.X : w.X - lo[0], wy = w.sy > 0 ? hi[1] - w.Y : w.Y - lo[1],
+                       wz = w.sz > 0 ? hi[2] - w.Z : w.Z - lo[2];
+        const bool ux = axis_outrun(ax, wx), uy = axis_outrun(ay, wy), uz = axis_outrun(az, wz);
+        if (!any_lane(ux | uy | uz)) break;
+        // every value compared below is at least the clipped box's leaving time (or the bound)
+        const float Vx = axis_at(ax, w.tx, ax.l), Vy = axis_at(ay, w.ty, ay.l), Vz = axis_at(az, w.tz, az.l);
+        const float Vm = Vx < Vy ? Vx : Vy, Vn = Vm < Vz ? Vm : Vz, T2 = Vn < bound ? Vn : bound;
+        const uint32_t ox = axis_rebase(w.tx, w.dx, ax, wx, axis_head2(ax) < T2);
+        const uint32_t oy = axis_rebase(w.ty, w.dy, ay, wy, axis_head2(ay) < T2);
+        const uint32_t oz = axis_rebase(w.tz, w.dz, az, wz, axis_head2(az) < T2);
+        w.X += ox * (uint32_t)w.sx;
+        w.Y += oy * (uint32_t)w.sy;
+        w.Z += oz * (uint32_t)w.sz;
+        cells += ox + oy + oz;
     }
     const uint32_t lx = ax.l, ly = ay.l, lz = az.l;
     if (w.sx > 0) hi[0] = w.X + lx; else lo[0] = w.X - lx;
@@ -808,12 +862,38 @@ VPX_HD int skip_box_lean(Walk& w, uint32_t lo[3], uint32_t hi[3], float bound, u
     return 1;
 }
 
+// The maturity gate: is a skip from this state worth its cost?  An axis is mature when the
+// exponent of its tmax is at least G above its tdelta's: only then do its two closed-form
+// segments reach a useful number of events (at G = 0 seg_params_nb refuses the axis and the box
+// is clipped at its next event).  A walk that starts at t = 0 (shadow and bounce rays, a camera
+// inside the grid) has every tmax at or below its tdelta, and its first skips would advance a
+// handful of events each.  The gate is shut while an immature axis has its next event within N
+// events of the dominant axis (dom_axis, itself included): the caller then takes the brick as
+// class 3 and steps.  Stepping through an empty brick and skipping it visit the same cells, so
+// the gate changes no result, only which of the two the walk pays for.  Sign bits, infinities
+// and NaNs fall where the compares put them (an infinite tmax never shuts the gate).
+VPX_HD bool gate_immature(float t, float d, uint32_t G) { return (fbits(t) >> 23) < (fbits(d) >> 23) + G; }
+VPX_HD bool gate_open(float tx, float ty, float tz, float dx, float dy, float dz, uint32_t G, uint32_t N) {
+    const bool xd = (dx <= dy) & (dx <= dz), yd = !xd & (dy <= dz);  // dom_axis
+    const float lim = (xd ? tx : (yd ? ty : tz)) + (float)N * (xd ? dx : (yd ? dy : dz));
+    const bool ix = gate_immature(tx, dx, G), iy = gate_immature(ty, dy, G), iz = gate_immature(tz, dz, G);
+    return !((ix & (tx < lim)) | (iy & (ty < lim)) | (iz & (tz < lim)));
+}
+// The gate as walk_skip takes it: 0 = none, else 1 | G << 1 | f << 3 with G <= 3 and N = 4 << f,
+// f <= 3 (the walkers' RUN word holds the same five bits from bit 26, vpx_trace.hpp).
+VPX_HD uint32_t gate_word(uint32_t G, uint32_t f) { return 1u | G << 1 | f << 3; }
+VPX_HD bool gate_open(const Walk& w, uint32_t gate) {
+    return !(gate & 1u) || gate_open(w.tx, w.ty, w.tz, w.dx, w.dy, w.dz, (gate >> 1) & 3u, 4u << ((gate >> 3) & 3u));
+}
+
 // Scene::FindNearest (MODE nearest) / Scene::IsOccluded walk from an initialised state.
 // Returns true at the first solid cell (w.t / w.X,Y,Z describe it).  Exact.  The device
 // walker (walk_wave, vpx_trace.hpp) runs the same per-lane sequence.
 // With the axis planes (g.dfa / g.dfw) the boxes are theirs, along the ray's dominant axis, and
-// with g.dfw widened along its second.
-VPX_HD bool walk_skip(const GridView& g, Walk& w, float bound, uint32_t& cells) {
+// with g.dfw widened along its second.  `gate` (gate_word, 0: none): a class-2 brick is stepped
+// through while the maturity gate is shut, as the walkers do for the kinds that have the bit;
+// bits 5-7 of it: the further segments its skips may take (skip_box_lean's MORE, up to 4).
+VPX_HD bool walk_skip(const GridView& g, Walk& w, float bound, uint32_t& cells, uint32_t gate = 0u) {
     const bool wide = g.dfw != nullptr, axes = wide || g.dfa != nullptr;
     const uint32_t axis = dom_axis(w), sec = wide ? sec_axis(w) : 3u;
     const uint32_t apar = plane_parent(g, (w.osh >> 3) * 3u + axis);
@@ -824,11 +904,17 @@ VPX_HD bool walk_skip(const GridView& g, Walk& w, float bound, uint32_t& cells) 
             ++cells;
             return true;
         }
-        if (cls == 2) {
+        if (cls == 2 && gate_open(w, gate)) {
             uint32_t lo[3], hi[3];
             if (axes) df_box_axis(w, g.n, cube_dfp(w), len_dfa(w), axis, lo, hi, sec, wide ? wid_dfw(w, axis, sec) : 0u);
             else df_box(w, g.n, cube_l1(w), lo, hi);
-            if (skip_box_lean(w, lo, hi, bound, cells) == 1) return false;
+            const uint32_t more = (gate >> 5) & 7u;
+            const int sr = more == 0u   ? skip_box_lean(w, lo, hi, bound, cells)
+                           : more == 1u ? skip_box_lean<true, 1>(w, lo, hi, bound, cells)
+                           : more == 2u ? skip_box_lean<true, 2>(w, lo, hi, bound, cells)
+                           : more == 3u ? skip_box_lean<true, 3>(w, lo, hi, bound, cells)
+                                        : skip_box_lean<true, 4>(w, lo, hi, bound, cells);
+            if (sr == 1) return false;
         }
         ++cells;  // visit the (empty) current cell
         if (!step1(w, g.n)) return false;

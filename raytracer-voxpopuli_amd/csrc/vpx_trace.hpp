@@ -458,9 +458,12 @@ constexpr uint32_t kSkipwNearest = 1, kSkipwBounce = 2, kSkipwShadow = 4;
 #ifndef VPX_MINC_NEAREST
 #define VPX_MINC_NEAREST 2
 #endif
-constexpr uint32_t kMincNearest = VPX_MINC_NEAREST, kMincBounce = 2, kMincShadow = 1;
+#ifndef VPX_MINC_SHADOW
+#define VPX_MINC_SHADOW 1
+#endif
+constexpr uint32_t kMincNearest = VPX_MINC_NEAREST, kMincBounce = 2, kMincShadow = VPX_MINC_SHADOW;
 // Brick runs per walk kind, the RUN word: cap | passes << 8 | seg2 << 17 | min2 << 18 |
-// axis << 19 | minlen << 20 | wide << 24 | local << 25.
+// axis << 19 | minlen << 20 | wide << 24 | local << 25 | gate << 26 | G << 27 | N << 29 | seg3 << 31.
 // After its octant-plane byte (and, in an occupied brick, its cell mask) loads, a lane
 // steps up to `cap` cells inside its 4^3 brick on the register copy; `passes` brick loads
 // per step-phase iteration.  Measured (ms, one box): primary C1 0.432 -> 0.402 with 3|2<<8;
@@ -515,16 +518,56 @@ constexpr uint32_t kMincNearest = VPX_MINC_NEAREST, kMincBounce = 2, kMincShadow
 #define VPX_RUN_LOCAL(on) ((on) << 25)
 #endif
 #define VPX_RUN_AXIS ((VPX_AXIS_BOXES ? 1u : 0u) << 19 | VPX_AXIS_MINLEN << 20 | (VPX_AXIS_BOXES && VPX_WIDE_BOXES ? 1u : 0u) << 24)
+// gate (bit 26), G (bits 27-28), N (bits 29-30: N = 4 << field): the maturity gate (skip::gate_open,
+// vpx_skip.hpp).  A class-2 lane whose skip would be clipped at an immature axis's next event
+// (exponent of tmax below exponent of tdelta + G, that event within N events of the dominant
+// axis) takes its brick as class 3 and steps.  Walks that start at t = 0 (shadow and bounce rays)
+// begin with every axis immature, and in a compacted shadow wave all lanes at once.  Measured (ms
+// per step, one box, interleaved runs of the parent's library and this one, DESIGN.md section 4,
+// round 10): with the bit in k_frame0's shadow walks C1 0.4760-0.4795 -> 0.4503-0.4592; in the
+// other tile shadow walkers (kRunShadow) on top C4 24.90-25.42 -> 24.38-24.87; in the shadow pool
+// C3 3.307-3.351 -> 3.355-3.389 and in the bounce walks C2 / Z1 2.166-2.191 / 1.609-1.611 ->
+// 2.187-2.209 / 1.618-1.620 (their lanes start at different times, so a stepping lane holds its
+// wave in the step phase while the others wait to skip): off there.  G 2 or N 8 instead of 1 and 4
+// measured the same on C1.  VPX_SKIP_GATE=1 sets the bit for every kind, 0 for none; VPX_GATE_G /
+// VPX_GATE_NF set the fields.
+#ifndef VPX_GATE_G
+#define VPX_GATE_G 1u
+#endif
+#ifndef VPX_GATE_NF
+#define VPX_GATE_NF 0u
+#endif
+#ifdef VPX_SKIP_GATE
+#define VPX_RUN_GATE(on) ((VPX_SKIP_GATE ? 1u : 0u) << 26 | VPX_GATE_G << 27 | VPX_GATE_NF << 29)
+#else
+#define VPX_RUN_GATE(on) ((on) << 26 | VPX_GATE_G << 27 | VPX_GATE_NF << 29)
+#endif
+// seg3 (bit 31, with seg2): a skip whose box outruns its two closed-form segments rebases its
+// clipped axes onto the next binade, up to VPX_SEG_MORE times, behind a ballot like seg2's
+// (skip::skip_box_lean's MORE).  Off in every kind: the CPU model gives the shadow walks 13 % to
+// 18 % fewer wave-cost units with one or two further segments (none to the primary walks, whose
+// clipped axes are not the ones their boxes are left through), but k_frame0 spills 34 / 58 VGPRs
+// with them instead of 20 and C1 measured 0.518-0.526 / 0.581-0.588 ms against 0.476-0.480 (with
+// the gate on top 0.482-0.485 against 0.462-0.464).  VPX_SEG3=1 sets the bit for every kind that
+// has seg2.
+#ifndef VPX_SEG_MORE
+#define VPX_SEG_MORE 1
+#endif
+#ifdef VPX_SEG3
+#define VPX_RUN_SEG3(on) ((VPX_SEG3 ? 1u : 0u) << 31)
+#else
+#define VPX_RUN_SEG3(on) ((on) << 31)
+#endif
 #ifndef VPX_RUN_NEAREST
-#define VPX_RUN_NEAREST (3u | 3u << 8 | 1u << 17 | 1u << 18 | VPX_RUN_AXIS | VPX_RUN_LOCAL(1u))
+#define VPX_RUN_NEAREST (3u | 3u << 8 | 1u << 17 | 1u << 18 | VPX_RUN_AXIS | VPX_RUN_LOCAL(1u) | VPX_RUN_GATE(0u) | VPX_RUN_SEG3(0u))
 #endif
 constexpr uint32_t kRunNearest = VPX_RUN_NEAREST;
 #ifndef VPX_RUN_BOUNCE
-#define VPX_RUN_BOUNCE (4u | 1u << 8 | 0u << 17 | 1u << 18 | VPX_RUN_AXIS | VPX_RUN_LOCAL(0u))
+#define VPX_RUN_BOUNCE (4u | 1u << 8 | 0u << 17 | 1u << 18 | VPX_RUN_AXIS | VPX_RUN_LOCAL(0u) | VPX_RUN_GATE(0u))
 #endif
 constexpr uint32_t kRunBounce = VPX_RUN_BOUNCE;
 #ifndef VPX_RUN_SHADOW
-#define VPX_RUN_SHADOW (3u | 1u << 8 | 1u << 17 | 0u << 18 | VPX_RUN_AXIS | VPX_RUN_LOCAL(1u))
+#define VPX_RUN_SHADOW (3u | 1u << 8 | 1u << 17 | 0u << 18 | VPX_RUN_AXIS | VPX_RUN_LOCAL(1u) | VPX_RUN_GATE(1u) | VPX_RUN_SEG3(0u))
 #endif
 constexpr uint32_t kRunShadow = VPX_RUN_SHADOW;
 // Round 5 (ms per step, three interleaved runs, tools/gpu_ab.sh): FindNearest runs of 3 cells in
@@ -536,13 +579,15 @@ constexpr uint32_t kRunShadow = VPX_RUN_SHADOW;
 // 0.5433-0.5444 vs 0.5456-0.5482 ms in three, then 0.5427-0.5457 vs 0.5447-0.5484 (two boxes,
 // three interleaved runs each); five passes 0.5464-0.5474, runs of 2 in four 0.5428-0.5472.
 #ifndef VPX_RUN_FRAME_NEAREST
-#define VPX_RUN_FRAME_NEAREST (3u | 4u << 8 | 1u << 17 | 1u << 18 | VPX_RUN_AXIS | VPX_RUN_LOCAL(1u))
+#define VPX_RUN_FRAME_NEAREST (3u | 4u << 8 | 1u << 17 | 1u << 18 | VPX_RUN_AXIS | VPX_RUN_LOCAL(1u) | VPX_RUN_GATE(0u) | VPX_RUN_SEG3(0u))
 #endif
 constexpr uint32_t kRunFrameNearest = VPX_RUN_FRAME_NEAREST;
 // At 7 waves/SIMD the frame's shadow walks take the two-compare step too: C1 0.5418-0.5489 vs
-// 0.5456-0.5539 ms (seven interleaved runs, all won; three passes 0.5479-0.5591).
+// 0.5456-0.5539 ms (seven interleaved runs, all won; three passes 0.5479-0.5591).  Round 10: with
+// the gate a stepping lane needs several brick loads before its first skip, and three passes
+// win: C1 0.4514-0.4522 vs 0.4560-0.4626 ms in two (three interleaved runs each).
 #ifndef VPX_RUN_FRAME_SHADOW
-#define VPX_RUN_FRAME_SHADOW (3u | 2u << 8 | 1u << 17 | 1u << 18 | VPX_RUN_AXIS | VPX_RUN_LOCAL(1u))
+#define VPX_RUN_FRAME_SHADOW (3u | 3u << 8 | 1u << 17 | 1u << 18 | VPX_RUN_AXIS | VPX_RUN_LOCAL(1u) | VPX_RUN_GATE(1u) | VPX_RUN_SEG3(0u))
 #endif
 constexpr uint32_t kRunFrameShadow = VPX_RUN_FRAME_SHADOW;
 // The pools' walks (k_nearest_pool, k_shadow_pool: 96 VGPRs at 5 waves/SIMD) have their own
@@ -553,7 +598,7 @@ constexpr uint32_t kRunFrameShadow = VPX_RUN_FRAME_SHADOW;
 // weight 1 / 4, runs of 3 cells in two passes measured C2 2.63-2.66 / 2.60-2.64 / 2.66-2.75 /
 // 2.65-2.71 vs 2.59-2.65 ms, and re-checked at three lanes in round 5 (within noise).
 #ifndef VPX_RUN_SHADOW_POOL
-#define VPX_RUN_SHADOW_POOL (3u | 1u << 8 | 1u << 17 | 1u << 18 | VPX_RUN_AXIS | VPX_RUN_LOCAL(1u))
+#define VPX_RUN_SHADOW_POOL (3u | 1u << 8 | 1u << 17 | 1u << 18 | VPX_RUN_AXIS | VPX_RUN_LOCAL(1u) | VPX_RUN_GATE(0u) | VPX_RUN_SEG3(0u))
 #endif
 #ifndef VPX_SKIPW_SHADOW_POOL
 #define VPX_SKIPW_SHADOW_POOL 4u
@@ -599,6 +644,9 @@ __device__ __forceinline__ bool walk_wave(const skip::GridView& g, skip::Walk& w
     constexpr uint32_t kMinLen = (RUN >> 20) & 15u;
     constexpr bool kWide = (RUN >> 24) & 1u;  // ... widened along the second axis (skip::wid_dfw)
     constexpr bool kLocal = (RUN >> 25) & 1u;  // the skip phase's axes behind a barrier
+    constexpr bool kGate = (RUN >> 26) & 1u;   // the maturity gate on class 2 (skip::gate_open)
+    constexpr uint32_t kGateG = (RUN >> 27) & 3u, kGateN = 4u << ((RUN >> 29) & 3u);
+    constexpr int kMore = ((RUN >> 31) & 1u) && kSeg2Branch ? VPX_SEG_MORE : 0;  // further lean segments
     static_assert(!kWide || kAxis, "walk_wave: wide boxes are axis boxes");
     static_assert(SKIPW > 0 && kRun > 0 && kPasses > 0, "walk_wave: skip weight, run cap and passes");
     static_assert(!kAxis || kMinLen > 0, "walk_wave: the axis boxes' minimum length");
@@ -629,8 +677,13 @@ __device__ __forceinline__ bool walk_wave(const skip::GridView& g, skip::Walk& w
                     if (!(w.t < bound)) {
                         mode = kMiss;
                     } else {
-                        const int cls = kAxis ? skip::classify_axis_o<MINC, kAxis ? kMinLen : 1u>(w, g, opar)
-                                              : skip::classify_dfp_o<MINC>(w, g, opar);
+                        int cls = kAxis ? skip::classify_axis_o<MINC, kAxis ? kMinLen : 1u>(w, g, opar)
+                                        : skip::classify_dfp_o<MINC>(w, g, opar);
+                        if (kGate) {  // an immature lane steps through its empty brick (the RUN word's gate)
+                            float dx = w.dx, dy = w.dy, dz = w.dz;
+                            asm volatile("" : "+v"(dx), "+v"(dy), "+v"(dz));  // the tdeltas' compares stay here
+                            cls = (cls == 2 && !skip::gate_open(w.tx, w.ty, w.tz, dx, dy, dz, kGateG, kGateN)) ? 3 : cls;
+                        }
                         // the class's outcome by selects: 0 = the solid cell (visited, hit), 2 =
                         // skip; 1 / 3 visit the cell and run on in the brick
                         cells += cls != 2 ? 1u : 0u;
@@ -678,7 +731,7 @@ __device__ __forceinline__ bool walk_wave(const skip::GridView& g, skip::Walk& w
             } else {
                 skip::df_box(w, g.n, skip::cube_dfp(w), lo, hi);
             }
-            const int sr = skip::skip_box_lean<kSeg2Branch>(w, lo, hi, bound, cells);  // 2 (refused): a plain step
+            const int sr = skip::skip_box_lean<kSeg2Branch, kMore>(w, lo, hi, bound, cells);  // 2 (refused): a plain step
             VPX_MARK("skip end");
             VPX_PH(fb += __popcll(__ballot(sr == 2));)
             if (sr == 1) {

@@ -76,6 +76,26 @@ extern "C" void build_axis(const uint64_t* l1, const uint64_t* l2, uint32_t n) {
     build_wide_planes_host(g_dfp.data(), n, g_dfw.data());
 }
 static uint64_t g_slabskips;
+// The maturity gate (vpx_skip.hpp gate_open; set_gate(0, 0): none): a class-2 brick is stepped
+// through while the gate is shut — the model of the walkers' gate bit.
+static uint32_t g_gate = 0;
+extern "C" void set_gate(int G, int f) { g_gate = G > 0 ? gate_word((uint32_t)G, (uint32_t)f) : 0u; }  // N = 4 << f
+// Further lean segments (skip_box_lean's MORE, 0..4): the model of the walkers' seg3 bit.
+static int g_more = 0;
+extern "C" void set_more(int m) { g_more = m; }
+static int lean(Walk& t, uint32_t lo[3], uint32_t hi[3], float bound, uint32_t& cc) {
+    switch (g_more) {
+    case 1: return skip_box_lean<true, 1>(t, lo, hi, bound, cc);
+    case 2: return skip_box_lean<true, 2>(t, lo, hi, bound, cc);
+    case 3: return skip_box_lean<true, 3>(t, lo, hi, bound, cc);
+    case 4: return skip_box_lean<true, 4>(t, lo, hi, bound, cc);
+    default: return skip_box_lean(t, lo, hi, bound, cc);
+    }
+}
+static uint64_t g_gated;    // classifications the gate turned into steps
+static uint64_t g_adv[12];  // landing skips by the events they advanced: 0, 1, 2, 3-4, 5-8, ... 513+
+extern "C" uint64_t gated_out() { const uint64_t v = g_gated; g_gated = 0; return v; }
+extern "C" void adv_out(uint64_t* o) { for (int i = 0; i < 12; ++i) o[i] = g_adv[i], g_adv[i] = 0; }
 static uint64_t g_seg2[4];  // skips by the number of axes that need the second closed-form segment
 extern "C" void seg2_out(uint64_t* o) { for (int i = 0; i < 4; ++i) o[i] = g_seg2[i], g_seg2[i] = 0; }
 extern "C" uint64_t slab_out() { const uint64_t v = g_slabskips; g_slabskips = 0; return v; }
@@ -113,6 +133,7 @@ extern "C" void walk_sim(const uint8_t* cells, const uint64_t* l1, const uint64_
                 cls = (k >= kMinCube || L >= (uint32_t)g_axis) ? 2 : 3;
                 if (cls == 2) df_box_axis(w, n, k, L, a, slo, shi, sec, M), slab = true;
             }
+            if (cls == 2 && !gate_open(w, g_gate)) cls = 3, ++g_gated;
             if (g_mode && cls != 0) {
                 const uint32_t bb = ((w.X >> 2) & 3u) | (((w.Y >> 2) & 3u) << 2) | (((w.Z >> 2) & 3u) << 4);
                 if (!((w.m2 >> bb) & 1ull)) {
@@ -179,8 +200,9 @@ extern "C" void walk_sim(const uint8_t* cells, const uint64_t* l1, const uint64_
                 // g_full: the exact multi-binade tier (skip_box: every box whole, any number of
                 // binade crossings) instead of the lean two-segment tier — what a lean tier with
                 // more segments could reach
-                int sr = g_full ? skip_box(t, lo, hi, bound, cc) : skip_box_lean(t, lo, hi, bound, cc);
-                if (g_full && sr == 2) sr = skip_box_lean(t, lo, hi, bound, cc);
+                // (the upper bound of what further lean segments, set_more, can reach)
+                int sr = g_full ? skip_box(t, lo, hi, bound, cc) : lean(t, lo, hi, bound, cc);
+                if (g_full && sr == 2) sr = lean(t, lo, hi, bound, cc);
                 bool clipped = false;
                 for (int k = 0; k < 3; ++k) clipped |= lo[k] != olo[k] || hi[k] != ohi[k];
                 if (sr == 2 || clipped) {
@@ -200,6 +222,11 @@ extern "C" void walk_sim(const uint8_t* cells, const uint64_t* l1, const uint64_
                 if (sr == 2) { ++c; if (!step1(w, n)) break; continue; }
                 w = t; c += cc;
                 if (sr == 1) break;
+                {
+                    int bin = 0;
+                    while (bin < 11 && (bin < 2 ? (uint32_t)bin : 1u << (bin - 1)) < cc) ++bin;
+                    g_adv[bin]++;
+                }
                 ++c;
                 if (!step1(w, n)) break;
                 continue;

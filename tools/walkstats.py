@@ -1,6 +1,7 @@
 """Per-ray walk statistics of the skipping walker on a config's world (CPU model):
 python tools/walkstats.py [C1|C2|C3], MODES="0 -2 -102" (cubes, axis boxes of minimum length 2, then
-the same boxes widened along the second axis)."""
+the same boxes widened along the second axis); GATE="1 0" adds the maturity gate (G 1, N 4 << 0),
+MORE=1 a third lean segment, FULL=1 whole boxes."""
 import ctypes as C, os, subprocess, sys
 import numpy as np
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -99,6 +100,11 @@ lib.set_wide.argtypes = [C.c_int]
 modes = [int(x) for x in os.environ.get("MODES", "0 -2 -102").split()]
 lib.set_full.argtypes = [C.c_int]
 lib.set_full(int(os.environ.get("FULL", "0")))  # 1: whole boxes (the exact multi-binade tier)
+# GATE="G f": the maturity gate (vpx_skip.hpp gate_open) with N = 4 << f; MORE=m: m further lean segments
+lib.set_gate.argtypes = [C.c_int, C.c_int]
+lib.set_gate(*[int(x) for x in os.environ.get("GATE", "0 0").split()])
+lib.set_more.argtypes = [C.c_int]
+lib.set_more(int(os.environ.get("MORE", "0")))
 for name, (a, b, bnd), mode in [(nm_, v, md) for nm_, v in sets.items() for md in modes]:
     lib.set_mode(max(mode, 0))
     lib.set_axis(max(-mode, 0) % 100)
@@ -114,4 +120,8 @@ for name, (a, b, bnd), mode in [(nm_, v, md) for nm_, v in sets.items() for md i
     cr = np.zeros(16, np.uint64); lib.cross_out.argtypes = [V]; lib.cross_out(cr.ctypes.data)
     print("   clipped boxes by binade crossings of the full box (max over axes):", cr[:10])
     s2 = np.zeros(4, np.uint64); lib.seg2_out.argtypes = [V]; lib.seg2_out(s2.ctypes.data)
+    adv = np.zeros(12, np.uint64); lib.adv_out.argtypes = [V]; lib.adv_out(adv.ctypes.data)
+    lib.gated_out.restype = C.c_uint64
+    print(f"   classifications the gate turned into steps: {lib.gated_out() / R:.2f} per ray; events per landing skip "
+          f"(0, 1, 2, -4, -8, ... 513+):", adv)
     print("   skips by #axes needing the 2nd segment:", s2, "frac any:", round(float(s2[1:].sum()) / max(1, float(s2.sum())), 4))

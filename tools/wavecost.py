@@ -109,10 +109,25 @@ def run(st_, si_, bnd_):
                  np.ascontiguousarray(si_).ctypes.data, np.ascontiguousarray(bnd_, np.float32).ctypes.data, len(st_),
                  out_.ctypes.data, th_.ctypes.data, per_.ctypes.data)
     return per_, out_, th_
+lib.set_gate.argtypes = [C.c_int, C.c_int]
+lib.set_full.argtypes = lib.set_more.argtypes = [C.c_int]
+lib.adv_out.argtypes = [V]
+def adv():  # landing skips by the events they advanced (bins 0, 1, 2, 3-4, 5-8, ... 513+), then reset
+    h = np.zeros(12, np.uint64); lib.adv_out(h.ctypes.data); return [int(x) for x in h]
+# The box kinds, then (round 10) on the wide boxes the maturity gate for G in {1, 2, 3} and N in
+# {4, 8, 16}, the lean tier with 3 to 6 segments, both, and the whole-box tier that bounds what
+# any number of segments can reach (GATES="" skips these).
+rows = [("cubes", 0, 0, 0, 0, 0, 0), ("axis boxes", 2, 0, 0, 0, 0, 0), ("wide boxes", 2, 1, 0, 0, 0, 0)]
+if os.environ.get("GATES", "1"):
+    rows += [(f"gate G{G} N{4 << f}", 2, 1, G, f, 0, 0) for G in (1, 2, 3) for f in (0, 1, 2)]
+    rows += [(f"{2 + m} segments", 2, 1, 0, 0, 0, m) for m in (1, 2, 3, 4)]
+    rows += [(f"{2 + m} seg., G{G} N{4 << f}", 2, 1, G, f, 0, m) for m in (1, 2, 3) for G, f in ((1, 0), (1, 1), (2, 0))]
+    rows += [("whole boxes", 2, 1, 0, 0, 1, 0), ("whole, G1 N4", 2, 1, 1, 0, 1, 0)]
 first = None
-for name, axis, wide in (("cubes", 0, 0), ("axis boxes", 2, 0), ("wide boxes", 2, 1)):
-    lib.set_axis(axis); lib.set_wide(wide)
+for name, axis, wide, G, f, full, more in rows:
+    lib.set_axis(axis); lib.set_wide(wide); lib.set_gate(G, f); lib.set_full(full); lib.set_more(more)
     per, out, th = run(st, si, bnd)
+    padv = adv()
     hit = ok & (th > 0)
     cp_ = np.where(ok, per[:, 0] + per[:, 1] + 1 + SKIP * per[:, 1], 0).reshape(T, 256)[:, perm]
     okp = ok.reshape(T, 256)[:, perm]
@@ -132,12 +147,16 @@ for name, axis, wide in (("cubes", 0, 0), ("axis boxes", 2, 0), ("wide boxes", 2
                           (cell * sstep.astype(np.float32)) * srD], 1).astype(np.float32)
     ssi = np.concatenate([sP0, sstep], 1).astype(np.int32)
     sper, sout, _ = run(sst[hit], ssi[hit], dist[hit])
+    sadv = adv()
     cs_ = np.zeros(len(st)); cs_[hit] = sper[:, 0] + sper[:, 1] + 1 + SKIP * sper[:, 1]
     cs_ = cs_.reshape(T, 256)[:, perm]; hp = hit.reshape(T, 256)[:, perm]
     shad = sum(waves(cs_[t][hp[t]]) for t in range(T))
     tot = prim + shad
-    first = first or tot
+    if first is None: first, first_p, first_s = tot, prim, shad
     print(f"  {name:10s}: primary skips/ray {per[ok, 1].mean():.2f} (max {per[ok, 1].max()}) steps {per[ok, 0].mean():.2f}, "
           f"shadow skips/ray {sper[:, 1].mean():.2f} (max {sper[:, 1].max()}) steps {sper[:, 0].mean():.2f}; mean cost "
           f"{cp_[okp].mean():.1f} / {cs_[hp].mean():.1f}; wave cost {prim:.0f} + {shad:.0f} = {tot:.0f} ({tot / first - 1:+.1%}); "
-          f"hits {int(hit.sum())} occluded {int(sout[3])} sum of hit t bits {int(out[5])}")
+          f"hits {int(hit.sum())} occluded {int(sout[3])} sum of hit t bits {int(out[5])}; end cells {int(out[4])} / {int(sout[4])}, "
+          f"shadow t bits {int(sout[5])}, cells {int(out[0])} / {int(sout[0])}")
+    print(f"      wave cost primary {prim / first_p - 1:+.1%} shadow {shad / first_s - 1:+.1%} vs cubes; events per landing skip "
+          f"(0, 1, 2, -4, -8, ... 513+): primary {padv} shadow {sadv}")
