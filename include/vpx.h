@@ -25,6 +25,9 @@
  *                         Scene::IsOccluded           template/scene.cpp:1009-1047
  *   vpx_trace             Renderer::Trace(Ray&, int)  renderer.cpp:1076
  *   vpx_focus_distance    focus ray in Renderer::Tick renderer.cpp:1987-1991
+ *   vpx_find_nearest_filtered  Renderer::FindNearestPlayer  renderer.cpp:1020-1071 (Tick :2139-2152)
+ *                              Scene::FindNearestExcept     template/scene.cpp:813-873
+ *   vpx_is_occluded_filtered   Renderer::IsOccludedPlayerClimbable  renderer.cpp:245-273
  *   vpx_get_player_light  Renderer::inLight           renderer.h:231; set renderer.cpp:1228-1240,
  *                                                     1438-1450; read :2112-2118, cleared :2206
  *   vpx_trace_probe       Trace's smoke-branch probe  renderer.cpp:1228-1240 (per ray)
@@ -487,6 +490,35 @@ typedef struct vpx_ray_probe { uint32_t probes, lit; float max_sqr; uint32_t res
 int vpx_trace_probe(vpx_ctx* ctx, const vpx_ray* rays, const uint32_t* seeds, uint32_t n, int32_t depth,
                     const float sky[3], int32_t area_samples, float* radiance /* may be NULL */,
                     vpx_ray_probe* probes /* n, host */);
+/* Filtered ray queries: a batch of rays cast against a chosen part of the scene, with a material
+   range treated as transparent.  Renderer::FindNearestPlayer (renderer.cpp:1020-1071, the
+   player's ray in Renderer::Tick, :2139-2152) is FindNearest from volume 1 on (volume 0 is the
+   player), without the spheres and triangles, each volume walked with
+   Scene::FindNearestExcept(ray, SMOKE_LOW_DENSITY, SMOKE_PLAYER) (template/scene.cpp:813-873):
+   filter {1, VPX_MAT_SMOKE_LOW_DENSITY, VPX_MAT_SMOKE_PLAYER, VPX_QUERY_NO_SHAPES |
+   VPX_QUERY_RAW_DIRECTION}.  Renderer::IsOccludedPlayerClimbable (renderer.cpp:245-273) is
+   IsOccluded from volume 1 on without the shapes: {1, 1, 0, VPX_QUERY_NO_SHAPES}.
+   {0, 1, 0, 0} is vpx_find_nearest / vpx_is_occluded, bit for bit.
+   vpx_hit keeps its meaning: vox_index is the index in the context's volume list (not offset by
+   first_volume; first_volume >= count visits none: -2 and t = tmax, or the shapes' result),
+   cells counts every cell read, the excepted ones the ray passed included, and inside_glass
+   comes back as given when the shapes are off.  In VPX_ARITH_X86_HOST the filtered FindNearest
+   takes FastReciprocal (renderer.cpp:1043) like vpx_find_nearest; the occlusion keeps 1 / D.
+   VPX_E_INVALID (also with n == 0): f == NULL, unknown flag bits, a non-empty range with an
+   end above 255, and any non-empty range in vpx_is_occluded_filtered (the reference has no
+   IsOccludedExcept). */
+#define VPX_QUERY_NO_SHAPES     0x1u  /* do not test spheres / triangles (FindNearestPlayer, IsOccludedPlayerClimbable) */
+#define VPX_QUERY_RAW_DIRECTION 0x2u  /* vpx_ray.direction is used as given: Ray(O, D, rD, Dsign, len), scene.cpp:29-37
+                                         (PlayerCharacter::GetRay normalises by itself, src/Game/PlayerCharacter.cpp:11-18;
+                                         normalising twice changes low bits of D, and with them t) */
+typedef struct vpx_ray_filter {       /* 16 bytes */
+    uint32_t first_volume;            /* volumes first_volume .. count-1 are visited, in index order */
+    uint32_t mat_lo, mat_hi;          /* cells with mat_lo <= m <= mat_hi are read and passed through (scene.cpp:826);
+                                         mat_lo > mat_hi: no material is excepted */
+    uint32_t flags;                   /* VPX_QUERY_* ; other bits: VPX_E_INVALID */
+} vpx_ray_filter;
+int vpx_find_nearest_filtered(vpx_ctx* ctx, const vpx_ray* rays, uint32_t n, const vpx_ray_filter* f, vpx_hit* hits);
+int vpx_is_occluded_filtered(vpx_ctx* ctx, const vpx_ray* rays, uint32_t n, const vpx_ray_filter* f, uint8_t* occluded);
 /* Focus ray of Renderer::Tick (world-space ray against every Scene::FindNearest). */
 int vpx_focus_distance(vpx_ctx* ctx, uint32_t width, uint32_t height, float* focal_distance);
 

@@ -102,6 +102,15 @@ class RayProbe(C.Structure):  # vpx_ray_probe: one ray's player light probes (vp
 PLAYER_LIGHT_SQR = 16.0  # VPX_PLAYER_LIGHT_SQR: sqrThreshold, renderer.cpp:1233, 1443
 
 
+class RayFilter(C.Structure):  # vpx_ray_filter: which volumes, which materials pass, VPX_QUERY_* flags
+    _fields_ = [("first_volume", C.c_uint32), ("mat_lo", C.c_uint32), ("mat_hi", C.c_uint32), ("flags", C.c_uint32)]
+
+
+QUERY_NO_SHAPES = 0x1      # VPX_QUERY_NO_SHAPES: no spheres / triangles (FindNearestPlayer, IsOccludedPlayerClimbable)
+QUERY_RAW_DIRECTION = 0x2  # VPX_QUERY_RAW_DIRECTION: direction used as given (the five-argument Ray constructor)
+MAT_SMOKE_LOW_DENSITY, MAT_SMOKE_PLAYER = 9, 14  # VPX_MAT_SMOKE_*: the range FindNearestPlayer passes through
+
+
 class PrevCamera(C.Structure):
     _fields_ = [("cam_pos", f3), ("left_normal", f3), ("right_normal", f3), ("top_normal", f3),
                 ("bottom_normal", f3), ("pad", C.c_float)]
@@ -128,7 +137,7 @@ STAGES = ("primary", "shade", "shadow", "resolve", "bounce", "finish", "frame", 
 
 STRUCT_SIZES = {PrevCamera: 64, Profile: 160, Volume: 160, Material: 32, PointLight: 24, SpotLight: 40, AreaLight: 32, DirLight: 24,
                 Sphere: 32, Triangle: 64, Camera: 80, FrameParams: 48, Ray: 32, Hit: 32, Stats: 40,
-                BvhTri: 36, BvhNode: 32, PlayerLight: 24, RayProbe: 16}
+                BvhTri: 36, BvhNode: 32, PlayerLight: 24, RayProbe: 16, RayFilter: 16}
 
 
 def np_dtype(struct):
@@ -201,6 +210,8 @@ SIGNATURES = {
     "vpx_trace_probe": (C.c_int, [C.c_void_p, C.POINTER(Ray), C.c_void_p, C.c_uint32, C.c_int32, C.POINTER(C.c_float),
                                   C.c_int32, C.c_void_p, C.POINTER(RayProbe)]),
     "vpx_get_player_light": (C.c_int, [C.c_void_p, C.POINTER(PlayerLight), C.c_int]),
+    "vpx_find_nearest_filtered": (C.c_int, [C.c_void_p, C.POINTER(Ray), C.c_uint32, C.POINTER(RayFilter), C.POINTER(Hit)]),
+    "vpx_is_occluded_filtered": (C.c_int, [C.c_void_p, C.POINTER(Ray), C.c_uint32, C.POINTER(RayFilter), C.c_void_p]),
     "vpx_focus_distance": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_float)]),
     "vpx_camera_look_at": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_uint32, C.c_uint32,
                                      C.POINTER(Camera)]),

@@ -247,6 +247,35 @@ class Context:
         self._chk(self.lib.vpx_is_occluded(self.h, rays, n, occ.ctypes.data_as(C.c_void_p)), "vpx_is_occluded")
         return occ[:n]
 
+    @staticmethod
+    def ray_filter(first_volume=0, except_materials=None, shapes=True, raw_direction=False):
+        """abi.RayFilter: except_materials = (lo, hi), the cells read and passed through; None: none."""
+        lo, hi = (1, 0) if except_materials is None else except_materials
+        flags = (0 if shapes else abi.QUERY_NO_SHAPES) | (abi.QUERY_RAW_DIRECTION if raw_direction else 0)
+        return abi.RayFilter(int(first_volume), int(lo), int(hi), flags)
+
+    def find_nearest_filtered(self, rays, first_volume=0, except_materials=None, shapes=True, raw_direction=False,
+                              filter=None):
+        """vpx_find_nearest_filtered: FindNearest over the volumes first_volume .. count-1 with the
+        materials except_materials = (lo, hi) passed through (Scene::FindNearestExcept), without
+        the spheres / triangles when shapes is False; raw_direction: direction used as given.
+        filter: an abi.RayFilter instead of the keywords."""
+        n = len(rays)
+        hits = (abi.Hit * max(1, n))()
+        f = filter if filter is not None else self.ray_filter(first_volume, except_materials, shapes, raw_direction)
+        self._chk(self.lib.vpx_find_nearest_filtered(self.h, rays, n, C.byref(f), hits), "vpx_find_nearest_filtered")
+        return hits
+
+    def is_occluded_filtered(self, rays, first_volume=0, shapes=True, raw_direction=False, filter=None):
+        """vpx_is_occluded_filtered: IsOccluded over the volumes first_volume .. count-1, without the
+        spheres / triangles when shapes is False (Renderer::IsOccludedPlayerClimbable: 1, False)."""
+        n = len(rays)
+        occ = np.zeros(max(1, n), np.uint8)
+        f = filter if filter is not None else self.ray_filter(first_volume, None, shapes, raw_direction)
+        self._chk(self.lib.vpx_is_occluded_filtered(self.h, rays, n, C.byref(f), occ.ctypes.data_as(C.c_void_p)),
+                  "vpx_is_occluded_filtered")
+        return occ[:n]
+
     def trace(self, rays, seeds, depth, sky=abi.SKY_DEFAULT, area_samples=3):
         """Renderer::Trace per ray; sky=None samples the sky texture (activateSky)."""
         n = len(rays)

@@ -252,6 +252,7 @@ static_assert(sizeof(vpx_point_light) == 24 && sizeof(vpx_spot_light) == 40, "li
 static_assert(sizeof(vpx_profile) == 160, "vpx_profile layout");
 static_assert(sizeof(vpx_prev_camera) == 64, "vpx_prev_camera layout");
 static_assert(sizeof(vpx_player_light) == 24 && sizeof(vpx_ray_probe) == 16, "player light layout");
+static_assert(sizeof(vpx_ray_filter) == 16, "ray filter layout");
 static_assert(sizeof(vpx_area_light) == 32 && sizeof(vpx_dir_light) == 24, "light layout");
 static_assert(sizeof(vpx_sphere) == 32 && sizeof(vpx_triangle) == 64, "shape layout");
 static_assert(sizeof(vpx_camera) == 80 && sizeof(vpx_frame_params) == 48, "camera/frame layout");

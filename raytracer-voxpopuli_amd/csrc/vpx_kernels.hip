@@ -164,6 +164,39 @@ __global__ void is_occluded_k(SceneView sv, const vpx_ray* rays, uint32_t n, uin
     occ[i] = is_occluded(sv, r, k) ? 1 : 0;
 }
 
+// The filtered unit entries (vpx_find_nearest_filtered / vpx_is_occluded_filtered).
+// VPX_QUERY_RAW_DIRECTION: Ray(O, D, rD, Dsign, len) (scene.cpp:29-37) takes D as given; rD and
+// Dsign are formed per volume here, from the object-space D.
+__device__ __forceinline__ Ray ray_from(const vpx_ray& in, uint32_t flags) {
+    Ray r = ray_from(in);
+    if (flags & VPX_QUERY_RAW_DIRECTION) r.D = ld3(in.direction);
+    return r;
+}
+
+__global__ void find_nearest_filtered_k(SceneView sv, const vpx_ray* rays, uint32_t n, vpx_ray_filter f, vpx_hit* hits) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    Ray r = ray_from(rays[i], f.flags);
+    Counters k{0u, 0u, 0u};
+    const int32_t vox = find_nearest_filtered(sv, r, k, f.first_volume, f.mat_lo, f.mat_hi, !(f.flags & VPX_QUERY_NO_SHAPES));
+    vpx_hit h;
+    h.t = r.t;
+    h.normal[0] = r.N.x, h.normal[1] = r.N.y, h.normal[2] = r.N.z;
+    h.vox_index = vox;
+    h.material = r.mat;
+    h.cells = k.cells;
+    h.inside_glass = r.inside ? 1u : 0u;
+    hits[i] = h;
+}
+
+__global__ void is_occluded_filtered_k(SceneView sv, const vpx_ray* rays, uint32_t n, vpx_ray_filter f, uint8_t* occ) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const Ray r = ray_from(rays[i], f.flags);
+    Counters k{0u, 0u, 0u};
+    occ[i] = is_occluded(sv, r, k, f.first_volume, !(f.flags & VPX_QUERY_NO_SHAPES)) ? 1 : 0;
+}
+
 // BasicBVH::IntersectBVH (src/BVH/BasicBVH.cpp:19-70), one ray per lane.  The workgroup
 // stages the whole BVH in LDS (nodes, then the triangles already permuted into tri_idx
 // order, so a leaf's triangles are contiguous); the recursion (node test, then left
@@ -2381,6 +2414,60 @@ int vpx_is_occluded(vpx_ctx* c, const vpx_ray* rays, uint32_t n, uint8_t* occ) {
     VPX_HIP(c, hipMemcpyAsync(dr, rays, rb, hipMemcpyHostToDevice, c->stream));
     const float sky[3] = {0.392f, 0.584f, 0.829f};
     hipLaunchKernelGGL(is_occluded_k, dim3((n + 255) / 256), dim3(256), 0, c->stream, view_of(c, sky, 3), dr, n, doc);
+    VPX_HIP(c, hipGetLastError());
+    VPX_HIP(c, hipMemcpyAsync(occ, doc, n, hipMemcpyDeviceToHost, c->stream));
+    VPX_HIP(c, sync_all(c));
+    return VPX_OK;
+}
+
+// The filter's refusals, the same for n == 0.  occlusion: the reference has no IsOccludedExcept,
+// so a material range is refused there.
+static int check_filter(vpx_ctx* c, const vpx_ray_filter* f, bool occlusion) {
+    if (!f) return fail(c, VPX_E_INVALID, "null filter");
+    if (f->flags & ~(VPX_QUERY_NO_SHAPES | VPX_QUERY_RAW_DIRECTION)) return fail(c, VPX_E_INVALID, "unknown VPX_QUERY_* flag");
+    if (f->mat_lo <= f->mat_hi) {
+        if (occlusion) return fail(c, VPX_E_INVALID, "vpx_is_occluded_filtered takes no material range (mat_lo > mat_hi)");
+        if (f->mat_hi > 255u) return fail(c, VPX_E_INVALID, "material range above 255");
+    }
+    return VPX_OK;
+}
+
+int vpx_find_nearest_filtered(vpx_ctx* c, const vpx_ray* rays, uint32_t n, const vpx_ray_filter* f, vpx_hit* hits) {
+    VPX_GROUP_FIRST(c, vpx_find_nearest_filtered(m_, rays, n, f, hits));
+    if (!c || (n && (!rays || !hits))) return fail(c, VPX_E_INVALID, "null argument");
+    int rc = check_filter(c, f, false);
+    if (rc) return rc;
+    if ((rc = check_ready(c))) return rc;
+    if (n == 0) return VPX_OK;
+    const size_t rb = sizeof(vpx_ray) * n, hb = sizeof(vpx_hit) * n;
+    if ((rc = ensure_scratch(c, rb + hb))) return rc;
+    vpx_ray* dr = (vpx_ray*)c->d_scratch;
+    vpx_hit* dh = (vpx_hit*)((char*)c->d_scratch + rb);
+    VPX_HIP(c, hipMemcpyAsync(dr, rays, rb, hipMemcpyHostToDevice, c->stream));
+    const float sky[3] = {0.392f, 0.584f, 0.829f};
+    hipLaunchKernelGGL(find_nearest_filtered_k, dim3((n + 255) / 256), dim3(256), 0, c->stream, view_of(c, sky, 3), dr, n,
+                       *f, dh);
+    VPX_HIP(c, hipGetLastError());
+    VPX_HIP(c, hipMemcpyAsync(hits, dh, hb, hipMemcpyDeviceToHost, c->stream));
+    VPX_HIP(c, sync_all(c));
+    return VPX_OK;
+}
+
+int vpx_is_occluded_filtered(vpx_ctx* c, const vpx_ray* rays, uint32_t n, const vpx_ray_filter* f, uint8_t* occ) {
+    VPX_GROUP_FIRST(c, vpx_is_occluded_filtered(m_, rays, n, f, occ));
+    if (!c || (n && (!rays || !occ))) return fail(c, VPX_E_INVALID, "null argument");
+    int rc = check_filter(c, f, true);
+    if (rc) return rc;
+    if ((rc = check_ready(c))) return rc;
+    if (n == 0) return VPX_OK;
+    const size_t rb = sizeof(vpx_ray) * n;
+    if ((rc = ensure_scratch(c, rb + n))) return rc;
+    vpx_ray* dr = (vpx_ray*)c->d_scratch;
+    uint8_t* doc = (uint8_t*)c->d_scratch + rb;
+    VPX_HIP(c, hipMemcpyAsync(dr, rays, rb, hipMemcpyHostToDevice, c->stream));
+    const float sky[3] = {0.392f, 0.584f, 0.829f};
+    hipLaunchKernelGGL(is_occluded_filtered_k, dim3((n + 255) / 256), dim3(256), 0, c->stream, view_of(c, sky, 3), dr, n,
+                       *f, doc);
     VPX_HIP(c, hipGetLastError());
     VPX_HIP(c, hipMemcpyAsync(occ, doc, n, hipMemcpyDeviceToHost, c->stream));
     VPX_HIP(c, sync_all(c));

@@ -1112,6 +1112,100 @@ __device__ __forceinline__ int32_t find_nearest(const SceneView& sv, Ray& r, Cou
     return vox;
 }
 
+// Renderer::FindNearestPlayer (renderer.cpp:1020-1071) generalised (vpx_find_nearest_filtered):
+// find_nearest's loop over the volumes first .. count-1, each walked as Scene::FindNearestExcept
+// (template/scene.cpp:813-873) with the cells mlo <= m <= mhi read and passed through
+// (mlo > mhi: none, Scene::FindNearest), the shapes only when `shapes`.
+// The walkers' levels know only "cell != NONE", so an excepted cell ends walk_wave with a hit.
+// The lane then reads the cell's byte and, when it lies in the range, does what scene.cpp:835-864
+// does after the failed test: the cell's leaving event (skip::step1; the cell was counted when it
+// was visited), a miss when that leaves the grid, else it walks on under the same bound.  The
+// phases of walk_wave are wave-uniform, so the rounds are too: the wave re-enters the walk (its
+// POOL form, the lanes' modes through *pmode; finished lanes take no part) while any lane walks on.
+// Reference arithmetic and the culls: FastReciprocal of a zero object-space component is NaN
+// (inf * 0), and with a NaN slab Cube::Intersect's compares (scene.cpp:166-202) all fail, so the
+// reference enters a volume wherever the other two slabs let it, also one that the ray's
+// segment never reaches.  The player's rays have such components (up along an axis), so in that
+// mode a lane with a NaN rD is not culled by the volume's box, and the volumes are walked
+// linearly: the TLAS is a cull of the same kind and cannot know a lane's object-space D.
+__device__ __forceinline__ bool rcp_nan(float x) {  // zero (denormals flush), infinite or NaN
+    return !(fabsf(x) > 0.0f && fabsf(x) < __builtin_inff());
+}
+template <uint32_t SKIPW = kSkipwNearest, uint32_t MINC = kMincNearest, uint32_t RUN = kRunNearest>
+__device__ __forceinline__ int32_t find_nearest_filtered(const SceneView& sv, Ray& r, Counters& k, uint32_t first,
+                                                         uint32_t mlo, uint32_t mhi, bool shapes) {
+    int32_t vox = -2;
+    ++k.nearest;
+    uint32_t hmat = kNone;  // the byte of the hit cell in volume `vox`
+    const f3 inv = world_inv(r.D);
+    auto visit = [&](uint32_t i) {
+        if (i < first) return true;  // not visited: no cell read or counted
+        const vpx_volume& vol = sv.volumes[i];
+        ORay o;
+        o.D = xform_vec_ssem(r.D, vol.inv_matrix);
+        // the cull stands for Setup3DDDA failing, unless the reference's rD is NaN there (see above)
+        if (!(sv.x86.tab && (rcp_nan(o.D.x) || rcp_nan(o.D.y) || rcp_nan(o.D.z))) &&
+            misses_volume(sv.vbounds, i, r.O, inv, r.t))
+            return true;
+        const DevGrid g = sv.grids[vol.grid_id];
+        skip::Walk w;
+        {
+            o.O = xform_pos_ssem(r.O, vol.inv_matrix);
+            o.rD = nearest_rd(o.D, sv.x86);
+            Dda s;
+            if (!dda_setup(vol, g.n, o, s)) return true;
+            w = to_walk(s);
+        }
+        const skip::GridView gv = grid_view(g);
+        int mode = kWalkStep;
+        uint32_t cell = kNone;
+        for (;;) {
+            walk_wave<0, SKIPW, MINC, RUN, true>(gv, w, r.t, k.cells, &mode);
+            bool on = false;
+            if (mode == kWalkHit) {
+                cell = gv.cells[(uint64_t)w.X + (uint64_t)w.Y * gv.n + (uint64_t)w.Z * ((uint64_t)gv.n * gv.n)];
+                if (cell >= mlo && cell <= mhi) {  // scene.cpp:826: passed through
+                    on = skip::step1<((RUN >> 18) & 1u) != 0u>(w, gv.n);
+                    mode = on ? kWalkStep : kWalkMiss;
+                }
+            }
+            if (!__ballot(on)) break;
+        }
+        if (mode == kWalkHit) {
+            r.t = w.t;
+            hmat = cell;
+            vox = (int32_t)i;
+        }
+        return true;
+    };
+    if (sv.tlas_on && !sv.x86.tab)
+        for_volumes(sv, r.O, inv, r.t, visit);
+    else
+        for (uint32_t i = first; i < sv.num_volumes; ++i) visit(i);
+    if (vox >= 0) {
+        const vpx_volume& vol = sv.volumes[vox];
+        const DevGrid g = sv.grids[vol.grid_id];
+        ORay o;
+        o.O = xform_pos_ssem(r.O, vol.inv_matrix);
+        o.D = xform_vec_ssem(r.D, vol.inv_matrix);
+        r.N = normal_voxel(o, r.t, g.n, vol.matrix);
+        r.mat = hmat;
+    }
+    if (shapes && (sv.num_spheres | sv.num_triangles)) {
+        Ray sh = make_ray(r.O, r.D);
+        for (uint32_t i = 0; i < sv.num_spheres; ++i) sphere_hit(sv.spheres[i], sh);
+        for (uint32_t i = 0; i < sv.num_triangles; ++i) tri_hit(sv.triangles[i], sh);
+        if (r.t > sh.t) {
+            r.t = sh.t;
+            r.mat = sh.mat;
+            r.N = sh.N;
+            r.inside = sh.inside;
+            vox = -1;
+        }
+    }
+    return vox;
+}
+
 #ifndef VPX_LANE_VOLUMES
 #define VPX_LANE_VOLUMES 1
 #endif
@@ -1222,7 +1316,9 @@ __device__ __forceinline__ bool find_nearest_rest(const SceneView& sv, Ray& r, C
 // world, volume 0).  The instances alone through the TLAS (the world's walk left to the pool)
 // were slower too: C4 48.6-48.9 vs 47.2-47.4 ms per step at 5 waves/SIMD (8 spilled VGPRs),
 // 50.4-50.6 at 4 (round 3, three interleaved runs).
-__device__ __forceinline__ bool is_occluded(const SceneView& sv, const Ray& r, Counters& k, uint32_t first = 0) {
+// shapes: false leaves the spheres and triangles out (vpx_is_occluded_filtered).
+__device__ __forceinline__ bool is_occluded(const SceneView& sv, const Ray& r, Counters& k, uint32_t first = 0,
+                                            bool shapes = true) {
     bool occ = false;
     const f3 inv = world_inv(r.D);
     auto visit = [&](uint32_t i) {
@@ -1242,6 +1338,7 @@ __device__ __forceinline__ bool is_occluded(const SceneView& sv, const Ray& r, C
     };
     for (uint32_t i = first; i < sv.num_volumes && !occ; ++i) visit(i);
     if (occ) return true;
+    if (!shapes) return false;  // Renderer::IsOccludedPlayerClimbable (renderer.cpp:245-273): the volumes only
     for (uint32_t i = 0; i < sv.num_spheres; ++i)
         if (sphere_is_hit(sv.spheres[i], r)) return true;
     for (uint32_t i = 0; i < sv.num_triangles; ++i)

@@ -13,12 +13,18 @@
 //   of player smoke (SMOKE_PLAYER, cells x in [3n/4, 7n/8), y in [2, 2 + n/4), z in [n/4, 3n/8),
 //   albedo (0.8, 0.75, 0.7)) into the world under a point light of colour 8, tracks the player
 //   light (Renderer::trackPlayerLight: every Tick reads and clears the record, as the game's
-//   Tick does with inLight) and prints the run's sums as a second JSON line; '-' none.
+//   Tick does with inLight) and prints the run's sums as a second JSON line; 'w' renders nothing:
+//   it builds the zone scene's 21 volumes (scene.py zone_scene) and casts the player's four
+//   W / D / S / A rays (Renderer::FindNearestPlayer, renderer.cpp:2139-2152) from the player's
+//   centre, printing index, t, normal and material of each, and IsOccludedPlayerClimbable of
+//   the same ray, as one JSON line; '-' none.
 //   devices: comma-separated HIP devices, e.g. 0,1,2,3 — a device set (vpx_create_multi:
 //   tiles over the devices, RCCL gather to the first); default: device 0 alone.
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <vector>
 
 #include "vpx_renderer.h"
@@ -62,6 +68,79 @@ static std::vector<float> demo_sky(uint32_t w, uint32_t h) {
         }                                                                                     \
     } while (0)
 
+// Mode 'w': the volumes of scene.py's zone_scene (Renderer::SetUpFirstZone, renderer.cpp:592-657)
+// and the player's four rays.  The two model volumes hold empty grids here (the demo carries no
+// model store): volume 0, the player, which the cast never visits, and volume 6, the Text,
+// whose box (y in [1, 6]) lies above the rays, so neither changes a result or a cell count.
+static int player_rays(vpxhost::Renderer& r) {
+    struct V { float p[3], s[3]; int grid; };  // grid: >= 0 a 1^3 grid of that material; -1 smoke, -2 / -3 / -4 empty 64 / 16 / 32
+    static const V zone[21] = {
+        {{0, 0, 0}, {1, 1, 1}, -3},          {{0, -1, 0}, {5, 1, 5}, 7},        {{6, 0, 0}, {5, 5, 5}, 7},
+        {{-10, 2, 0}, {5, 5, 5}, 7},         {{0, 4, 0}, {10, 1, 10}, 7},       {{0, 0.3f, 0}, {3, 3, 3}, -1},
+        {{0, 3, -3}, {5, 5, 5}, -4},         {{0, 4, -7}, {10, 1, 5}, 1},       {{-1, 0, -11}, {3, 10, 1}, 8},
+        {{-5, 1, -12}, {2, 3, 10}, 2},       {{-3, 1, -19}, {7, 1, 1}, 3},      {{0, -1, -18}, {5, 1, 5}, 6},
+        {{0, 0.3f, -17}, {2, 2, 2}, -2},     {{0, -2, -24}, {10, 1, 5}, 0},     {{-1, 0, -28}, {3, 10, 1}, 8},
+        {{5, -41, -29}, {2, 3, 10}, 7},      {{-5, 1, -29}, {2, 3, 10}, 4},     {{3, 51, -36}, {7, 1, 1}, 8},
+        {{-3, 1, -36}, {7, 1, 1}, 2},        {{0, -1, -35}, {5, 1, 5}, 1},      {{0, 0.3f, -34}, {2, 2, 2}, -2}};
+    // grids 0..8: the 1^3 grids of materials 0..8; 9 the smoke ball; 10 / 11 / 12 empty 64^3 / 16^3 / 32^3
+    for (uint32_t m = 0; m <= 8; ++m) {
+        const uint8_t cell = (uint8_t)m;
+        CHECK(r.UploadGrid(m, &cell, 1));
+    }
+    std::vector<uint8_t> g(64 * 64 * 64, VPX_MAT_NONE);
+    CHECK(r.UploadGrid(10, g.data(), 64));
+    CHECK(r.UploadGrid(11, g.data(), 16));
+    CHECK(r.UploadGrid(12, g.data(), 32));
+    for (uint32_t z = 0; z < 64; ++z)  // the checkpoint's smoke ball: 9 + int(r) % 5 where r < 20
+        for (uint32_t y = 0; y < 64; ++y)
+            for (uint32_t x = 0; x < 64; ++x) {
+                const float dx = (float)x - 31.5f, dy = (float)y - 31.5f, dz = (float)z - 31.5f;
+                const float d2 = dx * dx + dy * dy + dz * dz;  // multiples of 0.25: exact
+                const float rr = std::sqrt(d2);
+                if (rr < 20.0f) g[x + 64u * y + 4096u * z] = (uint8_t)(9 + (int)rr % 5);
+            }
+    CHECK(r.UploadGrid(9, g.data(), 64));
+    std::vector<vpx_volume> vols(21);
+    const float zero[3] = {0, 0, 0};
+    for (int i = 0; i < 21; ++i) {
+        CHECK(vpx_volume_set_transform(zone[i].p, zone[i].s, zero, &vols[i]));
+        const int gi = zone[i].grid;
+        vols[i].grid_id = gi >= 0 ? (uint32_t)gi : gi == -1 ? 9u : gi == -2 ? 10u : gi == -3 ? 11u : 12u;
+    }
+    CHECK(r.SetVolumes(vols));
+    std::vector<vpx_material> mats(VPX_NUM_MATERIALS);
+    CHECK(vpx_default_materials(mats.data()));
+    CHECK(r.SetMaterials(mats));
+    // PlayerCharacter::UpdateInput's directions (PlayerCharacter.cpp:61-90), up = +y, GetRay (:11-18):
+    // dir = normalize(direction - up) = v * (1 / sqrtf(dot(v, v))), length 3 (PlayerCharacter.h:24)
+    const float eps = 1e-6f;  // EPSILON, template/common.h:11
+    const struct { char key; float d[3]; } wasd[4] = {
+        {'W', {eps, eps, -1}}, {'D', {-1, eps, eps}}, {'S', {eps, eps, 1}}, {'A', {1, eps, eps}}};
+    std::printf("{\"player_rays\": [");
+    for (int k = 0; k < 4; ++k) {
+        const float vx = wasd[k].d[0] - 0.0f, vy = wasd[k].d[1] - 1.0f, vz = wasd[k].d[2] - 0.0f;
+        const float xx = vx * vx, yy = vy * vy, zz = vz * vz;
+        const float xy = xx + yy;
+        const float len2 = xy + zz;
+        const float inv = 1.0f / std::sqrt(len2);
+        vpxhost::PlayerRay ray{{0.5f, 0.5f, 0.5f}, {vx * inv, vy * inv, vz * inv}, 3.0f};
+        int32_t vox = 0;
+        CHECK(r.FindNearestPlayer(ray, &vox));
+        bool occ = false;
+        vpxhost::PlayerRay probe = ray;
+        probe.t = 3.0f;
+        CHECK(r.IsOccludedPlayerClimbable(probe, &occ));
+        uint32_t b[4];
+        std::memcpy(&b[0], &ray.t, 4);
+        std::memcpy(&b[1], ray.rayNormal, 12);
+        std::printf("%s{\"key\": \"%c\", \"vox\": %d, \"t\": %.9g, \"t_bits\": %u, \"normal_bits\": [%u, %u, %u], "
+                    "\"material\": %u, \"occluded\": %d}",
+                    k ? ", " : "", wasd[k].key, vox, ray.t, b[0], b[1], b[2], b[3], ray.indexMaterial, occ ? 1 : 0);
+    }
+    std::printf("]}\n");
+    return 0;
+}
+
 int main(int argc, char** argv) {
     const uint32_t n = argc > 1 ? (uint32_t)atoi(argv[1]) : 256;
     const uint32_t W = argc > 2 ? (uint32_t)atoi(argv[2]) : 640;
@@ -70,8 +149,9 @@ int main(int argc, char** argv) {
     const int bounces = argc > 5 ? atoi(argv[5]) : 0;
     const char* out = argc > 6 && argv[6][0] != '-' ? argv[6] : nullptr;
     const char* mode = argc > 7 ? argv[7] : "";
-    bool is_static = false, sky = false, player_light = false;
-    for (const char* m = mode; *m; ++m) is_static |= *m == 's', sky |= *m == 'k', player_light |= *m == 'p';
+    bool is_static = false, sky = false, player_light = false, player_cast = false;
+    for (const char* m = mode; *m; ++m)
+        is_static |= *m == 's', sky |= *m == 'k', player_light |= *m == 'p', player_cast |= *m == 'w';
     std::vector<int> devices;
     if (argc > 8)
         for (const char* d = argv[8]; *d;) {
@@ -82,6 +162,7 @@ int main(int argc, char** argv) {
 
     vpxhost::Renderer r = devices.empty() ? vpxhost::Renderer(0) : vpxhost::Renderer(devices);
     CHECK(r.Init(W, H));
+    if (player_cast) return player_rays(r);
     std::vector<uint8_t> grid = pillars(n);
     if (player_light)  // the player: a block of smoke in the world, which is volume 0
         for (uint32_t z = n / 4; z < 3 * n / 8; ++z)

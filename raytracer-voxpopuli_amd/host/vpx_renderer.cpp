@@ -48,7 +48,10 @@ int Renderer::UploadGrid(uint32_t grid_id, const uint8_t* cells, uint32_t n) {
 }
 
 int Renderer::SetVolumes(const std::vector<vpx_volume>& v) {
-    return status_ ? status_ : vpx_set_volumes(ctx_, v.data(), (uint32_t)v.size());
+    if (status_) return status_;
+    const int rc = vpx_set_volumes(ctx_, v.data(), (uint32_t)v.size());
+    if (rc == VPX_OK) numVolumes_ = v.size();
+    return rc;
 }
 
 int Renderer::SetMaterials(const std::vector<vpx_material>& m) {
@@ -166,6 +169,41 @@ int Renderer::ReadPlayerLight(int rc) {
     if (rc || !trackPlayerLight) return rc;
     rc = vpx_get_player_light(ctx_, &playerLight, 1);
     if (!rc) inLight = playerLight.in_light != 0;
+    return rc;
+}
+
+static vpx_ray player_ray(const PlayerRay& ray) {
+    vpx_ray r{};
+    for (int i = 0; i < 3; ++i) r.origin[i] = ray.O[i], r.direction[i] = ray.D[i];
+    r.tmax = ray.t;
+    return r;
+}
+
+int Renderer::FindNearestPlayer(PlayerRay& ray, int32_t* vox_index) {
+    if (status_) return status_;
+    if (!vox_index) return VPX_E_INVALID;
+    const vpx_ray r = player_ray(ray);
+    const vpx_ray_filter f{1u, VPX_MAT_SMOKE_LOW_DENSITY, VPX_MAT_SMOKE_PLAYER, VPX_QUERY_NO_SHAPES | VPX_QUERY_RAW_DIRECTION};
+    vpx_hit h{};
+    const int rc = vpx_find_nearest_filtered(ctx_, &r, 1, &f, &h);
+    if (rc) return rc;
+    if (h.vox_index >= 0) {
+        ray.t = h.t;
+        for (int i = 0; i < 3; ++i) ray.rayNormal[i] = h.normal[i];
+        ray.indexMaterial = h.material;
+    }
+    *vox_index = player_vox_index(h.vox_index, numVolumes_, currentChunk);
+    return VPX_OK;
+}
+
+int Renderer::IsOccludedPlayerClimbable(const PlayerRay& ray, bool* occluded) {
+    if (status_) return status_;
+    if (!occluded) return VPX_E_INVALID;
+    const vpx_ray r = player_ray(ray);
+    const vpx_ray_filter f{1u, 1u, 0u, VPX_QUERY_NO_SHAPES | VPX_QUERY_RAW_DIRECTION};
+    uint8_t occ = 0;
+    const int rc = vpx_is_occluded_filtered(ctx_, &r, 1, &f, &occ);
+    if (rc == VPX_OK) *occluded = occ != 0;
     return rc;
 }
 

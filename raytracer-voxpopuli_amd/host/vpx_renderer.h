@@ -20,6 +20,22 @@
 
 namespace vpxhost {
 
+// The end of Renderer::FindNearestPlayer (renderer.cpp:1068-1069): from chunk 2 on, an index
+// above size() - 4 in the reference's unsigned compare becomes -1 — the last three volumes,
+// and a miss too (-2 is a huge uint32_t; size() - 4 is a size_t and wraps below four volumes).
+inline int32_t player_vox_index(int32_t vox, size_t n_volumes, int32_t current_chunk) {
+    if (current_chunk >= 2 && static_cast<uint32_t>(vox) > n_volumes - 4) return -1;
+    return vox;
+}
+
+// The fields of the reference Ray (template/scene.h) that the player's casts read and write.
+struct PlayerRay {
+    float O[3], D[3];  // D is used as given (PlayerCharacter::GetRay normalises by itself)
+    float t;
+    float rayNormal[3] = {0, 0, 0};
+    uint32_t indexMaterial = VPX_MAT_NONE;
+};
+
 class Renderer {
 public:
     explicit Renderer(int device = 0);
@@ -68,6 +84,14 @@ public:
     int CopyAccumulator(float* host_rgba) const;
     int CopyHistory(float* host_rgba) const;  // illuminationHistoryBuffer (static branch)
 
+    // --- the player's casts (Renderer::Tick, renderer.cpp:2139-2152) -----------------------
+    // Renderer::FindNearestPlayer (renderer.cpp:1020-1071): volumes 1 .. n-1 (0 is the player),
+    // smoke passed through (Scene::FindNearestExcept), no spheres / triangles.  *vox_index = the
+    // volume index after player_vox_index; on a hit t, rayNormal and indexMaterial are updated.
+    int FindNearestPlayer(PlayerRay& ray, int32_t* vox_index);
+    // Renderer::IsOccludedPlayerClimbable (renderer.cpp:245-273).
+    int IsOccludedPlayerClimbable(const PlayerRay& ray, bool* occluded);
+
     const char* LastError() const;
     vpx_ctx* Context() const { return ctx_; }
 
@@ -90,8 +114,10 @@ public:
     bool inLight = false;
     bool trackPlayerLight = false;
     vpx_player_light playerLight{};  // the last tracked Tick's record
+    int32_t currentChunk = 0;        // read by FindNearestPlayer (renderer.cpp:1068)
 
 private:
+    size_t numVolumes_ = 0;  // voxelVolumes.size() as SetVolumes left it
     int UpdateStatic(vpx_stats* stats);
     int ReadPlayerLight(int rc);  // after a Tick's render (rc: its status)
     int MapScreen(uint32_t** out) const;  // the frame's RGB8 target: the GL buffer or screen_

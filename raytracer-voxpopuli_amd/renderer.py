@@ -10,7 +10,26 @@ libvpx_hip.so (`vpx_render`) instead of the execution::par pixel loop
 import torch
 
 from . import abi
-from .context import Context
+from .context import Context, make_rays
+
+
+def player_vox_index(vox, n_volumes, current_chunk):
+    """The end of Renderer::FindNearestPlayer (renderer.cpp:1068-1069): from chunk 2 on, an index
+    above size - 4 in the reference's unsigned compare becomes -1: the last three volumes,
+    and a miss too (-2 is a huge uint32_t).  size() - 4 is a size_t: it wraps below four volumes."""
+    if current_chunk >= 2 and (int(vox) & 0xFFFFFFFF) > ((int(n_volumes) - 4) & 0xFFFFFFFFFFFFFFFF):
+        return -1
+    return int(vox)
+
+
+class Ray:
+    """The fields of the reference Ray (template/scene.h) that the player's casts read and write:
+    O, D (used as given: PlayerCharacter::GetRay normalises by itself), t, rayNormal, indexMaterial."""
+
+    def __init__(self, origin, direction, t=1e34):
+        self.O, self.D, self.t = tuple(origin), tuple(direction), float(t)
+        self.rayNormal = (0.0, 0.0, 0.0)
+        self.indexMaterial = abi.MAT_NONE
 
 
 class Renderer:
@@ -38,6 +57,7 @@ class Renderer:
         self.inLight = False
         self.trackPlayerLight = False
         self.last_player_light = None  # abi.PlayerLight of the last tracked Tick
+        self.currentChunk = 0  # renderer.h: read by FindNearestPlayer (renderer.cpp:1068)
 
     def Init(self):
         """Renderer::Init minus window/asset/game setup (renderer.cpp:688-736)."""
@@ -112,6 +132,24 @@ class Renderer:
         if self.trackPlayerLight:
             self.last_player_light = self.ctx.player_light(reset=True)
             self.inLight = bool(self.last_player_light.in_light)
+
+    def FindNearestPlayer(self, ray):
+        """Renderer::FindNearestPlayer (renderer.cpp:1020-1071), the player's cast in Tick
+        (:2139-2152): volumes 1 .. n-1 (0 is the player), smoke passed through
+        (Scene::FindNearestExcept), no spheres / triangles, ray.D as given.  Returns the volume
+        index (player_vox_index) and, on a hit, leaves t, rayNormal and indexMaterial in `ray`."""
+        h = self.ctx.find_nearest_filtered(make_rays([ray.O], [ray.D], ray.t), 1,
+                                           (abi.MAT_SMOKE_LOW_DENSITY, abi.MAT_SMOKE_PLAYER), shapes=False,
+                                           raw_direction=True)[0]
+        if h.vox_index >= 0:
+            ray.t, ray.rayNormal, ray.indexMaterial = h.t, tuple(h.normal), h.material
+        return player_vox_index(h.vox_index, len(self.scene.volumes), self.currentChunk)
+
+    def IsOccludedPlayerClimbable(self, ray):
+        """Renderer::IsOccludedPlayerClimbable (renderer.cpp:245-273): IsOccluded from volume 1 on,
+        without the spheres / triangles, ray.D as given."""
+        return bool(self.ctx.is_occluded_filtered(make_rays([ray.O], [ray.D], ray.t), 1, shapes=False,
+                                                  raw_direction=True)[0])
 
     def history_host(self):
         self.synchronize()
