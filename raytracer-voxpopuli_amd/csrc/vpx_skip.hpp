@@ -671,14 +671,43 @@ struct Axis {
 // segment (axis_seg1, sets fit1 = the events it reaches), the second (axis_seg2, returns
 // the events both reach; skipped when no lane of the wave wants more than fit1 on any
 // axis — its parameters are then never read: every index used is <= m1), the clip.
+//
+// PRE (the plain-step prefix): an axis whose first segment has no closed form only because its
+// head is immature is not refused.  Immature: h and d normal, exponent(d) >= exponent(h), which
+// is every axis of a walk that starts at t = 0 (tmax <= tdelta).  Such an axis is "no events in
+// segment one (fit1 = 0), the plain IEEE step A(1) = fl(h + d), then segment two from A(1)": the
+// form the code below already takes when a first segment ends at its head (fit1 == 0: am =
+// fbits(h)).  It is exact because d >= 2^exponent(d) >= 2^exponent(h) and h >= 2^exponent(h), so
+// h + d >= 2^(exponent(h) + 1) and, rounding being monotone, so is A(1): every A(i), i >= 1, lies
+// above h's binade.  axis_count reads the first segment only for a T in or below that binade
+// (s2 false), caps what it finds at m1 + 1 = 1 and raises it to 1 when h is below T: 1 or 0 from
+// h alone, which is the count, since no later term is below such a T.  A T in a higher binade
+// goes to the second segment as for any axis.
+// With PRE the plain step's value also counts as reached whenever it is held exactly (exact2: b2
+// is A(fit1 + 1)'s own significand, e2 its exponent, so axis_at(fit1 + 1) returns it bit for bit),
+// whether or not a closed form follows (ok2): reach = fit1 + 1 + (ok2 ? fit2 : 0).  Without ok2
+// the box is clipped at that index, so no index past it is formed, and a count that goes to the
+// second segment is capped at l <= fit1 + 1, so it counts indices up to fit1 only: h and the first
+// segment's terms, all below a T of a higher binade.  (axis_rebase then sees fit2 = 0 and takes its
+// own plain step from that value; a head it rebases onto is immature or stuck, see above.)  A tie at the plain step (exact2 false) clips at fit1 as before: 0 for an
+// admitted axis.  A refused segment's c is forced to 1 so that every divisor stays defined: its
+// quotients are formed (axis_count, seg_first_cap) and then capped by m1 + 1 or l.
+VPX_HD bool seg_immature(float h, float d) {
+    const uint32_t ea = fbits(h) >> 23, ed = fbits(d) >> 23;  // (a sign bit fails the range test)
+    return (ea - 1u < 254u) & (ed - 1u < 254u) & (ed >= ea);
+}
+template <bool PRE = false>
 VPX_HD bool axis_seg1(float h, float d, Axis& a, uint32_t& fit1) {
     const bool ok1 = seg_params_nb(h, d, a.b1, a.c1, a.e1);
+    if (PRE) a.c1 = ok1 ? a.c1 : 1u;
     // A(i), 1 <= i <= fit1, stay below 2^24 u (a tie base may be 2^24 itself: fit1 = 0)
     const uint32_t room = a.b1 <= 0xffffffu ? 0xffffffu - a.b1 : 0u;
     fit1 = floor_div_cap(room, a.c1 ? a.c1 : 1u);  // (c1 == 0: not ok1)
+    if (PRE) fit1 = ok1 ? fit1 : 0u;
     a.b2 = 0u, a.c2 = 1u, a.e2 = 0u;
-    return ok1;
+    return PRE ? ok1 | seg_immature(h, d) : ok1;
 }
+template <bool PRE = false>
 VPX_HD uint32_t axis_seg2(float h, float d, Axis& a, uint32_t fit1) {
     const uint32_t amc = (a.e1 << 23) | (mad24(fit1, a.c1, a.b1) & 0x7fffffu);
     const uint32_t am = fit1 ? amc : fbits(h);
@@ -687,8 +716,10 @@ VPX_HD uint32_t axis_seg2(float h, float d, Axis& a, uint32_t fit1) {
     const bool ok2 = seg_params_nb(A, d, b2, a.c2, a.e2);
     const bool exact2 = b2 == ((fbits(A) & 0x7fffffu) | 0x800000u);  // closed form from j = 0
     a.b2 = b2;
+    if (PRE) a.c2 = ok2 ? a.c2 : 1u;
     const uint32_t room2 = b2 <= 0xffffffu ? 0xffffffu - b2 : 0u;
     const uint32_t fit2 = floor_div_cap(room2, a.c2 ? a.c2 : 1u);
+    if (PRE) return exact2 ? fit1 + 1u + (ok2 ? fit2 : 0u) : fit1;
     return (ok2 & exact2) ? fit1 + 1u + fit2 : fit1;
 }
 VPX_HD void axis_clip(Axis& a, uint32_t l, bool ok1, uint32_t reach, uint32_t fit1) {
@@ -735,11 +766,14 @@ VPX_HD bool any_lane(bool b) {
 #endif
 }
 
+template <bool PRE = false>
 VPX_HD void axis_setup(float h, float d, uint32_t l, Axis& a) {
     const bool ok1 = seg_params_nb(h, d, a.b1, a.c1, a.e1);
+    if (PRE) a.c1 = ok1 ? a.c1 : 1u;
     // A(i), 1 <= i <= fit1, stay below 2^24 u (a tie base may be 2^24 itself: fit1 = 0)
     const uint32_t room = a.b1 <= 0xffffffu ? 0xffffffu - a.b1 : 0u;
-    const uint32_t fit1 = floor_div_cap(room, a.c1 ? a.c1 : 1u);  // (c1 == 0: not ok1)
+    const uint32_t fit1q = floor_div_cap(room, a.c1 ? a.c1 : 1u);  // (c1 == 0: not ok1)
+    const uint32_t fit1 = PRE && !ok1 ? 0u : fit1q;
     const uint32_t amc = (a.e1 << 23) | (mad24(fit1, a.c1, a.b1) & 0x7fffffu);
     const uint32_t am = fit1 ? amc : fbits(h);
     const float A = bitsf(am) + d;  // the plain IEEE step into the next binade
@@ -747,9 +781,11 @@ VPX_HD void axis_setup(float h, float d, uint32_t l, Axis& a) {
     const bool ok2 = seg_params_nb(A, d, b2, a.c2, a.e2);
     const bool exact2 = b2 == ((fbits(A) & 0x7fffffu) | 0x800000u);  // closed form from j = 0
     a.b2 = b2;
+    if (PRE) a.c2 = ok2 ? a.c2 : 1u;
     const uint32_t room2 = b2 <= 0xffffffu ? 0xffffffu - b2 : 0u;
     const uint32_t fit2 = floor_div_cap(room2, a.c2 ? a.c2 : 1u);
-    const uint32_t lim = ok1 ? ((ok2 & exact2) ? fit1 + 1u + fit2 : fit1) : 0u;
+    const uint32_t reach = PRE ? (exact2 ? fit1 + 1u + (ok2 ? fit2 : 0u) : fit1) : ((ok2 & exact2) ? fit1 + 1u + fit2 : fit1);
+    const uint32_t lim = (PRE ? ok1 | seg_immature(h, d) : ok1) ? reach : 0u;
     a.l = l < lim ? l : lim;
     a.m1 = a.l < fit1 ? a.l : fit1;
 }
@@ -779,7 +815,9 @@ VPX_HD uint32_t axis_count(const Axis& a, float h, float T, bool strict, uint32_
 // clipped axes are rebased onto the next binade (axis_rebase), so the lane crosses up to 1 + MORE
 // binade boundaries per axis in one skip instead of landing inside the box and skipping the
 // rest after another load.
-template <bool SEG2_BRANCH = true, int MORE = 0>
+// PRE: the plain-step prefix (axis_seg1's comment): immature axes are admitted, and the plain
+// step's value is reached without a closed form after it.
+template <bool SEG2_BRANCH = true, int MORE = 0, bool PRE = false>
 VPX_HD int skip_box_lean(Walk& w, uint32_t lo[3], uint32_t hi[3], float bound, uint32_t& cells) {
     static_assert(MORE == 0 || SEG2_BRANCH, "skip_box_lean: further segments build on the branch form");
     if (!((w.tx > 0.0f) & (w.ty > 0.0f) & (w.tz > 0.0f))) return 2;
@@ -788,21 +826,21 @@ VPX_HD int skip_box_lean(Walk& w, uint32_t lo[3], uint32_t hi[3], float bound, u
     const uint32_t wx = w.sx > 0 ? hi[0] - w.X : w.X - lo[0], wy = w.sy > 0 ? hi[1] - w.Y : w.Y - lo[1],
                    wz = w.sz > 0 ? hi[2] - w.Z : w.Z - lo[2];
     uint32_t fx, fy, fz;
-    const bool okx = axis_seg1(w.tx, w.dx, ax, fx), oky = axis_seg1(w.ty, w.dy, ay, fy),
-               okz = axis_seg1(w.tz, w.dz, az, fz);
+    const bool okx = axis_seg1<PRE>(w.tx, w.dx, ax, fx), oky = axis_seg1<PRE>(w.ty, w.dy, ay, fy),
+               okz = axis_seg1<PRE>(w.tz, w.dz, az, fz);
     uint32_t rx = fx, ry = fy, rz = fz;
     if (any_lane((okx & (wx > fx)) | (oky & (wy > fy)) | (okz & (wz > fz)))) {  // a box crosses a binade
-        rx = axis_seg2(w.tx, w.dx, ax, fx);
-        ry = axis_seg2(w.ty, w.dy, ay, fy);
-        rz = axis_seg2(w.tz, w.dz, az, fz);
+        rx = axis_seg2<PRE>(w.tx, w.dx, ax, fx);
+        ry = axis_seg2<PRE>(w.ty, w.dy, ay, fy);
+        rz = axis_seg2<PRE>(w.tz, w.dz, az, fz);
     }
     axis_clip(ax, wx, okx, rx, fx);
     axis_clip(ay, wy, oky, ry, fy);
     axis_clip(az, wz, okz, rz, fz);
     } else {
-    axis_setup(w.tx, w.dx, w.sx > 0 ? hi[0] - w.X : w.X - lo[0], ax);
-    axis_setup(w.ty, w.dy, w.sy > 0 ? hi[1] - w.Y : w.Y - lo[1], ay);
-    axis_setup(w.tz, w.dz, w.sz > 0 ? hi[2] - w.Z : w.Z - lo[2], az);
+    axis_setup<PRE>(w.tx, w.dx, w.sx > 0 ? hi[0] - w.X : w.X - lo[0], ax);
+    axis_setup<PRE>(w.ty, w.dy, w.sy > 0 ? hi[1] - w.Y : w.Y - lo[1], ay);
+    axis_setup<PRE>(w.tz, w.dz, w.sz > 0 ? hi[2] - w.Z : w.Z - lo[2], az);
     }
     // The events a rebase passes are taken at once (cell, head and visit count move to A(off)),
     // so nothing but the axes themselves is kept for the rest; w.t follows at the landing, where
@@ -892,7 +930,17 @@ VPX_HD bool gate_open(const Walk& w, uint32_t gate) {
 // With the axis planes (g.dfa / g.dfw) the boxes are theirs, along the ray's dominant axis, and
 // with g.dfw widened along its second.  `gate` (gate_word, 0: none): a class-2 brick is stepped
 // through while the maturity gate is shut, as the walkers do for the kinds that have the bit;
-// bits 5-7 of it: the further segments its skips may take (skip_box_lean's MORE, up to 4).
+// bits 5-7 of it: the further segments its skips may take (skip_box_lean's MORE, up to 4); bit 8
+// (kGatePre): its skips take the plain-step prefix (skip_box_lean's PRE).
+constexpr uint32_t kGatePre = 1u << 8;
+template <bool PRE>
+VPX_HD int skip_box_lean_more(Walk& w, uint32_t lo[3], uint32_t hi[3], float bound, uint32_t& cells, uint32_t more) {
+    return more == 0u   ? skip_box_lean<true, 0, PRE>(w, lo, hi, bound, cells)
+           : more == 1u ? skip_box_lean<true, 1, PRE>(w, lo, hi, bound, cells)
+           : more == 2u ? skip_box_lean<true, 2, PRE>(w, lo, hi, bound, cells)
+           : more == 3u ? skip_box_lean<true, 3, PRE>(w, lo, hi, bound, cells)
+                        : skip_box_lean<true, 4, PRE>(w, lo, hi, bound, cells);
+}
 VPX_HD bool walk_skip(const GridView& g, Walk& w, float bound, uint32_t& cells, uint32_t gate = 0u) {
     const bool wide = g.dfw != nullptr, axes = wide || g.dfa != nullptr;
     const uint32_t axis = dom_axis(w), sec = wide ? sec_axis(w) : 3u;
@@ -908,12 +956,8 @@ VPX_HD bool walk_skip(const GridView& g, Walk& w, float bound, uint32_t& cells, 
             uint32_t lo[3], hi[3];
             if (axes) df_box_axis(w, g.n, cube_dfp(w), len_dfa(w), axis, lo, hi, sec, wide ? wid_dfw(w, axis, sec) : 0u);
             else df_box(w, g.n, cube_l1(w), lo, hi);
-            const uint32_t more = (gate >> 5) & 7u;
-            const int sr = more == 0u   ? skip_box_lean(w, lo, hi, bound, cells)
-                           : more == 1u ? skip_box_lean<true, 1>(w, lo, hi, bound, cells)
-                           : more == 2u ? skip_box_lean<true, 2>(w, lo, hi, bound, cells)
-                           : more == 3u ? skip_box_lean<true, 3>(w, lo, hi, bound, cells)
-                                        : skip_box_lean<true, 4>(w, lo, hi, bound, cells);
+            const int sr = (gate & kGatePre) ? skip_box_lean_more<true>(w, lo, hi, bound, cells, (gate >> 5) & 7u)
+                                             : skip_box_lean_more<false>(w, lo, hi, bound, cells, (gate >> 5) & 7u);
             if (sr == 1) return false;
         }
         ++cells;  // visit the (empty) current cell

@@ -462,7 +462,7 @@ constexpr uint32_t kSkipwNearest = 1, kSkipwBounce = 2, kSkipwShadow = 4;
 #define VPX_MINC_SHADOW 1
 #endif
 constexpr uint32_t kMincNearest = VPX_MINC_NEAREST, kMincBounce = 2, kMincShadow = VPX_MINC_SHADOW;
-// Brick runs per walk kind, the RUN word: cap | passes << 8 | seg2 << 17 | min2 << 18 |
+// Brick runs per walk kind, the RUN word: cap | passes << 8 | pre << 16 | seg2 << 17 | min2 << 18 |
 // axis << 19 | minlen << 20 | wide << 24 | local << 25 | gate << 26 | G << 27 | N << 29 | seg3 << 31.
 // After its octant-plane byte (and, in an occupied brick, its cell mask) loads, a lane
 // steps up to `cap` cells inside its 4^3 brick on the register copy; `passes` brick loads
@@ -558,16 +558,57 @@ constexpr uint32_t kMincNearest = VPX_MINC_NEAREST, kMincBounce = 2, kMincShadow
 #else
 #define VPX_RUN_SEG3(on) ((on) << 31)
 #endif
+// pre (bit 16): the skip takes the plain-step prefix (skip::skip_box_lean's PRE, vpx_skip.hpp): an
+// axis whose tmax is at or below its tdelta (every axis of a walk that starts at t = 0) is not
+// clipped to zero events but to "the plain IEEE step, then the closed form from the value it lands
+// on", and the step's value is reached even where no closed form follows it.  Same Axis words,
+// nothing new live across the walk.  Measured per kind (ms per step, one box, interleaved runs of
+// the parent's library and each variant, DESIGN.md section 4, round 12, profiles/r12_prefix_ab.txt):
+// in the bounce walks (kRunBounce) Z1 1.560-1.572 against 1.604-1.612, C2 and C4 unchanged: on.  In
+// k_frame0's FindNearest (kRunFrameNearest) C1 0.4458-0.4524 in thirteen runs against 0.4524-0.4593
+// in eight: on, although the walk's iterations per wave are unchanged (the CPU model moves no
+// primary walk) and the counters show 16 % fewer vector memory reads at the same brick loads, that
+// is fewer scratch reloads: the gain is the register allocation around the changed skip.  In k_frame0's shadow walks on top of their
+// gate C1 0.4526-0.4622 against 0.4524-0.4593, without the gate 0.4612-0.4624 in two passes and
+// 0.4580-0.4653 in three (19 spilled VGPRs instead of 17): off.  In the other FindNearest kernels
+// (kRunNearest) C2 2.164-2.180 against 2.127-2.168, in the tile shadow walkers (kRunShadow) with or
+// without their gate and in the shadow pool nothing outside the parent's ranges on C2, C3, C4 and
+// Z1: off.  As shipped against the parent: C1 0.4399-0.4443 / 0.4489-0.4577, C2 2.143-2.170 /
+// 2.194-2.199, C3 3.296-3.310 / 3.324-3.335, Z1 1.571-1.599 / 1.601-1.627 (eight runs), C4
+// unchanged.  VPX_SKIP_PRE=1 sets the bit for every kind, 0 for none; VPX_PRE_<KIND> one kind's.
+#ifdef VPX_SKIP_PRE
+#define VPX_RUN_PRE(on) ((VPX_SKIP_PRE ? 1u : 0u) << 16)
+#else
+#define VPX_RUN_PRE(on) ((on) << 16)
+#endif
+#ifndef VPX_PRE_NEAREST
+#define VPX_PRE_NEAREST 0u
+#endif
+#ifndef VPX_PRE_BOUNCE
+#define VPX_PRE_BOUNCE 1u
+#endif
+#ifndef VPX_PRE_SHADOW
+#define VPX_PRE_SHADOW 0u
+#endif
+#ifndef VPX_PRE_FRAME_NEAREST
+#define VPX_PRE_FRAME_NEAREST 1u
+#endif
+#ifndef VPX_PRE_FRAME_SHADOW
+#define VPX_PRE_FRAME_SHADOW 0u
+#endif
+#ifndef VPX_PRE_SHADOW_POOL
+#define VPX_PRE_SHADOW_POOL 0u
+#endif
 #ifndef VPX_RUN_NEAREST
-#define VPX_RUN_NEAREST (3u | 3u << 8 | 1u << 17 | 1u << 18 | VPX_RUN_AXIS | VPX_RUN_LOCAL(1u) | VPX_RUN_GATE(0u) | VPX_RUN_SEG3(0u))
+#define VPX_RUN_NEAREST (3u | 3u << 8 | 1u << 17 | 1u << 18 | VPX_RUN_AXIS | VPX_RUN_LOCAL(1u) | VPX_RUN_GATE(0u) | VPX_RUN_SEG3(0u) | VPX_RUN_PRE(VPX_PRE_NEAREST))
 #endif
 constexpr uint32_t kRunNearest = VPX_RUN_NEAREST;
 #ifndef VPX_RUN_BOUNCE
-#define VPX_RUN_BOUNCE (4u | 1u << 8 | 0u << 17 | 1u << 18 | VPX_RUN_AXIS | VPX_RUN_LOCAL(0u) | VPX_RUN_GATE(0u))
+#define VPX_RUN_BOUNCE (4u | 1u << 8 | 0u << 17 | 1u << 18 | VPX_RUN_AXIS | VPX_RUN_LOCAL(0u) | VPX_RUN_GATE(0u) | VPX_RUN_PRE(VPX_PRE_BOUNCE))
 #endif
 constexpr uint32_t kRunBounce = VPX_RUN_BOUNCE;
 #ifndef VPX_RUN_SHADOW
-#define VPX_RUN_SHADOW (3u | 1u << 8 | 1u << 17 | 0u << 18 | VPX_RUN_AXIS | VPX_RUN_LOCAL(1u) | VPX_RUN_GATE(1u) | VPX_RUN_SEG3(0u))
+#define VPX_RUN_SHADOW (3u | 1u << 8 | 1u << 17 | 0u << 18 | VPX_RUN_AXIS | VPX_RUN_LOCAL(1u) | VPX_RUN_GATE(1u) | VPX_RUN_SEG3(0u) | VPX_RUN_PRE(VPX_PRE_SHADOW))
 #endif
 constexpr uint32_t kRunShadow = VPX_RUN_SHADOW;
 // Round 5 (ms per step, three interleaved runs, tools/gpu_ab.sh): FindNearest runs of 3 cells in
@@ -579,7 +620,7 @@ constexpr uint32_t kRunShadow = VPX_RUN_SHADOW;
 // 0.5433-0.5444 vs 0.5456-0.5482 ms in three, then 0.5427-0.5457 vs 0.5447-0.5484 (two boxes,
 // three interleaved runs each); five passes 0.5464-0.5474, runs of 2 in four 0.5428-0.5472.
 #ifndef VPX_RUN_FRAME_NEAREST
-#define VPX_RUN_FRAME_NEAREST (3u | 4u << 8 | 1u << 17 | 1u << 18 | VPX_RUN_AXIS | VPX_RUN_LOCAL(1u) | VPX_RUN_GATE(0u) | VPX_RUN_SEG3(0u))
+#define VPX_RUN_FRAME_NEAREST (3u | 4u << 8 | 1u << 17 | 1u << 18 | VPX_RUN_AXIS | VPX_RUN_LOCAL(1u) | VPX_RUN_GATE(0u) | VPX_RUN_SEG3(0u) | VPX_RUN_PRE(VPX_PRE_FRAME_NEAREST))
 #endif
 constexpr uint32_t kRunFrameNearest = VPX_RUN_FRAME_NEAREST;
 // At 7 waves/SIMD the frame's shadow walks take the two-compare step too: C1 0.5418-0.5489 vs
@@ -587,7 +628,7 @@ constexpr uint32_t kRunFrameNearest = VPX_RUN_FRAME_NEAREST;
 // the gate a stepping lane needs several brick loads before its first skip, and three passes
 // win: C1 0.4514-0.4522 vs 0.4560-0.4626 ms in two (three interleaved runs each).
 #ifndef VPX_RUN_FRAME_SHADOW
-#define VPX_RUN_FRAME_SHADOW (3u | 3u << 8 | 1u << 17 | 1u << 18 | VPX_RUN_AXIS | VPX_RUN_LOCAL(1u) | VPX_RUN_GATE(1u) | VPX_RUN_SEG3(0u))
+#define VPX_RUN_FRAME_SHADOW (3u | 3u << 8 | 1u << 17 | 1u << 18 | VPX_RUN_AXIS | VPX_RUN_LOCAL(1u) | VPX_RUN_GATE(1u) | VPX_RUN_SEG3(0u) | VPX_RUN_PRE(VPX_PRE_FRAME_SHADOW))
 #endif
 constexpr uint32_t kRunFrameShadow = VPX_RUN_FRAME_SHADOW;
 // The pools' walks (k_nearest_pool, k_shadow_pool: 96 VGPRs at 5 waves/SIMD) have their own
@@ -598,7 +639,7 @@ constexpr uint32_t kRunFrameShadow = VPX_RUN_FRAME_SHADOW;
 // weight 1 / 4, runs of 3 cells in two passes measured C2 2.63-2.66 / 2.60-2.64 / 2.66-2.75 /
 // 2.65-2.71 vs 2.59-2.65 ms, and re-checked at three lanes in round 5 (within noise).
 #ifndef VPX_RUN_SHADOW_POOL
-#define VPX_RUN_SHADOW_POOL (3u | 1u << 8 | 1u << 17 | 1u << 18 | VPX_RUN_AXIS | VPX_RUN_LOCAL(1u) | VPX_RUN_GATE(0u) | VPX_RUN_SEG3(0u))
+#define VPX_RUN_SHADOW_POOL (3u | 1u << 8 | 1u << 17 | 1u << 18 | VPX_RUN_AXIS | VPX_RUN_LOCAL(1u) | VPX_RUN_GATE(0u) | VPX_RUN_SEG3(0u) | VPX_RUN_PRE(VPX_PRE_SHADOW_POOL))
 #endif
 #ifndef VPX_SKIPW_SHADOW_POOL
 #define VPX_SKIPW_SHADOW_POOL 4u
@@ -638,6 +679,7 @@ __device__ __forceinline__ bool walk_wave(const skip::GridView& g, skip::Walk& w
     enum : int { kStep = kWalkStep, kSkip = kWalkSkip, kMiss = kWalkMiss, kHit = kWalkHit };
     constexpr int kRun = (int)(RUN & 255u);
     constexpr int kPasses = (int)((RUN >> 8) & 255u);
+    constexpr bool kPre = (RUN >> 16) & 1u;  // the skip's plain-step prefix (skip::skip_box_lean's PRE)
     constexpr bool kSeg2Branch = (RUN >> 17) & 1u;
     constexpr bool kMin2 = (RUN >> 18) & 1u;  // step1's two-compare axis choice (vpx_skip.hpp)
     constexpr bool kAxis = (RUN >> 19) & 1u;  // boxes from the axis planes (skip::classify_axis_o)
@@ -731,7 +773,7 @@ __device__ __forceinline__ bool walk_wave(const skip::GridView& g, skip::Walk& w
             } else {
                 skip::df_box(w, g.n, skip::cube_dfp(w), lo, hi);
             }
-            const int sr = skip::skip_box_lean<kSeg2Branch, kMore>(w, lo, hi, bound, cells);  // 2 (refused): a plain step
+            const int sr = skip::skip_box_lean<kSeg2Branch, kMore, kPre>(w, lo, hi, bound, cells);  // 2 (refused): a plain step
             VPX_MARK("skip end");
             VPX_PH(fb += __popcll(__ballot(sr == 2));)
             if (sr == 1) {

@@ -83,14 +83,12 @@ extern "C" void set_gate(int G, int f) { g_gate = G > 0 ? gate_word((uint32_t)G,
 // Further lean segments (skip_box_lean's MORE, 0..4): the model of the walkers' seg3 bit.
 static int g_more = 0;
 extern "C" void set_more(int m) { g_more = m; }
+// The plain-step prefix (skip_box_lean's PRE): the model of the walkers' pre bit.
+static int g_pre = 0;
+extern "C" void set_pre(int on) { g_pre = on; }
 static int lean(Walk& t, uint32_t lo[3], uint32_t hi[3], float bound, uint32_t& cc) {
-    switch (g_more) {
-    case 1: return skip_box_lean<true, 1>(t, lo, hi, bound, cc);
-    case 2: return skip_box_lean<true, 2>(t, lo, hi, bound, cc);
-    case 3: return skip_box_lean<true, 3>(t, lo, hi, bound, cc);
-    case 4: return skip_box_lean<true, 4>(t, lo, hi, bound, cc);
-    default: return skip_box_lean(t, lo, hi, bound, cc);
-    }
+    const uint32_t more = (uint32_t)(g_more < 0 ? 0 : g_more > 4 ? 4 : g_more);
+    return g_pre ? skip_box_lean_more<true>(t, lo, hi, bound, cc, more) : skip_box_lean_more<false>(t, lo, hi, bound, cc, more);
 }
 static uint64_t g_gated;    // classifications the gate turned into steps
 static uint64_t g_adv[12];  // landing skips by the events they advanced: 0, 1, 2, 3-4, 5-8, ... 513+
@@ -190,7 +188,9 @@ extern "C" void walk_sim(const uint8_t* cells, const uint64_t* l1, const uint64_
                     const uint32_t c3[3] = {w.X, w.Y, w.Z};
                     int n2 = 0;
                     for (int k = 0; k < 3; ++k) {
-                        axis_setup(hh[k], dd[k], sg[k] > 0 ? hi[k] - c3[k] : c3[k] - lo[k], ax[k]);
+                        const uint32_t want = sg[k] > 0 ? hi[k] - c3[k] : c3[k] - lo[k];
+                        if (g_pre) axis_setup<true>(hh[k], dd[k], want, ax[k]);
+                        else axis_setup(hh[k], dd[k], want, ax[k]);
                         n2 += ax[k].l > ax[k].m1;
                     }
                     g_seg2[n2]++;

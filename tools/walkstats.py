@@ -1,7 +1,7 @@
 """Per-ray walk statistics of the skipping walker on a config's world (CPU model):
 python tools/walkstats.py [C1|C2|C3], MODES="0 -2 -102" (cubes, axis boxes of minimum length 2, then
 the same boxes widened along the second axis); GATE="1 0" adds the maturity gate (G 1, N 4 << 0),
-MORE=1 a third lean segment, FULL=1 whole boxes."""
+MORE=1 a third lean segment, PRE=1 the plain-step prefix, FULL=1 whole boxes."""
 import ctypes as C, os, subprocess, sys
 import numpy as np
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -105,6 +105,8 @@ lib.set_gate.argtypes = [C.c_int, C.c_int]
 lib.set_gate(*[int(x) for x in os.environ.get("GATE", "0 0").split()])
 lib.set_more.argtypes = [C.c_int]
 lib.set_more(int(os.environ.get("MORE", "0")))
+lib.set_pre.argtypes = [C.c_int]
+lib.set_pre(int(os.environ.get("PRE", "0")))  # 1: the plain-step prefix (skip_box_lean's PRE)
 for name, (a, b, bnd), mode in [(nm_, v, md) for nm_, v in sets.items() for md in modes]:
     lib.set_mode(max(mode, 0))
     lib.set_axis(max(-mode, 0) % 100)

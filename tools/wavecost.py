@@ -117,15 +117,23 @@ def adv():  # landing skips by the events they advanced (bins 0, 1, 2, 3-4, 5-8,
 # The box kinds, then (round 10) on the wide boxes the maturity gate for G in {1, 2, 3} and N in
 # {4, 8, 16}, the lean tier with 3 to 6 segments, both, and the whole-box tier that bounds what
 # any number of segments can reach (GATES="" skips these).
-rows = [("cubes", 0, 0, 0, 0, 0, 0), ("axis boxes", 2, 0, 0, 0, 0, 0), ("wide boxes", 2, 1, 0, 0, 0, 0)]
+# Round 12: the plain-step prefix (the walkers' pre bit) on the wide boxes, alone, under the gates
+# G1 N4, G1 N8 and G2 N4, and with a third segment.
+rows = [("cubes", 0, 0, 0, 0, 0, 0, 0), ("axis boxes", 2, 0, 0, 0, 0, 0, 0), ("wide boxes", 2, 1, 0, 0, 0, 0, 0)]
 if os.environ.get("GATES", "1"):
-    rows += [(f"gate G{G} N{4 << f}", 2, 1, G, f, 0, 0) for G in (1, 2, 3) for f in (0, 1, 2)]
-    rows += [(f"{2 + m} segments", 2, 1, 0, 0, 0, m) for m in (1, 2, 3, 4)]
-    rows += [(f"{2 + m} seg., G{G} N{4 << f}", 2, 1, G, f, 0, m) for m in (1, 2, 3) for G, f in ((1, 0), (1, 1), (2, 0))]
-    rows += [("whole boxes", 2, 1, 0, 0, 1, 0), ("whole, G1 N4", 2, 1, 1, 0, 1, 0)]
+    rows += [(f"gate G{G} N{4 << f}", 2, 1, G, f, 0, 0, 0) for G in (1, 2, 3) for f in (0, 1, 2)]
+    rows += [(f"{2 + m} segments", 2, 1, 0, 0, 0, m, 0) for m in (1, 2, 3, 4)]
+    rows += [(f"{2 + m} seg., G{G} N{4 << f}", 2, 1, G, f, 0, m, 0) for m in (1, 2, 3) for G, f in ((1, 0), (1, 1), (2, 0))]
+    rows += [("whole boxes", 2, 1, 0, 0, 1, 0, 0), ("whole, G1 N4", 2, 1, 1, 0, 1, 0, 0)]
+    rows += [("plain step", 2, 1, 0, 0, 0, 0, 1)]
+    rows += [(f"plain step, G{G} N{4 << f}", 2, 1, G, f, 0, 0, 1) for G, f in ((1, 0), (1, 1), (2, 0))]
+    rows += [("plain step, 3 seg.", 2, 1, 0, 0, 0, 1, 1)]
+if os.environ.get("ROWS"):  # a subset by name, separated by ';' (its first row sets the baseline)
+    rows = [r for r in rows if r[0] in os.environ["ROWS"].split(";")]
+lib.set_pre.argtypes = [C.c_int]
 first = None
-for name, axis, wide, G, f, full, more in rows:
-    lib.set_axis(axis); lib.set_wide(wide); lib.set_gate(G, f); lib.set_full(full); lib.set_more(more)
+for name, axis, wide, G, f, full, more, pre in rows:
+    lib.set_axis(axis); lib.set_wide(wide); lib.set_gate(G, f); lib.set_full(full); lib.set_more(more); lib.set_pre(pre)
     per, out, th = run(st, si, bnd)
     padv = adv()
     hit = ok & (th > 0)
