@@ -32,6 +32,13 @@
  *                                                     1438-1450; read :2112-2118, cleared :2206
  *   vpx_trace_probe       Trace's smoke-branch probe  renderer.cpp:1228-1240 (per ray)
  *   vpx_upload_grid       Scene::grid (owned by host) template/scene.h:258
+ *   vpx_model_upload      ogt_vox models[0]->voxel_data  template/scene.cpp:474 (kept on the device)
+ *   vpx_grid_load_model   Scene::LoadModel               template/scene.cpp:449-529
+ *                         Scene::LoadModelPartial        template/scene.cpp:531-604
+ *                           (ModifyingProp::Update, src/Game/ModifyingProp.cpp:11-21)
+ *                         Scene::LoadModelRandomMaterials template/scene.cpp:606-683
+ *                           (renderer.cpp:628, 2190)
+ *   vpx_grid_read_box     Scene::grid read back (debug)  template/scene.h:258
  *   vpx_set_volumes       Renderer::voxelVolumes      renderer.h:211
  *   vpx_set_materials     Renderer::materials         renderer.h:190, MaterialSetUp renderer.cpp:357-443
  *   vpx_set_lights        point/spot/area/dirLight    renderer.h:193-197
@@ -48,6 +55,9 @@
  *   vpx_bvh_random_tris      BasicBVH::BasicBVH()        src/BVH/BasicBVH.cpp:4-16
  *   vpx_bvh_depth            (recursion depth of IntersectBVH, src/BVH/BasicBVH.cpp:47-61)
  *   vpx_vox_decode           ogt_vox_read_scene ->models[0], ->palette, template/scene.cpp:474-475
+ *   vpx_model_place_host     the three loaders' placement loop  template/scene.cpp:449-683
+ *   vpx_xorshift32_jump      RandomUInt, k steps at once        template/tmpl8math.cpp:119-125
+ *   vpx_model_palette_materials  LoadModel's palette override   template/scene.cpp:516-520
  */
 #ifndef VPX_H_
 #define VPX_H_
@@ -276,6 +286,51 @@ int vpx_grid_write_box(vpx_ctx* ctx, uint32_t grid_id, const uint8_t* src, uint3
 /* Scene::CreateEmmisiveSphere(mat, radius) (template/scene.cpp:685-711) on the device:
    cells with length(worldsize/2 - (x,y,z)) < radius get `mat` (others unchanged). */
 int vpx_grid_emissive_sphere(vpx_ctx* ctx, uint32_t grid_id, uint8_t mat, float radius);
+/* Resident models: ogt_vox's models[0]->voxel_data as vpx_vox_decode returns it
+   (index x + y*sx + z*sx*sy, 0 = empty), each dimension 1..256.  voxels == NULL removes the
+   model.  A device set keeps a copy on every member. */
+int vpx_model_upload(vpx_ctx* ctx, uint32_t model_id, const uint8_t* voxels,
+                     uint32_t sx, uint32_t sy, uint32_t sz);
+
+#define VPX_LOAD_FULL    0u  /* Scene::LoadModel placement            scene.cpp:449-529 */
+#define VPX_LOAD_PARTIAL 1u  /* Scene::LoadModelPartial               scene.cpp:531-604 */
+#define VPX_LOAD_RANDOM  2u  /* Scene::LoadModelRandomMaterials       scene.cpp:606-683 */
+typedef struct vpx_model_load {      /* 40 bytes */
+    float    scale_model[3];         /* Scene::scaleModel on entry */
+    uint32_t mode;                   /* VPX_LOAD_* */
+    uint32_t columns, thickness;     /* PARTIAL: keep model x in [columns - thickness, columns + thickness],
+                                        uint32 arithmetic as written (the lower bound wraps) */
+    uint32_t seed;                   /* RANDOM: the caller's xorshift32 state (tmpl8math.cpp:16) */
+    float    rand_lo, rand_hi;       /* RANDOM: Rand(rand_lo, rand_hi); the reference passes 12, 13 */
+    uint32_t reserved;               /* 0 */
+} vpx_model_load;
+typedef struct vpx_model_result {    /* 16 bytes */
+    float    scale_model[3];         /* Scene::scaleModel as the call leaves it */
+    uint32_t seed;                   /* RANDOM: state after sx*sy*sz draws; else the seed given */
+} vpx_model_result;
+/* ResetGrid() to NONE, then the placement, on the device: no host grid, one level rebuild.
+   Creates the grid (or resizes it), like vpx_generate_tiled_grid: a fresh Scene(position, n)
+   needs no host upload.  The result is the grid the reference's loop leaves, bit for bit:
+     - when sx > n, scale_model is multiplied by (float)n / (float)size per axis — on every
+       call, as the reference does, so `out->scale_model` carries the multiplied value and a
+       host that mirrors Scene::scaleModel feeds it back;
+     - voxel (x, y, z) goes to the cell (trunc(x * s.x), trunc(z * s.y), trunc(y * s.z)), y and z
+       swapped; a NaN or an overflowing product truncates to INT_MIN as on x86;
+     - empty voxels and targets outside [0, n) are skipped (the reference's Set does not check);
+     - where several voxels land in one cell the last one of the loop (z outer, y, x inner) stays,
+       whatever order the device works in;
+     - RANDOM: voxel i = x + y*sx + z*sx*sy draws u_i, the state after i + 1 steps from `seed`
+       (empty voxels draw too, scene.cpp:661), and a non-empty one writes
+       (uint8_t)(rand_lo + (float)u_i * 2.3283064365387e-10f * (rand_hi - rand_lo)).
+   VPX_E_INVALID: in == NULL, reserved != 0, unknown mode, unknown model_id, n outside
+   vpx_upload_grid's range, RANDOM with a range not in 0 <= rand_lo <= rand_hi <= 255 (NaN
+   included).  Like every world edit the call waits for the frames in flight. */
+int vpx_grid_load_model(vpx_ctx* ctx, uint32_t grid_id, uint32_t n, uint32_t model_id,
+                        const vpx_model_load* in, vpx_model_result* out /* may be NULL */);
+/* Debug read-back of a box of cells, host bytes x fastest: the inverse of vpx_grid_write_box
+   (a device set reads its first member). */
+int vpx_grid_read_box(vpx_ctx* ctx, uint32_t grid_id, uint8_t* dst, uint32_t x0, uint32_t y0, uint32_t z0,
+                      uint32_t dx, uint32_t dy, uint32_t dz);
 /* FNV-1a-style 64-bit checksum of a device grid (for size-independent parity checks). */
 int vpx_grid_checksum(vpx_ctx* ctx, uint32_t grid_id, uint64_t* out);
 /* Debug read-back of a grid's 24 distance-field axis planes as the walkers read them
@@ -576,6 +631,17 @@ int vpx_bvh_build_host(const vpx_bvh_tri* tris, uint32_t n, vpx_bvh_node* nodes,
    built-in default palette is not carried). */
 int vpx_vox_decode(const uint8_t* data, uint64_t len, uint32_t size_out[3], uint8_t* voxels,
                    uint64_t voxels_cap, uint8_t palette_rgba[1024]);
+/* vpx_grid_load_model on the host (no device): cells = n^3 bytes.  The CPU path of the same
+   code (csrc/vpx_model.hpp); a model dimension outside 1..256 is VPX_E_INVALID too. */
+int vpx_model_place_host(const uint8_t* voxels, uint32_t sx, uint32_t sy, uint32_t sz, uint32_t n,
+                         const vpx_model_load* in, uint8_t* cells, vpx_model_result* out);
+/* The xorshift32 state (13, 17, 5: RandomUInt, tmpl8math.cpp:119-125) after `steps` steps,
+   by the jump: the step is linear over GF(2), so T^steps is a product of the T^(2^j). */
+uint32_t vpx_xorshift32_jump(uint32_t state, uint64_t steps);
+/* LoadModel's palette override (scene.cpp:516-520) on a 256-entry table: every index used
+   by a non-empty voxel gets albedo = rgb / 255.0f and roughness 1. */
+int vpx_model_palette_materials(vpx_material* mats256, const uint8_t* voxels, uint64_t count,
+                                const uint8_t palette_rgba[1024]);
 /* Depth of a tree built by vpx_bvh_build_host (a leaf root = 1; 0 when nodes_used == 0). */
 uint32_t vpx_bvh_depth(const vpx_bvh_node* nodes, uint32_t nodes_used);
 /* BasicBVH::BasicBVH() triangle set (BasicBVH.cpp:4-16): 64 triangles, vertex0 = r0*9-5,

@@ -111,6 +111,26 @@ QUERY_RAW_DIRECTION = 0x2  # VPX_QUERY_RAW_DIRECTION: direction used as given (t
 MAT_SMOKE_LOW_DENSITY, MAT_SMOKE_PLAYER = 9, 14  # VPX_MAT_SMOKE_*: the range FindNearestPlayer passes through
 
 
+LOAD_FULL, LOAD_PARTIAL, LOAD_RANDOM = 0, 1, 2  # VPX_LOAD_*: Scene::LoadModel / LoadModelPartial / LoadModelRandomMaterials
+
+
+class ModelLoad(C.Structure):  # vpx_model_load: one placement of a resident model (vpx_grid_load_model)
+    _fields_ = [("scale_model", f3), ("mode", C.c_uint32), ("columns", C.c_uint32), ("thickness", C.c_uint32),
+                ("seed", C.c_uint32), ("rand_lo", C.c_float), ("rand_hi", C.c_float), ("reserved", C.c_uint32)]
+
+
+class ModelResult(C.Structure):  # vpx_model_result: Scene::scaleModel and the xorshift32 state after the load
+    _fields_ = [("scale_model", f3), ("seed", C.c_uint32)]
+
+
+def model_load(mode=LOAD_FULL, scale_model=(1.0, 1.0, 1.0), columns=0, thickness=0, seed=0, rand_lo=12.0,
+               rand_hi=13.0):
+    """abi.ModelLoad; the defaults of the random range are the reference's
+    Rand(SMOKE_MID2_DENSITY, SMOKE_HIGH_DENSITY) (scene.cpp:661-662)."""
+    return ModelLoad(vec3(scale_model), int(mode), int(columns) & 0xFFFFFFFF, int(thickness) & 0xFFFFFFFF,
+                     int(seed) & 0xFFFFFFFF, float(rand_lo), float(rand_hi), 0)
+
+
 class PrevCamera(C.Structure):
     _fields_ = [("cam_pos", f3), ("left_normal", f3), ("right_normal", f3), ("top_normal", f3),
                 ("bottom_normal", f3), ("pad", C.c_float)]
@@ -137,7 +157,7 @@ STAGES = ("primary", "shade", "shadow", "resolve", "bounce", "finish", "frame", 
 
 STRUCT_SIZES = {PrevCamera: 64, Profile: 160, Volume: 160, Material: 32, PointLight: 24, SpotLight: 40, AreaLight: 32, DirLight: 24,
                 Sphere: 32, Triangle: 64, Camera: 80, FrameParams: 48, Ray: 32, Hit: 32, Stats: 40,
-                BvhTri: 36, BvhNode: 32, PlayerLight: 24, RayProbe: 16, RayFilter: 16}
+                BvhTri: 36, BvhNode: 32, PlayerLight: 24, RayProbe: 16, RayFilter: 16, ModelLoad: 40, ModelResult: 16}
 
 
 def np_dtype(struct):
@@ -230,6 +250,14 @@ SIGNATURES = {
     "vpx_x86_arith_verify": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64),
                                        C.POINTER(C.c_uint32)]),
     "vpx_vox_decode": (C.c_int, [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint32), C.c_void_p, C.c_uint64, C.c_void_p]),
+    "vpx_model_upload": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p] + [C.c_uint32] * 3),
+    "vpx_grid_load_model": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(ModelLoad),
+                                      C.POINTER(ModelResult)]),
+    "vpx_model_place_host": (C.c_int, [C.c_void_p] + [C.c_uint32] * 4 + [C.POINTER(ModelLoad), C.c_void_p,
+                                                                         C.POINTER(ModelResult)]),
+    "vpx_grid_read_box": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p] + [C.c_uint32] * 6),
+    "vpx_xorshift32_jump": (C.c_uint32, [C.c_uint32, C.c_uint64]),
+    "vpx_model_palette_materials": (C.c_int, [C.POINTER(Material), C.c_void_p, C.c_uint64, C.c_void_p]),
 }
 
 _LIB = None

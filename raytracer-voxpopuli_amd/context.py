@@ -97,6 +97,10 @@ class Context:
         self._chk(self.lib.vpx_set_sky(self.h, a.ctypes.data_as(C.c_void_p), w, h, float(hdr_contribution)),
                   "vpx_set_sky")
 
+    def set_materials(self, materials):
+        """Renderer::materials: a ctypes array of 256 abi.Material (vpx_set_materials)."""
+        self._chk(self.lib.vpx_set_materials(self.h, materials, 256), "vpx_set_materials")
+
     def set_camera(self, cam):
         self._chk(self.lib.vpx_set_camera(self.h, C.byref(cam)), "vpx_set_camera")
 
@@ -117,6 +121,40 @@ class Context:
         """Scene::CreateEmmisiveSphere(mat, radius) (template/scene.cpp:685-711)."""
         self._chk(self.lib.vpx_grid_emissive_sphere(self.h, grid_id, int(mat), float(radius)),
                   "vpx_grid_emissive_sphere")
+
+    def model_upload(self, model_id, size, voxels):
+        """A resident model (vpx_model_upload): ogt_vox's voxel_data as scene.load_model returns
+        it, size = (sx, sy, sz); voxels None removes it."""
+        if voxels is None:
+            self._chk(self.lib.vpx_model_upload(self.h, model_id, None, 0, 0, 0), "vpx_model_upload")
+            return
+        v = np.ascontiguousarray(voxels, np.uint8).reshape(-1)
+        sx, sy, sz = (int(s) for s in size)
+        assert v.size == sx * sy * sz, "voxels do not match the model size"
+        self._chk(self.lib.vpx_model_upload(self.h, model_id, v.ctypes.data_as(C.c_void_p), sx, sy, sz),
+                  "vpx_model_upload")
+
+    def grid_load_model(self, grid_id, n, model_id, mode=abi.LOAD_FULL, scale_model=(1.0, 1.0, 1.0), columns=0,
+                        thickness=0, seed=0, rand_lo=12.0, rand_hi=13.0, load=None):
+        """Scene::LoadModel / LoadModelPartial / LoadModelRandomMaterials of a resident model into
+        grid grid_id (n^3, created or resized as needed) on the device (vpx_grid_load_model).
+        load: an abi.ModelLoad instead of the keywords.  Returns the abi.ModelResult:
+        Scene::scaleModel as the call leaves it and the xorshift32 state after the draws."""
+        ld = load if load is not None else abi.model_load(mode, scale_model, columns, thickness, seed, rand_lo, rand_hi)
+        res = abi.ModelResult()
+        self._chk(self.lib.vpx_grid_load_model(self.h, grid_id, int(n), model_id, C.byref(ld), C.byref(res)),
+                  "vpx_grid_load_model")
+        return res
+
+    def grid_read_box(self, grid_id, origin, shape):
+        """Debug read-back (vpx_grid_read_box): the cells of the box at origin (x0, y0, z0) as a
+        uint8 array of shape (dz, dy, dx), the inverse of grid_write_box."""
+        dz, dy, dx = (int(s) for s in shape)
+        x0, y0, z0 = (int(s) for s in origin)
+        out = np.empty((dz, dy, dx), np.uint8)
+        self._chk(self.lib.vpx_grid_read_box(self.h, grid_id, out.ctypes.data_as(C.c_void_p), x0, y0, z0, dx, dy, dz),
+                  "vpx_grid_read_box")
+        return out
 
     def grid_checksum(self, grid_id=0):
         out = C.c_uint64()

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../include/vpx.h"
+#include "vpx_model.hpp"
 
 namespace {
 
@@ -253,6 +254,7 @@ static_assert(sizeof(vpx_profile) == 160, "vpx_profile layout");
 static_assert(sizeof(vpx_prev_camera) == 64, "vpx_prev_camera layout");
 static_assert(sizeof(vpx_player_light) == 24 && sizeof(vpx_ray_probe) == 16, "player light layout");
 static_assert(sizeof(vpx_ray_filter) == 16, "ray filter layout");
+static_assert(sizeof(vpx_model_load) == 40 && sizeof(vpx_model_result) == 16, "model load layout");
 static_assert(sizeof(vpx_area_light) == 32 && sizeof(vpx_dir_light) == 24, "light layout");
 static_assert(sizeof(vpx_sphere) == 32 && sizeof(vpx_triangle) == 64, "shape layout");
 static_assert(sizeof(vpx_camera) == 80 && sizeof(vpx_frame_params) == 48, "camera/frame layout");
@@ -492,6 +494,63 @@ int vpx_vox_decode(const uint8_t* data, uint64_t len, uint32_t size_out[3], uint
         for (int i = 1; i < 256; ++i) std::memcpy(palette_rgba + 4 * i, disp + 4 * (i - 1), 4);
         std::memcpy(palette_rgba, disp + 4 * 255, 4);
         palette_rgba[3] = 0;
+    }
+    return VPX_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------ model loaders
+// Scene::LoadModel / LoadModelPartial / LoadModelRandomMaterials (template/scene.cpp:449-683)
+// on the host, through the code the device runs (vpx_model.hpp).
+namespace {
+const uint32_t* jump_tables() {  // T^(2^j), j < 64
+    static const std::vector<uint32_t> t = [] {
+        std::vector<uint32_t> v(32 * vpx::model::kJumpHost);
+        vpx::model::xs32_build_tables(v.data(), vpx::model::kJumpHost);
+        return v;
+    }();
+    return t.data();
+}
+}  // namespace
+
+extern "C" {
+
+uint32_t vpx_xorshift32_jump(uint32_t state, uint64_t steps) {
+    return vpx::model::xs32_jump(jump_tables(), state, steps);
+}
+
+int vpx_model_place_host(const uint8_t* voxels, uint32_t sx, uint32_t sy, uint32_t sz, uint32_t n,
+                         const vpx_model_load* in, uint8_t* cells, vpx_model_result* out) {
+    namespace m = vpx::model;
+    if (!voxels || !cells || m::check_load(in, sx, sy, sz, n)) return VPX_E_INVALID;
+    const uint64_t count = (uint64_t)sx * sy * sz;
+    std::vector<uint16_t> plan(m::plan_bytes(n) / 2);
+    uint8_t* pb = reinterpret_cast<uint8_t*>(plan.data());
+    vpx_model_result res{};
+    m::plan_load(pb, in, sx, sy, sz, n, res.scale_model);
+    res.seed = in->seed;
+    std::vector<uint8_t> mat;
+    if (in->mode == VPX_LOAD_RANDOM) {
+        mat.resize((count + m::kChunk - 1) / m::kChunk * m::kChunk);
+        for (uint64_t first = 0; first < count; first += m::kChunk)
+            m::random_chunk(jump_tables(), in->seed, first, in->rand_lo, in->rand_hi, mat.data());
+        res.seed = vpx_xorshift32_jump(in->seed, count);
+    }
+    m::place_grid(m::plan_view(pb, n), voxels, mat.empty() ? voxels : mat.data(), sx, sy, cells);
+    if (out) *out = res;
+    return VPX_OK;
+}
+
+int vpx_model_palette_materials(vpx_material* mats, const uint8_t* voxels, uint64_t count,
+                                const uint8_t palette_rgba[1024]) {
+    if (!mats || !voxels || !palette_rgba) return VPX_E_INVALID;
+    bool used[256] = {false};
+    for (uint64_t i = 0; i < count; ++i) used[voxels[i]] = true;
+    for (int i = 1; i < 256; ++i) {
+        if (!used[i]) continue;
+        for (int k = 0; k < 3; ++k) mats[i].albedo[k] = (float)palette_rgba[4 * i + k] / 255.0f;
+        mats[i].roughness = 1.0f;
     }
     return VPX_OK;
 }

@@ -8,6 +8,7 @@
 //   composite_rgb8                rank-0 unpack of gathered RGB8 tiles (sharded accumulator).
 //   find_nearest_k / is_occluded_k / trace_k   per-ray unit entries.
 //   tiled_world_k / checksum_k    world generator and grid checksum.
+//   model_gather_k / model_random_k   the model loaders' placement (vpx_model.hpp).
 #include <hip/hip_runtime.h>
 #include <hip/hip_gl_interop.h>
 #include <rccl/rccl.h>
@@ -23,6 +24,7 @@
 #include <vector>
 
 #include "vpx_wavefront.hpp"
+#include "vpx_model.hpp"
 
 using namespace vpx;
 
@@ -337,6 +339,62 @@ __global__ void tiled_world_k(uint8_t* __restrict__ out, uint32_t n, const uint8
     }
 }
 
+// Scene::LoadModel / LoadModelPartial / LoadModelRandomMaterials (template/scene.cpp:449-683):
+// every cell of the grid gathers its last writer through the plan's preimage tables
+// (vpx_model.hpp), cells no voxel reaches get NONE — the ResetGrid() is part of the pass.
+// One thread per 16 consecutive x-cells of a row (n % 16 == 0) or per cell otherwise.
+__global__ __launch_bounds__(256) void model_gather_k(uint8_t* __restrict__ out, uint32_t n,
+                                                      const uint8_t* __restrict__ plan, const uint8_t* __restrict__ vox,
+                                                      const uint8_t* __restrict__ mat, uint32_t sx, uint32_t sy) {
+    const model::PlanView pv{plan, reinterpret_cast<const uint16_t*>(plan + model::kSrcBytes), n};
+    const uint64_t n64 = n;
+    const bool wide = (n % 16u) == 0;
+    const uint64_t per_row = wide ? n64 / 16 : n64;
+    const uint64_t total = per_row * n64 * n64;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
+         i += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t row = i / per_row;
+        const uint32_t x0 = (uint32_t)(i % per_row) * (wide ? 16u : 1u);
+        const uint32_t y = (uint32_t)(row % n64), z = (uint32_t)(row / n64);
+        uint8_t* dst = out + z * n64 * n64 + y * n64 + x0;
+        if (wide) {
+            uint8_t vals[16];
+            model::place_span<16>(pv, vox, mat, sx, sy, x0, y, z, vals);
+            uint32_t w[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+                w[q] = (uint32_t)vals[4 * q] | (uint32_t)vals[4 * q + 1] << 8 | (uint32_t)vals[4 * q + 2] << 16 |
+                       (uint32_t)vals[4 * q + 3] << 24;
+            *reinterpret_cast<uint4*>(dst) = make_uint4(w[0], w[1], w[2], w[3]);
+        } else {
+            uint8_t v;
+            model::place_span<1>(pv, vox, mat, sx, sy, x0, y, z, &v);
+            dst[0] = v;
+        }
+    }
+}
+
+// LoadModelRandomMaterials' draws (scene.cpp:661): the material of every voxel, empty ones
+// included, into `mat` (whole chunks of model::kChunk voxels); a thread jumps to its chunk's
+// first xorshift32 state and steps from there.
+__global__ __launch_bounds__(256) void model_random_k(const uint32_t* __restrict__ tables, uint32_t seed, uint64_t count,
+                                                      float lo, float hi, uint8_t* __restrict__ mat) {
+    const uint64_t chunks = (count + model::kChunk - 1) / model::kChunk;
+    for (uint64_t c = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; c < chunks; c += (uint64_t)gridDim.x * blockDim.x)
+        model::random_chunk(tables, seed, c * model::kChunk, lo, hi, mat);
+}
+
+// Gather a box of the grid into a staging buffer (x fastest): write_box_k's inverse.
+__global__ void read_box_k(const uint8_t* __restrict__ grid, uint32_t n, uint8_t* __restrict__ dst, uint32_t x0,
+                           uint32_t y0, uint32_t z0, uint32_t dx, uint32_t dy, uint32_t dz) {
+    const uint64_t total = (uint64_t)dx * dy * dz;
+    const uint64_t n64 = n;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t x = i % dx, y = (i / dx) % dy, z = i / ((uint64_t)dx * dy);
+        dst[i] = grid[(x0 + x) + (y0 + y) * n64 + (z0 + z) * n64 * n64];
+    }
+}
+
 // ------------------------------------------------------------- occupancy masks
 // Layout: vpx_skip.hpp blk_index (l1, l2 blocked by parent) / lin_index (l3).
 // l1: one thread per output word (padded space nb2^3 * 64) reads its brick's 64 cells.
@@ -572,6 +630,17 @@ struct vpx_ctx {
         uint64_t plane() const { return 64ull * nb2 * nb2 * nb2; }
     };
     std::vector<GridBuf> grids;
+    // resident .vox models (vpx_model_upload) and what a load needs, allocated with the first
+    // model so that vpx_grid_load_model allocates nothing: the xorshift32 jump tables followed
+    // by the load's plan (d_model_aux, the plan staged in the pinned h_plan)
+    struct ModelBuf {
+        uint8_t* vox = nullptr;  // voxel_data, sx*sy*sz bytes
+        uint8_t* mat = nullptr;  // random materials, whole chunks of model::kChunk
+        uint32_t sx = 0, sy = 0, sz = 0;
+    };
+    std::vector<ModelBuf> models;
+    uint8_t* d_model_aux = nullptr;
+    uint8_t* h_plan = nullptr;
     DevGrid* d_grids = nullptr;
     uint32_t d_grids_cap = 0;
     std::vector<vpx_volume> volumes;
@@ -1373,6 +1442,12 @@ int vpx_destroy(vpx_ctx* c) {
         if (g.l2) (void)hipFree(g.l2);
         if (g.dfp) (void)hipFree(g.dfp);
     }
+    for (auto& m : c->models) {
+        if (m.vox) (void)hipFree(m.vox);
+        if (m.mat) (void)hipFree(m.mat);
+    }
+    if (c->d_model_aux) (void)hipFree(c->d_model_aux);
+    if (c->h_plan) (void)hipHostFree(c->h_plan);
     void* ptrs[] = {c->d_grids, c->d_volumes, c->d_vbounds, c->d_tlas, c->d_bvh, c->d_materials, c->d_points, c->d_spots, c->d_areas,
                     c->d_spheres, c->d_triangles, c->d_ctr, c->d_sum, c->d_scratch, c->wave.d, c->d_sky, c->d_x86};
     for (void* p : ptrs)
@@ -1672,6 +1747,100 @@ int vpx_generate_tiled_grid(vpx_ctx* c, uint32_t id, uint32_t n, const uint8_t* 
     VPX_HIP(c, sync_all(c));
     (void)hipFree(dm);
     return build_masks(c, id);
+}
+
+constexpr size_t kJumpBytes = sizeof(uint32_t) * 32 * model::kJumpDevice;
+
+int vpx_model_upload(vpx_ctx* c, uint32_t id, const uint8_t* voxels, uint32_t sx, uint32_t sy, uint32_t sz) {
+    VPX_GROUP_ALL(c, vpx_model_upload(m_, id, voxels, sx, sy, sz));
+    if (!c) return VPX_E_INVALID;
+    if (id > 4096) return fail(c, VPX_E_INVALID, "model_id too large");
+    if (voxels && (!sx || !sy || !sz || sx > model::kMaxDim || sy > model::kMaxDim || sz > model::kMaxDim))
+        return fail(c, VPX_E_INVALID, "model dimension outside 1..256");
+    VPX_HIP(c, hipSetDevice(c->device));
+    VPX_HIP(c, sync_all(c));
+    if (id < c->models.size() && c->models[id].vox) {
+        (void)hipFree(c->models[id].vox);
+        (void)hipFree(c->models[id].mat);
+        c->models[id] = vpx_ctx::ModelBuf{};
+    }
+    if (!voxels) return VPX_OK;
+    if (!c->d_model_aux) {  // jump tables once; the plan of the largest grid (n = 4096) fits behind them
+        std::vector<uint32_t> t(32 * model::kJumpDevice);
+        model::xs32_build_tables(t.data(), model::kJumpDevice);
+        VPX_HIP(c, hipHostMalloc((void**)&c->h_plan, model::plan_bytes(4096)));
+        VPX_HIP(c, hipMalloc(&c->d_model_aux, kJumpBytes + model::plan_bytes(4096)));
+        VPX_HIP(c, hipMemcpy(c->d_model_aux, t.data(), kJumpBytes, hipMemcpyHostToDevice));
+    }
+    if (id >= c->models.size()) c->models.resize(id + 1);
+    auto& m = c->models[id];
+    const size_t count = (size_t)sx * sy * sz;
+    VPX_HIP(c, hipMalloc(&m.vox, count));
+    VPX_HIP(c, hipMalloc(&m.mat, (count + model::kChunk - 1) / model::kChunk * model::kChunk));
+    VPX_HIP(c, hipMemcpy(m.vox, voxels, count, hipMemcpyHostToDevice));
+    m.sx = sx, m.sy = sy, m.sz = sz;
+    return VPX_OK;
+}
+
+int vpx_grid_load_model(vpx_ctx* c, uint32_t id, uint32_t n, uint32_t model_id, const vpx_model_load* in,
+                        vpx_model_result* out) {
+    VPX_GROUP_ALL(c, vpx_grid_load_model(m_, id, n, model_id, in, out));
+    if (!c) return VPX_E_INVALID;
+    if (!in) return fail(c, VPX_E_INVALID, "null vpx_model_load");
+    if (model_id >= c->models.size() || !c->models[model_id].vox) return fail(c, VPX_E_INVALID, "unknown model");
+    const auto& m = c->models[model_id];
+    if (const char* why = model::check_load(in, m.sx, m.sy, m.sz, n)) return fail(c, VPX_E_INVALID, why);
+    if (id > 4096) return fail(c, VPX_E_INVALID, "grid_id too large");
+    VPX_HIP(c, hipSetDevice(c->device));
+    VPX_HIP(c, sync_all(c));  // frames in flight still read the grid
+    if (id >= c->grids.size() || !c->grids[id].ptr || c->grids[id].n != n)
+        if (int rc = alloc_grid(c, id, n)) return rc;
+    vpx_model_result res{};
+    model::plan_load(c->h_plan, in, m.sx, m.sy, m.sz, n, res.scale_model);
+    res.seed = in->seed;
+    uint8_t* d_plan = c->d_model_aux + kJumpBytes;
+    VPX_HIP(c, hipMemcpyAsync(d_plan, c->h_plan, model::plan_bytes(n), hipMemcpyHostToDevice, c->stream));
+    const uint64_t count = (uint64_t)m.sx * m.sy * m.sz;
+    const uint8_t* mat = m.vox;
+    if (in->mode == VPX_LOAD_RANDOM) {
+        const uint64_t chunks = (count + model::kChunk - 1) / model::kChunk;
+        hipLaunchKernelGGL(model_random_k, dim3((unsigned)std::min<uint64_t>(1024, (chunks + 255) / 256)), dim3(256), 0,
+                           c->stream, (const uint32_t*)c->d_model_aux, in->seed, count, in->rand_lo, in->rand_hi, m.mat);
+        VPX_HIP(c, hipGetLastError());
+        res.seed = vpx_xorshift32_jump(in->seed, count);
+        mat = m.mat;
+    }
+    const uint64_t threads = (uint64_t)n * n * ((n % 16u) ? n : n / 16);
+    hipLaunchKernelGGL(model_gather_k, dim3((unsigned)std::min<uint64_t>(4096, (threads + 255) / 256)), dim3(256), 0,
+                       c->stream, c->grids[id].ptr, n, (const uint8_t*)d_plan, (const uint8_t*)m.vox, mat, m.sx, m.sy);
+    VPX_HIP(c, hipGetLastError());
+    if (int rc = build_masks(c, id)) return rc;
+    if (out) *out = res;
+    return VPX_OK;
+}
+
+int vpx_grid_read_box(vpx_ctx* c, uint32_t id, uint8_t* dst, uint32_t x0, uint32_t y0, uint32_t z0, uint32_t dx,
+                      uint32_t dy, uint32_t dz) {
+    VPX_GROUP_FIRST(c, vpx_grid_read_box(m_, id, dst, x0, y0, z0, dx, dy, dz));
+    if (!c || !dst) return fail(c, VPX_E_INVALID, "null argument");
+    if (id >= c->grids.size() || !c->grids[id].ptr) return fail(c, VPX_E_INVALID, "unknown grid");
+    const auto& g = c->grids[id];
+    if ((uint64_t)x0 + dx > g.n || (uint64_t)y0 + dy > g.n || (uint64_t)z0 + dz > g.n)
+        return fail(c, VPX_E_INVALID, "box outside the grid");
+    const size_t bytes = (size_t)dx * dy * dz;
+    if (!bytes) return VPX_OK;
+    VPX_HIP(c, sync_all(c));
+    if (dx == g.n && dy == g.n) {  // whole slabs are contiguous
+        VPX_HIP(c, hipMemcpy(dst, g.ptr + (size_t)z0 * g.n * g.n, bytes, hipMemcpyDeviceToHost));
+        return VPX_OK;
+    }
+    if (int rc = ensure_scratch(c, bytes)) return rc;
+    hipLaunchKernelGGL(read_box_k, dim3((unsigned)std::min<size_t>(4096, (bytes + 255) / 256)), dim3(256), 0, c->stream,
+                       g.ptr, g.n, (uint8_t*)c->d_scratch, x0, y0, z0, dx, dy, dz);
+    VPX_HIP(c, hipGetLastError());
+    VPX_HIP(c, hipMemcpyAsync(dst, c->d_scratch, bytes, hipMemcpyDeviceToHost, c->stream));
+    VPX_HIP(c, sync_all(c));
+    return VPX_OK;
 }
 
 int vpx_grid_checksum(vpx_ctx* c, uint32_t id, uint64_t* out) {

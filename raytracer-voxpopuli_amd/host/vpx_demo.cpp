@@ -17,7 +17,9 @@
 //   it builds the zone scene's 21 volumes (scene.py zone_scene) and casts the player's four
 //   W / D / S / A rays (Renderer::FindNearestPlayer, renderer.cpp:2139-2152) from the player's
 //   centre, printing index, t, normal and material of each, and IsOccludedPlayerClimbable of
-//   the same ray, as one JSON line; '-' none.
+//   the same ray, as one JSON line; 'm' renders nothing either: it runs five ModifyingProp edits,
+//   a LoadModel and a LoadModelRandomMaterials of a synthetic model through the mirror
+//   (prop_edits below) and prints the grid checksum after each as one JSON line; '-' none.
 //   devices: comma-separated HIP devices, e.g. 0,1,2,3 — a device set (vpx_create_multi:
 //   tiles over the devices, RCCL gather to the first); default: device 0 alone.
 #include <chrono>
@@ -141,6 +143,45 @@ static int player_rays(vpxhost::Renderer& r) {
     return 0;
 }
 
+// Mode 'm': the model loaders through the C++ mirror, nothing rendered.  The demo carries no
+// model store, so the model is synthetic (tests rebuild it with numpy): 96 x 40 x 72 voxels,
+// voxel (x, y, z) = 1 + (x + 3y + 5z) % 200 where (7x + 13y + 5z) % 11 < 4, else empty.  It is
+// larger than the prop's 64^3 grid, so every load multiplies Scene::scaleModel once more, as the
+// reference does.  Five ModifyingProp edits (index 16, rate 16: 16, 32, 48, 64, 16), then a
+// LoadModel and a LoadModelRandomMaterials; the grid checksum after each as one JSON line.
+static int prop_edits(vpxhost::Renderer& r) {
+    const uint32_t sx = 96, sy = 40, sz = 72, n = 64;
+    std::vector<uint8_t> vox((size_t)sx * sy * sz);
+    for (uint32_t z = 0; z < sz; ++z)
+        for (uint32_t y = 0; y < sy; ++y)
+            for (uint32_t x = 0; x < sx; ++x)
+                vox[x + (size_t)y * sx + (size_t)z * sx * sy] =
+                    (7 * x + 13 * y + 5 * z) % 11 < 4 ? (uint8_t)(1 + (x + 3 * y + 5 * z) % 200) : (uint8_t)0;
+    CHECK(r.UploadModel(0, vox.data(), sx, sy, sz, nullptr));
+    r.CreateGrid(0, n);  // Scene(position, 64): filled by the first load, no host grid
+    vpx_volume vol{};
+    const float zero[3] = {0, 0, 0}, one[3] = {1, 1, 1};
+    CHECK(vpx_volume_set_transform(zero, one, zero, &vol));
+    CHECK(r.SetVolumes({vol}));
+    vpxhost::ModifyingProp prop{r, 0, 0, 16, 16};
+    std::printf("{\"prop_edits\": [");
+    for (int e = 0; e < 5; ++e) {
+        const uint32_t index = prop.index;
+        CHECK(prop.Update());
+        uint64_t sum = 0;
+        CHECK(vpx_grid_checksum(r.Context(), 0, &sum));
+        std::printf("%s{\"index\": %u, \"checksum\": \"%llu\"}", e ? ", " : "", index, (unsigned long long)sum);
+    }
+    uint64_t full = 0, random = 0;
+    CHECK(r.LoadModel(0, 0));
+    CHECK(vpx_grid_checksum(r.Context(), 0, &full));
+    CHECK(r.LoadModelRandomMaterials(0, 0));
+    CHECK(vpx_grid_checksum(r.Context(), 0, &random));
+    std::printf("], \"full\": \"%llu\", \"random\": \"%llu\", \"seed\": %u}\n", (unsigned long long)full,
+                (unsigned long long)random, r.seed);
+    return 0;
+}
+
 int main(int argc, char** argv) {
     const uint32_t n = argc > 1 ? (uint32_t)atoi(argv[1]) : 256;
     const uint32_t W = argc > 2 ? (uint32_t)atoi(argv[2]) : 640;
@@ -149,9 +190,9 @@ int main(int argc, char** argv) {
     const int bounces = argc > 5 ? atoi(argv[5]) : 0;
     const char* out = argc > 6 && argv[6][0] != '-' ? argv[6] : nullptr;
     const char* mode = argc > 7 ? argv[7] : "";
-    bool is_static = false, sky = false, player_light = false, player_cast = false;
+    bool is_static = false, sky = false, player_light = false, player_cast = false, prop_edit = false;
     for (const char* m = mode; *m; ++m)
-        is_static |= *m == 's', sky |= *m == 'k', player_light |= *m == 'p', player_cast |= *m == 'w';
+        is_static |= *m == 's', sky |= *m == 'k', player_light |= *m == 'p', player_cast |= *m == 'w', prop_edit |= *m == 'm';
     std::vector<int> devices;
     if (argc > 8)
         for (const char* d = argv[8]; *d;) {
@@ -163,6 +204,7 @@ int main(int argc, char** argv) {
     vpxhost::Renderer r = devices.empty() ? vpxhost::Renderer(0) : vpxhost::Renderer(devices);
     CHECK(r.Init(W, H));
     if (player_cast) return player_rays(r);
+    if (prop_edit) return prop_edits(r);
     std::vector<uint8_t> grid = pillars(n);
     if (player_light)  // the player: a block of smoke in the world, which is volume 0
         for (uint32_t z = n / 4; z < 3 * n / 8; ++z)

@@ -44,18 +44,93 @@ int Renderer::Init(uint32_t width, uint32_t height) {
 }
 
 int Renderer::UploadGrid(uint32_t grid_id, const uint8_t* cells, uint32_t n) {
-    return status_ ? status_ : vpx_upload_grid(ctx_, grid_id, cells, n);
+    if (status_) return status_;
+    const int rc = vpx_upload_grid(ctx_, grid_id, cells, n);
+    if (rc == VPX_OK) CreateGrid(grid_id, n);
+    return rc;
+}
+
+void Renderer::CreateGrid(uint32_t grid_id, uint32_t n) {
+    if (grid_id > 4096) return;  // the library refuses such ids
+    if (grid_id >= gridSize_.size()) gridSize_.resize(grid_id + 1, 0u);
+    gridSize_[grid_id] = n;
 }
 
 int Renderer::SetVolumes(const std::vector<vpx_volume>& v) {
     if (status_) return status_;
     const int rc = vpx_set_volumes(ctx_, v.data(), (uint32_t)v.size());
-    if (rc == VPX_OK) numVolumes_ = v.size();
+    if (rc == VPX_OK) numVolumes_ = v.size(), volumes_ = v;
     return rc;
 }
 
 int Renderer::SetMaterials(const std::vector<vpx_material>& m) {
-    return status_ ? status_ : vpx_set_materials(ctx_, m.data(), (uint32_t)m.size());
+    if (status_) return status_;
+    const int rc = vpx_set_materials(ctx_, m.data(), (uint32_t)m.size());
+    if (rc == VPX_OK) materials_ = m;
+    return rc;
+}
+
+int Renderer::UploadModel(uint32_t model_id, const uint8_t* voxels, uint32_t sx, uint32_t sy, uint32_t sz,
+                          const uint8_t* palette_rgba) {
+    if (status_) return status_;
+    const int rc = vpx_model_upload(ctx_, model_id, voxels, sx, sy, sz);
+    if (rc || !voxels) return rc;
+    if (model_id >= models_.size()) models_.resize(model_id + 1);
+    models_[model_id].voxels.assign(voxels, voxels + (size_t)sx * sy * sz);
+    models_[model_id].palette.clear();
+    if (palette_rgba) models_[model_id].palette.assign(palette_rgba, palette_rgba + 1024);
+    return VPX_OK;
+}
+
+const float* Renderer::ScaleModel(uint32_t volume) {
+    if (volume >= scaleModel_.size()) scaleModel_.resize(volume + 1, {1.0f, 1.0f, 1.0f});
+    return scaleModel_[volume].data();
+}
+
+// One loader call on the Scene of `volume`: its grid, its size and its scaleModel member, which
+// the loaders multiply when the model is larger than the grid (so the result is fed back).
+int Renderer::Load(uint32_t volume, uint32_t model_id, vpx_model_load in, vpx_model_result* out) {
+    if (status_) return status_;
+    if (volume >= volumes_.size()) return VPX_E_INVALID;
+    const uint32_t gid = volumes_[volume].grid_id;
+    if (gid >= gridSize_.size() || !gridSize_[gid]) return VPX_E_STATE;  // CreateGrid / UploadGrid first
+    const float* s = ScaleModel(volume);
+    for (int k = 0; k < 3; ++k) in.scale_model[k] = s[k];
+    vpx_model_result res{};
+    const int rc = vpx_grid_load_model(ctx_, gid, gridSize_[gid], model_id, &in, &res);
+    if (rc) return rc;
+    for (int k = 0; k < 3; ++k) scaleModel_[volume][k] = res.scale_model[k];
+    if (out) *out = res;
+    return VPX_OK;
+}
+
+int Renderer::LoadModel(uint32_t volume, uint32_t model_id) {
+    vpx_model_load in{};
+    in.mode = VPX_LOAD_FULL;
+    int rc = Load(volume, model_id, in, nullptr);
+    if (rc || model_id >= models_.size() || models_[model_id].palette.empty()) return rc;
+    if (materials_.size() < VPX_NUM_MATERIALS) return VPX_E_STATE;  // SetMaterials first
+    const Model& m = models_[model_id];
+    rc = vpx_model_palette_materials(materials_.data(), m.voxels.data(), m.voxels.size(), m.palette.data());
+    return rc ? rc : vpx_set_materials(ctx_, materials_.data(), (uint32_t)materials_.size());
+}
+
+int Renderer::LoadModelPartial(uint32_t volume, uint32_t model_id, uint32_t columns, uint32_t thickness) {
+    vpx_model_load in{};
+    in.mode = VPX_LOAD_PARTIAL;
+    in.columns = columns, in.thickness = thickness;
+    return Load(volume, model_id, in, nullptr);
+}
+
+int Renderer::LoadModelRandomMaterials(uint32_t volume, uint32_t model_id) {
+    vpx_model_load in{};
+    in.mode = VPX_LOAD_RANDOM;
+    in.seed = seed;
+    in.rand_lo = 12.0f, in.rand_hi = 13.0f;  // SMOKE_MID2_DENSITY, SMOKE_HIGH_DENSITY (scene.cpp:661-662)
+    vpx_model_result res{};
+    const int rc = Load(volume, model_id, in, &res);
+    if (rc == VPX_OK) seed = res.seed;
+    return rc;
 }
 
 int Renderer::SetLights(const std::vector<vpx_point_light>& p, const std::vector<vpx_spot_light>& s,

@@ -12,6 +12,7 @@
 // never throws; `LastError()` is the library's message.
 #pragma once
 
+#include <array>
 #include <cstdint>
 #include <string>
 #include <vector>
@@ -67,6 +68,23 @@ public:
     // primary rays) as this host computes it: VPX_ARITH_X86_HOST; VPX_ARITH_EXACT (default).
     int SetArithmetic(uint32_t mode);
 
+    // --- model loaders (template/scene.cpp:449-683) on the device: no host grid ------------
+    // A decoded .vox model (vpx_vox_decode) made resident; palette_rgba (1024 bytes, may be
+    // nullptr) stays on the host for LoadModel's material override.
+    int UploadModel(uint32_t model_id, const uint8_t* voxels, uint32_t sx, uint32_t sy, uint32_t sz,
+                    const uint8_t* palette_rgba);
+    // Scene(position, n) without a host grid: the grid a volume's loaders fill (UploadGrid
+    // records its size too).
+    void CreateGrid(uint32_t grid_id, uint32_t n);
+    // Scene::LoadModel (:449-529) into the volume's grid, then its palette override of
+    // Renderer::materials (:516-520) and the table re-sent.
+    int LoadModel(uint32_t volume, uint32_t model_id);
+    int LoadModelPartial(uint32_t volume, uint32_t model_id, uint32_t columns, uint32_t thickness);  // :531-604
+    // :606-683; draws Rand(SMOKE_MID2_DENSITY, SMOKE_HIGH_DENSITY) from, and advances, `seed`.
+    int LoadModelRandomMaterials(uint32_t volume, uint32_t model_id);
+    // Scene::scaleModel of a volume ((1, 1, 1) until a loader multiplies it).
+    const float* ScaleModel(uint32_t volume);
+
     // --- per frame -----------------------------------------------------------------------
     void ResetAccumulator() { numRenderedFrames = 0; }  // renderer.cpp:343-346
     int Update(vpx_stats* stats = nullptr);             // renderer.cpp:1646-1891
@@ -115,8 +133,16 @@ public:
     bool trackPlayerLight = false;
     vpx_player_light playerLight{};  // the last tracked Tick's record
     int32_t currentChunk = 0;        // read by FindNearestPlayer (renderer.cpp:1068)
+    uint32_t seed = 0x12345678u;     // the xorshift32 state of LoadModelRandomMaterials (tmpl8math.cpp:16)
 
 private:
+    int Load(uint32_t volume, uint32_t model_id, vpx_model_load in, vpx_model_result* out);
+    struct Model { std::vector<uint8_t> voxels, palette; };
+    std::vector<Model> models_;
+    std::vector<vpx_volume> volumes_;      // voxelVolumes as SetVolumes left them
+    std::vector<vpx_material> materials_;  // materials as SetMaterials / LoadModel left them
+    std::vector<uint32_t> gridSize_;       // grid id -> n (0: unknown)
+    std::vector<std::array<float, 3>> scaleModel_;
     size_t numVolumes_ = 0;  // voxelVolumes.size() as SetVolumes left it
     int UpdateStatic(vpx_stats* stats);
     int ReadPlayerLight(int rc);  // after a Tick's render (rc: its status)
@@ -133,6 +159,21 @@ private:
     float* accumulator_ = nullptr;  // float4[W*H] in HBM
     uint32_t* screen_ = nullptr;    // uint32[W*H] in HBM
     std::string err_;
+};
+
+// src/Game/ModifyingProp.{h,cpp}: every toChange seconds (0.9 in the game) the prop's Scene shows
+// the next slice of its model.  Update() is one due edit (the timer stays with the host): one
+// call into the library instead of a host loop, a ResetGrid and a box upload.
+struct ModifyingProp {
+    Renderer& renderer;
+    uint32_t volume, model_id;
+    uint32_t index, increaseRate;
+    int Update() {  // ModifyingProp.cpp:11-21
+        const int rc = renderer.LoadModelPartial(volume, model_id, index, increaseRate);
+        index += increaseRate;
+        if (index > 64) index = increaseRate;
+        return rc;
+    }
 };
 
 }  // namespace vpxhost

@@ -7,10 +7,27 @@ libvpx_hip.so (`vpx_render`) instead of the execution::par pixel loop
 0x00RRGGBB, template/surface.h) live in HBM as torch tensors; `screen_host()` copies the
 8-bit frame out for display.  The C++ twin of this class is host/vpx_renderer.{h,cpp}.
 """
+import numpy as np
 import torch
 
 from . import abi
 from .context import Context, make_rays
+
+
+class ModifyingProp:
+    """src/Game/ModifyingProp.{h,cpp}: every `toChange` seconds (0.9 in the game) the prop's
+    Scene shows the next slice of its model, LoadModelPartial(model, index, increaseRate).
+    Update() here is one due edit (the timer stays with the host): one call into the library."""
+
+    def __init__(self, renderer, volume, model_id, startingIndex, increasingRate):
+        self.renderer, self.volume, self.model_id = renderer, volume, model_id
+        self.index, self.increaseRate = int(startingIndex), int(increasingRate)
+
+    def Update(self):  # ModifyingProp.cpp:11-21
+        self.renderer.LoadModelPartial(self.volume, self.model_id, self.index, self.increaseRate)
+        self.index += self.increaseRate
+        if self.index > 64:
+            self.index = self.increaseRate
 
 
 def player_vox_index(vox, n_volumes, current_chunk):
@@ -58,6 +75,9 @@ class Renderer:
         self.trackPlayerLight = False
         self.last_player_light = None  # abi.PlayerLight of the last tracked Tick
         self.currentChunk = 0  # renderer.h: read by FindNearestPlayer (renderer.cpp:1068)
+        self.seed = 0x12345678  # the xorshift32 state LoadModelRandomMaterials draws from (tmpl8math.cpp:16)
+        self.scaleModel = {}    # volume index -> Scene::scaleModel, (1, 1, 1) until a loader multiplies it
+        self._models = {}       # model_id -> (voxels, palette) of the resident models (UploadModel)
 
     def Init(self):
         """Renderer::Init minus window/asset/game setup (renderer.cpp:688-736)."""
@@ -150,6 +170,44 @@ class Renderer:
         without the spheres / triangles, ray.D as given."""
         return bool(self.ctx.is_occluded_filtered(make_rays([ray.O], [ray.D], ray.t), 1, shapes=False,
                                                   raw_direction=True)[0])
+
+    # ------------------------------------------------------------ model loaders
+    def UploadModel(self, model_id, size, voxels, palette=None):
+        """Make a decoded .vox model (scene.load_model / decode_vox) resident on the device; the
+        loaders below then place it by id.  The palette stays on the host for LoadModel's
+        material override."""
+        self.ctx.model_upload(model_id, size, voxels)
+        self._models[model_id] = (np.ascontiguousarray(voxels, np.uint8).reshape(-1),
+                                  None if palette is None else np.ascontiguousarray(palette, np.uint8))
+
+    def _load(self, volume, model_id, **kw):
+        """One loader call on the Scene of `volume`: its grid, its size and its scaleModel member
+        (template/scene.h), which the loaders multiply when the model is larger than the grid."""
+        gid = self.scene.volumes[volume].grid_id
+        res = self.ctx.grid_load_model(gid, self.scene.grids[gid].n, model_id,
+                                       scale_model=self.scaleModel.get(volume, (1.0, 1.0, 1.0)), **kw)
+        self.scaleModel[volume] = tuple(res.scale_model)
+        return res
+
+    def LoadModel(self, volume, model_id):
+        """Scene::LoadModel (template/scene.cpp:449-529) on the device, then its palette override
+        of Renderer::materials (:516-520) and the table re-sent."""
+        self._load(volume, model_id, mode=abi.LOAD_FULL)
+        vox, pal = self._models[model_id]
+        if pal is not None:
+            abi.check(self.ctx.lib, None,
+                      self.ctx.lib.vpx_model_palette_materials(self.scene.materials, vox.ctypes.data, vox.size,
+                                                               pal.ctypes.data), "vpx_model_palette_materials")
+            self.ctx.set_materials(self.scene.materials)
+
+    def LoadModelPartial(self, volume, model_id, columns, thickness):
+        """Scene::LoadModelPartial (template/scene.cpp:531-604) on the device."""
+        self._load(volume, model_id, mode=abi.LOAD_PARTIAL, columns=columns, thickness=thickness)
+
+    def LoadModelRandomMaterials(self, volume, model_id):
+        """Scene::LoadModelRandomMaterials (template/scene.cpp:606-683) on the device: the draws
+        come from, and advance, self.seed (the thread's xorshift32 state, tmpl8math.cpp:16)."""
+        self.seed = self._load(volume, model_id, mode=abi.LOAD_RANDOM, seed=self.seed, rand_lo=12.0, rand_hi=13.0).seed
 
     def history_host(self):
         self.synchronize()

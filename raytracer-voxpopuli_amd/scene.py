@@ -10,6 +10,9 @@ Everything here is HOST-side input preparation restating the reference's scene s
     + palette of all 12 reference assets as ogt_vox returns them; tests/test_vox_decode.py
     checks vpx_vox_decode against the test fixtures and the store against the fixtures);
   - `load_model_grid`  Scene::LoadModel placement      template/scene.cpp:449-529
+  - `load_model_partial` Scene::LoadModelPartial        template/scene.cpp:531-604
+  - `load_model_random` Scene::LoadModelRandomMaterials template/scene.cpp:606-683
+    (the device does all three from a resident model: Context.grid_load_model)
   - `palette_materials` LoadModel's palette override    template/scene.cpp:516-520
   - lights / materials / camera defaults                renderer.cpp:93-100,357-443; camera.h
   - the build-defined tiled worlds of SURVEY.md §8(d) (C1/C2/C3/C4): the reference has no
@@ -68,9 +71,10 @@ def orient_model(size, voxels):
     return o, (sx, sz, sy)
 
 
-def load_model_grid(size, voxels, n, scale_model=(1.0, 1.0, 1.0)):
+def load_model_grid(size, voxels, n, scale_model=(1.0, 1.0, 1.0), values=None):
     """Scene::LoadModel into an n^3 grid (template/scene.cpp:449-529): ResetGrid() to
-    NONE, downscale only when size_x > n, (x, y, z) -> (x*s.x, z*s.y, y*s.z)."""
+    NONE, downscale only when size_x > n, (x, y, z) -> (x*s.x, z*s.y, y*s.z).
+    values: what the non-empty voxels write instead of their own byte (load_model_random)."""
     sx, sy, sz = (int(v) for v in size)
     scl = np.array(scale_model, np.float32)
     if sx > n:
@@ -78,7 +82,7 @@ def load_model_grid(size, voxels, n, scale_model=(1.0, 1.0, 1.0)):
     grid = np.full(n * n * n, NONE, np.uint8)
     v = voxels.reshape(sz, sy, sx)
     zz, yy, xx = np.nonzero(v)
-    vals = v[zz, yy, xx]
+    vals = (v if values is None else np.asarray(values, np.uint8).reshape(sz, sy, sx))[zz, yy, xx]
     gx = (xx.astype(np.float32) * scl[0]).astype(np.int64)
     gy = (zz.astype(np.float32) * scl[1]).astype(np.int64)
     gz = (yy.astype(np.float32) * scl[2]).astype(np.int64)
@@ -112,6 +116,48 @@ def load_model_partial(size, voxels, n, columns, thickness, scale_model=(1.0, 1.
         return grid, None
     z, y, x = nz
     return grid, (int(x.min()), int(y.min()), int(z.min()), int(x.max()) + 1, int(y.max()) + 1, int(z.max()) + 1)
+
+
+def _xorshift32(s):
+    """RandomUInt (tmpl8math.cpp:119-125) on uint32 arrays."""
+    s = s ^ (s << np.uint32(13))
+    s = s ^ (s >> np.uint32(17))
+    return s ^ (s << np.uint32(5))
+
+
+def xorshift32_stream(seed, count):
+    """The states after 1 .. count steps from `seed`, uint32[count].  The step is linear over
+    GF(2): with M = T^k as the images of the 32 bits, the states k+1 .. 2k are M applied to the
+    states 1 .. k, so the stream doubles per round instead of stepping count times."""
+    def apply(m, x):
+        r = np.zeros_like(x)
+        for b in range(32):
+            r ^= m[b] * ((x >> np.uint32(b)) & np.uint32(1))
+        return r
+
+    out = np.empty(max(1, count), np.uint32)
+    m = _xorshift32(np.uint32(1) << np.arange(32, dtype=np.uint32))  # T
+    out[0] = _xorshift32(np.array([seed & 0xFFFFFFFF], np.uint32))[0]
+    have = 1
+    while have < count:
+        k = min(have, count - have)
+        out[have:have + k] = apply(m, out[:k])
+        m = apply(m, m)
+        have += k
+    return out[:count]
+
+
+def load_model_random(size, voxels, n, seed, lo=12.0, hi=13.0, scale_model=(1.0, 1.0, 1.0)):
+    """Scene::LoadModelRandomMaterials (template/scene.cpp:606-683): LoadModel's placement, but
+    every voxel in loop order (x fastest, empty ones included) draws
+    static_cast<MatType>(Rand(lo, hi)) = lo + RandomFloat() * (hi - lo) from the xorshift32
+    state `seed`, and the non-empty ones write that.  The reference passes SMOKE_MID2_DENSITY,
+    SMOKE_HIGH_DENSITY (12, 13).  Returns (grid, the state after the sx*sy*sz draws)."""
+    count = int(size[0]) * int(size[1]) * int(size[2])
+    u = xorshift32_stream(int(seed), count)
+    r = u.astype(np.float32) * np.float32(2.3283064365387e-10)
+    mats = (np.float32(lo) + r * (np.float32(hi) - np.float32(lo))).astype(np.uint8)
+    return load_model_grid(size, voxels, n, scale_model, values=mats), int(u[-1]) if count else int(seed)
 
 
 def default_materials():
