@@ -529,6 +529,12 @@ int vpx_profile_read(vpx_ctx* ctx, vpx_profile* out, int reset);
    of n intervals [se[2i], se[2i+1]) in ms, overlaps counted once.  Starts may be negative
    (a lane's launch that began before the first recorded event). */
 float vpx_profile_busy_union(const float* se, uint32_t n);
+/* Debug: which form of the one-launch depth-0 frame kernel the context's last render launched:
+   0 = none (the frame ran as separate stages), 1 = the kernel specialised on what its launch
+   guarantees (one volume, no shapes, depth 0, one shadow slot per path), 2 = the lean form on
+   top (no spot or area lights, constant sky, no VPX_FLAG_DOF).  The forms compute the same
+   bits; tests use it to know which one they compared.  Host state only, no synchronisation. */
+int vpx_debug_last_frame_kernel(vpx_ctx* ctx);
 
 /* ---- unit entries (host pointers; mirror the reference per-ray functions) ---------- */
 int vpx_find_nearest(vpx_ctx* ctx, const vpx_ray* rays, uint32_t n, vpx_hit* hits);

@@ -260,6 +260,11 @@ class Context:
         return {name: (pr.stage_ms[i], pr.stage_launches[i], pr.stage_cells[i], pr.stage_busy_ms[i])
                 for i, name in enumerate(abi.STAGES)}
 
+    def last_frame_kernel(self):
+        """Debug (vpx_debug_last_frame_kernel): the form of the one-launch depth-0 frame kernel the
+        last render launched: 0 none, 1 specialised on its launch condition, 2 the lean form."""
+        return int(self.lib.vpx_debug_last_frame_kernel(self.h))
+
     def counters(self, reset=False):
         st = abi.Stats()
         self._chk(self.lib.vpx_get_counters(self.h, C.byref(st), 1 if reset else 0), "vpx_get_counters")

@@ -650,6 +650,7 @@ struct vpx_ctx {
     uint32_t tlas_nodes = 0;
     bool tlas_on = false;
     uint64_t tlas_always = 0;
+    int last_frame_kernel = 0;  // the last launch_render's form (vpx_debug_last_frame_kernel)
     void* d_bvh = nullptr;        // BasicBVH: nodes, then the triangles in tri_idx order (vpx_bvh_set)
     uint32_t bvh_nodes = 0, bvh_tris = 0;
     uint32_t d_volumes_cap = 0;
@@ -1098,15 +1099,29 @@ int launch_render(vpx_ctx* c, hipStream_t s, vpx_ctx::WaveStore& ws, const Scene
             hipLaunchKernelGGL(k_shadow_slots, dim3(std::min(tiles * S, c->cus * (uint32_t)VPX_WPE_SHADOW_SLOTS)), block, 0, s, sv,
                                w, level, c->d_ctr);
     };
-    if (one && fuse_tail && f.max_bounces == 0 && tiles <= kFuseFrameTiles && S == 1 && !f.batch_tiles) {
+    c->last_frame_kernel = 0;
+    if (frame0_fits(sv, f, S, rp != nullptr) && tiles <= kFuseFrameTiles) {
         // the whole depth-0 frame in one launch (k_frame0), its path state and one shadow slot
-        // per path in LDS; with area lights the frame splits to use the shadow pool
+        // per path in LDS; with area lights the frame splits to use the shadow pool.
+        // frame0_fits is what the kernel's kFrameGuaranteed view folds in as constants, and
+        // frame0_lean what kFrameLean adds (vpx_wavefront.hpp, side by side with the views): the
+        // form is chosen here, from the same sv / f the kernel receives.
         prof_mark(c, s, VPX_STAGE_FRAME);
 #ifndef VPX_FRAME_EXTRA_LDS
 #define VPX_FRAME_EXTRA_LDS 0  // A/B hook: bytes of unused LDS added per k_frame0 workgroup (occupancy sensitivity)
 #endif
-        hipLaunchKernelGGL((x86 ? k_frame0<true, MODE, true> : k_frame0<true, MODE, false>), grid, block,
-                           slds + VPX_FRAME_EXTRA_LDS, s, sv, f, w, c->d_ctr, accum, rgb8, packed);
+// The views that are built and launched: 2 = lean where frame0_lean holds, else guaranteed;
+// 1 = guaranteed only; 0 = the kernel as it was, on the runtime values (the A/B baseline).
+#ifndef VPX_FRAME_VIEWS
+#define VPX_FRAME_VIEWS 2
+#endif
+        constexpr int kBase = VPX_FRAME_VIEWS >= 1 ? kFrameGuaranteed : kFrameAsGiven;
+        constexpr int kLean = VPX_FRAME_VIEWS >= 2 ? kFrameLean : kBase;
+        const bool lean = VPX_FRAME_VIEWS >= 2 && frame0_lean(sv, f);
+        c->last_frame_kernel = lean ? 2 : 1;
+        hipLaunchKernelGGL((lean ? (x86 ? k_frame0<true, MODE, true, kLean> : k_frame0<true, MODE, false, kLean>)
+                                 : (x86 ? k_frame0<true, MODE, true, kBase> : k_frame0<true, MODE, false, kBase>)),
+                           grid, block, slds + VPX_FRAME_EXTRA_LDS, s, sv, f, w, c->d_ctr, accum, rgb8, packed);
         prof_mark(c, s, -1);
         VPX_HIP(c, hipGetLastError());
         return VPX_OK;
@@ -3017,12 +3032,26 @@ extern "C" int vpx_profile_read(vpx_ctx* c, vpx_profile* out, int reset) {
     return VPX_OK;
 }
 
+int vpx_debug_last_frame_kernel(vpx_ctx* c) {
+    VPX_GROUP_FIRST(c, vpx_debug_last_frame_kernel(m_));
+    return c ? c->last_frame_kernel : VPX_E_INVALID;
+}
+
 #ifdef VPX_PHASE_PROF
+// out: 48 words: g_phase, then the frame kernel's phases (g_frame_phase summed over its stripes)
 extern "C" int vpx_debug_phase(unsigned long long* out, int reset) {
+    static unsigned long long fp[vpx::kFrameStripes][16];
     if (hipMemcpyFromSymbol(out, HIP_SYMBOL(vpx::g_phase), sizeof(unsigned long long) * 32) != hipSuccess) return -1;
+    if (hipMemcpyFromSymbol(fp, HIP_SYMBOL(vpx::g_frame_phase), sizeof(fp)) != hipSuccess) return -1;
+    for (int k = 0; k < 16; ++k) {
+        out[32 + k] = 0;
+        for (int s = 0; s < vpx::kFrameStripes; ++s) out[32 + k] += fp[s][k];
+    }
     if (reset) {
         const unsigned long long z[32] = {};
         if (hipMemcpyToSymbol(HIP_SYMBOL(vpx::g_phase), z, sizeof(z)) != hipSuccess) return -1;
+        std::memset(fp, 0, sizeof(fp));
+        if (hipMemcpyToSymbol(HIP_SYMBOL(vpx::g_frame_phase), fp, sizeof(fp)) != hipSuccess) return -1;
     }
     return 0;
 }

@@ -658,10 +658,42 @@ constexpr uint32_t kRunShadowPool = VPX_RUN_SHADOW_POOL, kSkipwShadowPool = VPX_
 #ifdef VPX_PHASE_PROF
 // Debug build only (-DVPX_PHASE_PROF): per-wave cycles / iterations / active lanes of the
 // step and skip phases of walk_wave, read back with vpx_debug_phase().
+// (vpx_debug_phase returns 48 words: these 32, then the depth-0 frame kernel's phases, below.)
 __device__ unsigned long long g_phase[32];
 #define VPX_PH(...) __VA_ARGS__
 #else
 #define VPX_PH(...)
+#endif
+
+// The depth-0 frame kernel's phases (k_frame0, through primary_tile and shadow_tile), a
+// boundary each: VPX_FRAME_PHASE(k) ends phase k - 1 and starts phase k.  An -DVPX_ASM_MARKS
+// listing carries the boundaries as "; MARK frame <k>" (static counts per phase); a
+// -DVPX_PHASE_PROF build sums each phase's cycles over the launch's waves (the end times minus
+// the start times, mod 2^64, so a boundary keeps no state) and counts the waves; vpx_debug_phase
+// returns them as words 32 + k and 32 + kFramePhases.  The sums are kept per workgroup stripe, a
+// 128-byte line each (kFrameStripes: on one line the boundaries' atomics queued behind each
+// other and the walks' loads behind them).  A barrier's wait belongs to the phase it ends.  Only
+// frames that run k_frame0 give meaningful sums (k_primary and the shadow tile kernels pass
+// some of the boundaries, not all).
+//   0 head: primary ray, Setup3DDDA, the walker list        4 shadow list (counting sort by light)
+//   1 FindNearest waves: walk setup, walk, hit record       5 shadow waves: slot setup, walk, mark
+//   2 counters, waiting for the tile's walkers              6 counters, waiting for the tile's walkers
+//   3 level-0 shade                                         7 resolve and finish
+constexpr int kFramePhases = 8, kFrameStripes = 64;
+#ifdef VPX_PHASE_PROF
+__device__ unsigned long long g_frame_phase[kFrameStripes][16];
+__device__ __forceinline__ void frame_phase(int k) {
+    const unsigned long long t = __builtin_amdgcn_s_memtime();
+    if ((threadIdx.x & 63) == __builtin_amdgcn_readfirstlane(threadIdx.x & 63)) {
+        unsigned long long* g = g_frame_phase[blockIdx.x % kFrameStripes];
+        if (k > 0) atomicAdd(&g[k - 1], t);
+        if (k < kFramePhases) atomicAdd(&g[k], 0ull - t);
+        if (k == 0) atomicAdd(&g[kFramePhases], 1ull);
+    }
+}
+#define VPX_FRAME_PHASE(k) do { VPX_MARK("frame " #k); frame_phase(k); } while (0)
+#else
+#define VPX_FRAME_PHASE(k) VPX_MARK("frame " #k)
 #endif
 
 // Lane modes: kStep wants a cell step, kSkip an empty-box skip (the distance-field cube
