@@ -38,6 +38,8 @@
  *                           (ModifyingProp::Update, src/Game/ModifyingProp.cpp:11-21)
  *                         Scene::LoadModelRandomMaterials template/scene.cpp:606-683
  *                           (renderer.cpp:628, 2190)
+ *   vpx_grid_generate_noise  Scene::GenerateSomeNoise    template/scene.cpp:226-282 (renderer.cpp:2883-2898)
+ *                            Scene::GenerateSomeSmoke    template/scene.cpp:285-356 (renderer.cpp:626, 2174)
  *   vpx_grid_read_box     Scene::grid read back (debug)  template/scene.h:258
  *   vpx_set_volumes       Renderer::voxelVolumes      renderer.h:211
  *   vpx_set_materials     Renderer::materials         renderer.h:190, MaterialSetUp renderer.cpp:357-443
@@ -58,6 +60,8 @@
  *   vpx_model_place_host     the three loaders' placement loop  template/scene.cpp:449-683
  *   vpx_xorshift32_jump      RandomUInt, k steps at once        template/tmpl8math.cpp:119-125
  *   vpx_model_palette_materials  LoadModel's palette override   template/scene.cpp:516-520
+ *   vpx_noise_generate_host  the two generators' loops          template/scene.cpp:226-356
+ *   vpx_perlin3              the noise field (this project's definition, DESIGN parity decision 9)
  */
 #ifndef VPX_H_
 #define VPX_H_
@@ -327,6 +331,40 @@ typedef struct vpx_model_result {    /* 16 bytes */
    included).  Like every world edit the call waits for the frames in flight. */
 int vpx_grid_load_model(vpx_ctx* ctx, uint32_t grid_id, uint32_t n, uint32_t model_id,
                         const vpx_model_load* in, vpx_model_result* out /* may be NULL */);
+
+#define VPX_GEN_NOISE 0u   /* Scene::GenerateSomeNoise  scene.cpp:226-282 */
+#define VPX_GEN_SMOKE 1u   /* Scene::GenerateSomeSmoke  scene.cpp:285-356 */
+typedef struct vpx_noise_gen {       /* 16 bytes */
+    uint32_t mode;                   /* VPX_GEN_* */
+    float    frequency;              /* the generators' argument (0.167f at renderer.cpp:626, 2174) */
+    uint32_t seed;                   /* the caller's xorshift32 state (tmpl8math.cpp:16) */
+    uint32_t reserved;               /* 0 */
+} vpx_noise_gen;
+typedef struct vpx_noise_result {    /* 16 bytes */
+    uint32_t seed;                   /* the state the reference's thread-local seed is left in */
+    uint32_t noise_seed;             /* the call's first RandomUInt(), the field's seed */
+    uint64_t draws;                  /* every RandomUInt() of the call, the noise seed included */
+} vpx_noise_result;
+/* ResetGrid(), then Scene::GenerateSomeNoise or GenerateSomeSmoke on the device: no host grid,
+   no host noise library, one level rebuild.  Creates the grid (or resizes it) like
+   vpx_grid_load_model.  Every cell is written exactly once:
+     - the field: cell (x, y, z) samples vpx_perlin3((int32_t)noise_seed, x*f, y*f, z*f), all
+       float32; FastNoise2 is a binary in the reference, so the noise VALUES are this project's
+       definition (csrc/vpx_noise.hpp) while positions, thresholds and RNG order are the
+       reference's;
+     - NOISE: the chain of scene.cpp:250-275 as written — n <= 0.04f NONE; (double)n < 0.08 draws
+       (uint8_t)(RandomFloat() * 8.0f), 0..8; (double)n < 0.2 NON_METAL_RED; n < 0.17f is dead;
+       (double)n < 0.3 EMISSIVE; n < 0.5f METAL_HIGH; n < 0.7f METAL_MID; n < 0.9f METAL_LOW;
+       otherwise (NaN included) NONE.  The k-th drawing cell in loop order (z outer, y, x inner),
+       0-based, uses the state after 2 + k steps from `seed`;
+     - SMOKE: cell i = x + y*n + z*n*n draws randomX and randomZ from the states after 2 + 2i and
+       3 + 2i steps; the ellipsoid test and the five densities are scene.cpp:306-349.
+   VPX_E_INVALID: in == NULL, reserved != 0, unknown mode, n outside vpx_upload_grid's range, a
+   non-finite frequency, (n - 1) * |frequency| >= 2^30 (the float-to-int conversion of a lattice
+   coordinate stays in range below that).  VPX_E_NOMEM when the per-call prefix buffer cannot
+   be had.  Like every world edit the call waits for the frames in flight. */
+int vpx_grid_generate_noise(vpx_ctx* ctx, uint32_t grid_id, uint32_t n, const vpx_noise_gen* in,
+                            vpx_noise_result* out /* may be NULL */);
 /* Debug read-back of a box of cells, host bytes x fastest: the inverse of vpx_grid_write_box
    (a device set reads its first member). */
 int vpx_grid_read_box(vpx_ctx* ctx, uint32_t grid_id, uint8_t* dst, uint32_t x0, uint32_t y0, uint32_t z0,
@@ -644,6 +682,12 @@ int vpx_model_place_host(const uint8_t* voxels, uint32_t sx, uint32_t sy, uint32
 /* The xorshift32 state (13, 17, 5: RandomUInt, tmpl8math.cpp:119-125) after `steps` steps,
    by the jump: the step is linear over GF(2), so T^steps is a product of the T^(2^j). */
 uint32_t vpx_xorshift32_jump(uint32_t state, uint64_t steps);
+/* vpx_grid_generate_noise on the host (no device): cells = n^3 bytes.  The CPU path of the same
+   code (csrc/vpx_noise.hpp), block by block with the prefix and the jump like the kernels. */
+int vpx_noise_generate_host(uint32_t n, const vpx_noise_gen* in, uint8_t* cells, vpx_noise_result* out);
+/* One sample of the noise field: gradient noise on the integer lattice, float32 throughout,
+   exactly 0 on lattice points. */
+float vpx_perlin3(int32_t seed, float x, float y, float z);
 /* LoadModel's palette override (scene.cpp:516-520) on a 256-entry table: every index used
    by a non-empty voxel gets albedo = rgb / 255.0f and roughness 1. */
 int vpx_model_palette_materials(vpx_material* mats256, const uint8_t* voxels, uint64_t count,

@@ -131,6 +131,22 @@ def model_load(mode=LOAD_FULL, scale_model=(1.0, 1.0, 1.0), columns=0, thickness
                      int(seed) & 0xFFFFFFFF, float(rand_lo), float(rand_hi), 0)
 
 
+GEN_NOISE, GEN_SMOKE = 0, 1  # VPX_GEN_*: Scene::GenerateSomeNoise / GenerateSomeSmoke
+
+
+class NoiseGen(C.Structure):  # vpx_noise_gen: one generator call (vpx_grid_generate_noise)
+    _fields_ = [("mode", C.c_uint32), ("frequency", C.c_float), ("seed", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class NoiseResult(C.Structure):  # vpx_noise_result: the state left behind, the field's seed, every RandomUInt of the call
+    _fields_ = [("seed", C.c_uint32), ("noise_seed", C.c_uint32), ("draws", C.c_uint64)]
+
+
+def noise_gen(mode=GEN_NOISE, frequency=0.03, seed=0x12345678):
+    """abi.NoiseGen; the default frequency is GenerateSomeNoise's (scene.cpp:226)."""
+    return NoiseGen(int(mode), float(frequency), int(seed) & 0xFFFFFFFF, 0)
+
+
 class PrevCamera(C.Structure):
     _fields_ = [("cam_pos", f3), ("left_normal", f3), ("right_normal", f3), ("top_normal", f3),
                 ("bottom_normal", f3), ("pad", C.c_float)]
@@ -157,7 +173,8 @@ STAGES = ("primary", "shade", "shadow", "resolve", "bounce", "finish", "frame", 
 
 STRUCT_SIZES = {PrevCamera: 64, Profile: 160, Volume: 160, Material: 32, PointLight: 24, SpotLight: 40, AreaLight: 32, DirLight: 24,
                 Sphere: 32, Triangle: 64, Camera: 80, FrameParams: 48, Ray: 32, Hit: 32, Stats: 40,
-                BvhTri: 36, BvhNode: 32, PlayerLight: 24, RayProbe: 16, RayFilter: 16, ModelLoad: 40, ModelResult: 16}
+                BvhTri: 36, BvhNode: 32, PlayerLight: 24, RayProbe: 16, RayFilter: 16, ModelLoad: 40, ModelResult: 16,
+                NoiseGen: 16, NoiseResult: 16}
 
 
 def np_dtype(struct):
@@ -259,6 +276,9 @@ SIGNATURES = {
     "vpx_grid_read_box": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p] + [C.c_uint32] * 6),
     "vpx_xorshift32_jump": (C.c_uint32, [C.c_uint32, C.c_uint64]),
     "vpx_model_palette_materials": (C.c_int, [C.POINTER(Material), C.c_void_p, C.c_uint64, C.c_void_p]),
+    "vpx_grid_generate_noise": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(NoiseGen), C.POINTER(NoiseResult)]),
+    "vpx_noise_generate_host": (C.c_int, [C.c_uint32, C.POINTER(NoiseGen), C.c_void_p, C.POINTER(NoiseResult)]),
+    "vpx_perlin3": (C.c_float, [C.c_int32, C.c_float, C.c_float, C.c_float]),
 }
 
 _LIB = None

@@ -146,6 +146,17 @@ class Context:
                   "vpx_grid_load_model")
         return res
 
+    def grid_generate_noise(self, grid_id, n, mode=abi.GEN_NOISE, frequency=0.03, seed=0x12345678, gen=None):
+        """Scene::GenerateSomeNoise / GenerateSomeSmoke into grid grid_id (n^3, created or resized
+        as needed) on the device (vpx_grid_generate_noise).  gen: an abi.NoiseGen instead of the
+        keywords.  Returns the abi.NoiseResult: the xorshift32 state the call leaves, the field's
+        seed and the number of draws."""
+        g = gen if gen is not None else abi.noise_gen(mode, frequency, seed)
+        res = abi.NoiseResult()
+        self._chk(self.lib.vpx_grid_generate_noise(self.h, grid_id, int(n), C.byref(g), C.byref(res)),
+                  "vpx_grid_generate_noise")
+        return res
+
     def grid_read_box(self, grid_id, origin, shape):
         """Debug read-back (vpx_grid_read_box): the cells of the box at origin (x0, y0, z0) as a
         uint8 array of shape (dz, dy, dx), the inverse of grid_write_box."""

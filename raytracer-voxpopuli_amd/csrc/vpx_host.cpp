@@ -12,6 +12,7 @@
 
 #include "../../include/vpx.h"
 #include "vpx_model.hpp"
+#include "vpx_noise.hpp"
 
 namespace {
 
@@ -255,6 +256,7 @@ static_assert(sizeof(vpx_prev_camera) == 64, "vpx_prev_camera layout");
 static_assert(sizeof(vpx_player_light) == 24 && sizeof(vpx_ray_probe) == 16, "player light layout");
 static_assert(sizeof(vpx_ray_filter) == 16, "ray filter layout");
 static_assert(sizeof(vpx_model_load) == 40 && sizeof(vpx_model_result) == 16, "model load layout");
+static_assert(sizeof(vpx_noise_gen) == 16 && sizeof(vpx_noise_result) == 16, "noise generator layout");
 static_assert(sizeof(vpx_area_light) == 32 && sizeof(vpx_dir_light) == 24, "light layout");
 static_assert(sizeof(vpx_sphere) == 32 && sizeof(vpx_triangle) == 64, "shape layout");
 static_assert(sizeof(vpx_camera) == 80 && sizeof(vpx_frame_params) == 48, "camera/frame layout");
@@ -554,5 +556,20 @@ int vpx_model_palette_materials(vpx_material* mats, const uint8_t* voxels, uint6
     }
     return VPX_OK;
 }
+
+}  // extern "C"
+
+// ------------------------------------------------------------------ noise generators
+// Scene::GenerateSomeNoise / GenerateSomeSmoke (template/scene.cpp:226-356) on the host, through
+// the code the device runs (vpx_noise.hpp).
+extern "C" {
+
+int vpx_noise_generate_host(uint32_t n, const vpx_noise_gen* in, uint8_t* cells, vpx_noise_result* out) {
+    if (!cells || vpx::noise::check_gen(in, n)) return VPX_E_INVALID;
+    vpx::noise::generate_host(jump_tables(), n, in, cells, out);
+    return VPX_OK;
+}
+
+float vpx_perlin3(int32_t seed, float x, float y, float z) { return vpx::noise::perlin3(seed, x, y, z); }
 
 }  // extern "C"

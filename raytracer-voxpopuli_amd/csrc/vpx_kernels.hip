@@ -9,6 +9,7 @@
 //   find_nearest_k / is_occluded_k / trace_k   per-ray unit entries.
 //   tiled_world_k / checksum_k    world generator and grid checksum.
 //   model_gather_k / model_random_k   the model loaders' placement (vpx_model.hpp).
+//   smoke_gen_k / noise_mark_k / noise_scan_k / noise_draw_k   the noise generators (vpx_noise.hpp).
 #include <hip/hip_runtime.h>
 #include <hip/hip_gl_interop.h>
 #include <rccl/rccl.h>
@@ -25,6 +26,7 @@
 
 #include "vpx_wavefront.hpp"
 #include "vpx_model.hpp"
+#include "vpx_noise.hpp"
 
 using namespace vpx;
 
@@ -392,6 +394,167 @@ __global__ void read_box_k(const uint8_t* __restrict__ grid, uint32_t n, uint8_t
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (uint64_t)gridDim.x * blockDim.x) {
         const uint64_t x = i % dx, y = (i / dx) % dy, z = i / ((uint64_t)dx * dy);
         dst[i] = grid[(x0 + x) + (y0 + y) * n64 + (z0 + z) * n64 * n64];
+    }
+}
+
+// ------------------------------------------------------------- noise generators
+// Scene::GenerateSomeNoise / GenerateSomeSmoke (template/scene.cpp:226-356, vpx_noise.hpp).  A
+// workgroup takes blocks of noise::kBlockCells consecutive cells, a thread the span of kSpan
+// cells at 16 * threadIdx.x of the block: one 16-byte store when n % 16 == 0 (a span then lies
+// in one grid row), byte stores with the grid's end checked otherwise.  Every cell is written:
+// the ResetGrid() is part of the pass.
+
+__device__ __forceinline__ void span_store(uint8_t* __restrict__ out, uint64_t first, uint32_t count, bool row,
+                                           const uint8_t (&v)[noise::kSpan]) {
+    if (row) {
+        uint32_t w[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+            w[q] = (uint32_t)v[4 * q] | (uint32_t)v[4 * q + 1] << 8 | (uint32_t)v[4 * q + 2] << 16 |
+                   (uint32_t)v[4 * q + 3] << 24;
+        *reinterpret_cast<uint4*>(out + first) = make_uint4(w[0], w[1], w[2], w[3]);
+    } else {
+#pragma unroll
+        for (uint32_t c = 0; c < noise::kSpan; ++c)
+            if (c < count) out[first + c] = v[c];
+    }
+}
+
+// The drawers of a wave, span masks in lane order: how many lie in the lanes below this one,
+// and how many the wave has (wave64: a ballot per span position, counted below the lane by
+// mbcnt).  Every lane of the wave must call it.
+__device__ __forceinline__ void wave_rank(uint32_t mask, uint32_t& below, uint32_t& total) {
+    below = 0, total = 0;
+#pragma unroll
+    for (uint32_t c = 0; c < noise::kSpan; ++c) {
+        const unsigned long long b = __ballot((mask >> c) & 1u);
+        below += __builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u));
+        total += (uint32_t)__popcll(b);
+    }
+}
+
+// GenerateSomeSmoke: one pass.  Cell i draws twice, so the block's first state is the jump of
+// 1 + 2 * (its first cell) steps — the same for the whole workgroup — and a thread jumps the
+// 32 * threadIdx.x steps of the spans before its own from there.
+__global__ __launch_bounds__(256) void smoke_gen_k(uint8_t* __restrict__ out, uint32_t n, float f, int32_t nseed,
+                                                   const uint32_t* __restrict__ tables, uint32_t seed, uint64_t blocks) {
+    const uint64_t total = (uint64_t)n * n * n;
+    const bool row = (n % noise::kSpan) == 0;
+    for (uint64_t b = blockIdx.x; b < blocks; b += gridDim.x) {
+        const uint64_t first = b * noise::kBlockCells + (uint64_t)threadIdx.x * noise::kSpan;
+        if (first >= total) continue;
+        const uint32_t base = model::xs32_jump(tables, seed, 1 + 2 * b * noise::kBlockCells);
+        const uint32_t s = model::xs32_jump(tables, base, 2ull * noise::kSpan * threadIdx.x);
+        const uint32_t count = (uint32_t)(total - first < noise::kSpan ? total - first : noise::kSpan);
+        uint8_t v[noise::kSpan];
+        if (row)
+            noise::smoke_span<true>(nseed, n, f, first, noise::kSpan, s, v);
+        else
+            noise::smoke_span<false>(nseed, n, f, first, count, s, v);
+        span_store(out, first, count, row, v);
+    }
+}
+
+// GenerateSomeNoise, pass 1: every cell's material, noise::kDrawMark where the cell draws, and
+// the number of drawers of each block into counts.
+__global__ __launch_bounds__(256) void noise_mark_k(uint8_t* __restrict__ out, uint32_t n, float f, int32_t nseed,
+                                                    uint64_t blocks, uint32_t* __restrict__ counts) {
+    __shared__ uint32_t wsum[noise::kBlockThreads / 64];
+    const uint64_t total = (uint64_t)n * n * n;
+    const bool row = (n % noise::kSpan) == 0;
+    for (uint64_t b = blockIdx.x; b < blocks; b += gridDim.x) {
+        const uint64_t first = b * noise::kBlockCells + (uint64_t)threadIdx.x * noise::kSpan;
+        uint32_t mask = 0;
+        if (first < total) {
+            const uint32_t count = (uint32_t)(total - first < noise::kSpan ? total - first : noise::kSpan);
+            uint8_t v[noise::kSpan];
+            mask = row ? noise::noise_span<true>(nseed, n, f, first, noise::kSpan, v)
+                       : noise::noise_span<false>(nseed, n, f, first, count, v);
+            span_store(out, first, count, row, v);
+        }
+        uint32_t below, wave;
+        wave_rank(mask, below, wave);
+        if ((threadIdx.x & 63u) == 0) wsum[threadIdx.x >> 6] = wave;
+        __syncthreads();
+        if (threadIdx.x == 0) counts[b] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+        __syncthreads();
+    }
+}
+
+// Pass 2: offsets[b] = the drawers of the blocks before b, total[0] = all of them, 64-bit.  One
+// workgroup walks the counts noise::kScanPass at a time and carries the sum from pass to pass,
+// so the prefix is exact for any number of blocks (a pass sums at most 256 * 4096).
+__global__ __launch_bounds__(256) void noise_scan_k(const uint32_t* __restrict__ counts, uint64_t blocks,
+                                                    uint64_t* __restrict__ offsets, uint64_t* __restrict__ total) {
+    __shared__ uint32_t wsum[noise::kScanPass / 64];
+    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+    uint64_t carry = 0;
+    for (uint64_t at = 0; at < blocks; at += noise::kScanPass) {
+        const uint64_t i = at + threadIdx.x;
+        const uint32_t v = i < blocks ? counts[i] : 0u;
+        uint32_t incl = v;
+#pragma unroll
+        for (uint32_t d = 1; d < 64; d <<= 1) {
+            const uint32_t up = __shfl_up(incl, d);
+            if (lane >= d) incl += up;
+        }
+        if (lane == 63) wsum[w] = incl;
+        __syncthreads();
+        uint32_t before = 0, all = 0;
+#pragma unroll
+        for (uint32_t k = 0; k < noise::kScanPass / 64; ++k) {
+            before += k < w ? wsum[k] : 0u;
+            all += wsum[k];
+        }
+        if (i < blocks) offsets[i] = carry + before + (incl - v);
+        carry += all;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) total[0] = carry;
+}
+
+// Pass 3: every marked cell takes its draw.  Its rank among the drawers is the block's offset
+// plus the drawers of the block's spans before its own plus its place in the span; the state is
+// the jump to the block's first rank — the same for the whole workgroup — then the jump by the
+// in-block rank (< 4096), then plain steps along the span.  Spans without a mark are not
+// touched; a block without drawers is skipped by all its threads alike.
+__global__ __launch_bounds__(256) void noise_draw_k(uint8_t* __restrict__ out, uint32_t n,
+                                                    const uint32_t* __restrict__ tables, uint32_t seed, uint64_t blocks,
+                                                    const uint32_t* __restrict__ counts,
+                                                    const uint64_t* __restrict__ offsets) {
+    __shared__ uint32_t wsum[noise::kBlockThreads / 64];
+    const uint64_t total = (uint64_t)n * n * n;
+    const bool row = (n % noise::kSpan) == 0;
+    for (uint64_t b = blockIdx.x; b < blocks; b += gridDim.x) {
+        if (counts[b] == 0) continue;
+        const uint64_t first = b * noise::kBlockCells + (uint64_t)threadIdx.x * noise::kSpan;
+        const uint32_t count = first >= total ? 0u : (uint32_t)(total - first < noise::kSpan ? total - first : noise::kSpan);
+        uint8_t v[noise::kSpan];
+        if (row) {
+            const uint4 q = *reinterpret_cast<const uint4*>(out + first);
+            const uint32_t w[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+            for (uint32_t c = 0; c < noise::kSpan; ++c) v[c] = (uint8_t)(w[c >> 2] >> (8 * (c & 3)));
+        } else {
+#pragma unroll
+            for (uint32_t c = 0; c < noise::kSpan; ++c) v[c] = c < count ? out[first + c] : noise::kNone;
+        }
+        uint32_t mask = 0;
+#pragma unroll
+        for (uint32_t c = 0; c < noise::kSpan; ++c) mask |= (uint32_t)(v[c] == noise::kDrawMark) << c;
+        uint32_t below, wave;
+        wave_rank(mask, below, wave);
+        if ((threadIdx.x & 63u) == 0) wsum[threadIdx.x >> 6] = wave;
+        __syncthreads();
+        uint32_t before = below;
+#pragma unroll
+        for (uint32_t k = 0; k < noise::kBlockThreads / 64; ++k) before += k < (threadIdx.x >> 6) ? wsum[k] : 0u;
+        if (mask) {
+            const uint32_t base = model::xs32_jump(tables, seed, 1 + offsets[b]);
+            noise::noise_fill_span(model::xs32_jump(tables, base, before), mask, v);
+            span_store(out, first, count, row, v);
+        }
+        __syncthreads();
     }
 }
 
@@ -1766,6 +1929,23 @@ int vpx_generate_tiled_grid(vpx_ctx* c, uint32_t id, uint32_t n, const uint8_t* 
 
 constexpr size_t kJumpBytes = sizeof(uint32_t) * 32 * model::kJumpDevice;
 
+// The jump tables, once, with room for the plan of the largest grid (n = 4096) behind them.
+static int ensure_model_aux(vpx_ctx* c) {
+    if (c->d_model_aux) return VPX_OK;
+    std::vector<uint32_t> t(32 * model::kJumpDevice);
+    model::xs32_build_tables(t.data(), model::kJumpDevice);
+    if (!c->h_plan) VPX_HIP(c, hipHostMalloc((void**)&c->h_plan, model::plan_bytes(4096)));
+    uint8_t* aux = nullptr;
+    VPX_HIP(c, hipMalloc(&aux, kJumpBytes + model::plan_bytes(4096)));
+    const hipError_t e = hipMemcpy(aux, t.data(), kJumpBytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        (void)hipFree(aux);
+        return fail(c, VPX_E_DEVICE, std::string("jump tables: ") + hipGetErrorString(e));
+    }
+    c->d_model_aux = aux;
+    return VPX_OK;
+}
+
 int vpx_model_upload(vpx_ctx* c, uint32_t id, const uint8_t* voxels, uint32_t sx, uint32_t sy, uint32_t sz) {
     VPX_GROUP_ALL(c, vpx_model_upload(m_, id, voxels, sx, sy, sz));
     if (!c) return VPX_E_INVALID;
@@ -1780,13 +1960,7 @@ int vpx_model_upload(vpx_ctx* c, uint32_t id, const uint8_t* voxels, uint32_t sx
         c->models[id] = vpx_ctx::ModelBuf{};
     }
     if (!voxels) return VPX_OK;
-    if (!c->d_model_aux) {  // jump tables once; the plan of the largest grid (n = 4096) fits behind them
-        std::vector<uint32_t> t(32 * model::kJumpDevice);
-        model::xs32_build_tables(t.data(), model::kJumpDevice);
-        VPX_HIP(c, hipHostMalloc((void**)&c->h_plan, model::plan_bytes(4096)));
-        VPX_HIP(c, hipMalloc(&c->d_model_aux, kJumpBytes + model::plan_bytes(4096)));
-        VPX_HIP(c, hipMemcpy(c->d_model_aux, t.data(), kJumpBytes, hipMemcpyHostToDevice));
-    }
+    if (int rc = ensure_model_aux(c)) return rc;
     if (id >= c->models.size()) c->models.resize(id + 1);
     auto& m = c->models[id];
     const size_t count = (size_t)sx * sy * sz;
@@ -1831,6 +2005,55 @@ int vpx_grid_load_model(vpx_ctx* c, uint32_t id, uint32_t n, uint32_t model_id, 
     VPX_HIP(c, hipGetLastError());
     if (int rc = build_masks(c, id)) return rc;
     if (out) *out = res;
+    return VPX_OK;
+}
+
+int vpx_grid_generate_noise(vpx_ctx* c, uint32_t id, uint32_t n, const vpx_noise_gen* in, vpx_noise_result* out) {
+    VPX_GROUP_ALL(c, vpx_grid_generate_noise(m_, id, n, in, out));
+    if (!c) return VPX_E_INVALID;
+    if (const char* why = noise::check_gen(in, n)) return fail(c, VPX_E_INVALID, why);
+    if (id > 4096) return fail(c, VPX_E_INVALID, "grid_id too large");
+    VPX_HIP(c, hipSetDevice(c->device));
+    VPX_HIP(c, sync_all(c));  // frames in flight still read the grid
+    if (int rc = ensure_model_aux(c)) return rc;
+    const uint64_t total = (uint64_t)n * n * n, blocks = (total + noise::kBlockCells - 1) / noise::kBlockCells;
+    uint64_t drawers = 2 * total;  // SMOKE: two per cell
+    uint32_t *d_counts = nullptr;
+    uint64_t *d_total = nullptr, *d_offsets = nullptr;
+    if (in->mode == VPX_GEN_NOISE) {  // the prefix buffer of this call: total | offsets | counts
+        if (int rc = ensure_scratch(c, (size_t)(8 + 12 * blocks))) return rc;
+        d_total = (uint64_t*)c->d_scratch;
+        d_offsets = d_total + 1;
+        d_counts = (uint32_t*)(d_offsets + blocks);
+    }
+    if (id >= c->grids.size() || !c->grids[id].ptr || c->grids[id].n != n)
+        if (int rc = alloc_grid(c, id, n)) return rc;
+    uint8_t* cells = c->grids[id].ptr;
+    const uint32_t* tables = (const uint32_t*)c->d_model_aux;
+    const uint32_t noise_seed = model::xs32_step(in->seed);
+    const dim3 grid((unsigned)std::min<uint64_t>(8192, blocks)), wg(noise::kBlockThreads);
+    if (in->mode == VPX_GEN_SMOKE) {
+        hipLaunchKernelGGL(smoke_gen_k, grid, wg, 0, c->stream, cells, n, in->frequency, (int32_t)noise_seed, tables,
+                           in->seed, blocks);
+        VPX_HIP(c, hipGetLastError());
+    } else {
+        hipLaunchKernelGGL(noise_mark_k, grid, wg, 0, c->stream, cells, n, in->frequency, (int32_t)noise_seed, blocks,
+                           d_counts);
+        VPX_HIP(c, hipGetLastError());
+        hipLaunchKernelGGL(noise_scan_k, dim3(1), dim3(noise::kScanPass), 0, c->stream, (const uint32_t*)d_counts, blocks,
+                           d_offsets, d_total);
+        VPX_HIP(c, hipGetLastError());
+        hipLaunchKernelGGL(noise_draw_k, grid, wg, 0, c->stream, cells, n, tables, in->seed, blocks,
+                           (const uint32_t*)d_counts, (const uint64_t*)d_offsets);
+        VPX_HIP(c, hipGetLastError());
+        VPX_HIP(c, hipMemcpyAsync(&drawers, d_total, sizeof(drawers), hipMemcpyDeviceToHost, c->stream));
+    }
+    if (int rc = build_masks(c, id)) return rc;  // ends with sync_all: `drawers` has arrived
+    if (out) {
+        out->noise_seed = noise_seed;
+        out->draws = 1 + drawers;
+        out->seed = vpx_xorshift32_jump(in->seed, out->draws);
+    }
     return VPX_OK;
 }
 

@@ -37,7 +37,8 @@ namespace model {
 
 constexpr uint32_t kMaxDim = 256;     // a .vox model is at most 256 voxels a side
 constexpr uint8_t kNoneMat = 255;     // MaterialType::NONE
-constexpr uint32_t kJumpDevice = 24;  // T^(2^j), j < 24: every voxel index of a 256^3 model
+constexpr uint32_t kJumpDevice = 40;  // T^(2^j), j < 40: every voxel index of a 256^3 model, and the
+                                      // 1 + 2 * 4096^3 draws of a smoke grid (vpx_noise.hpp)
 constexpr uint32_t kJumpHost = 64;
 constexpr uint32_t kChunk = 64;       // voxels per thread of the random-material pass
 

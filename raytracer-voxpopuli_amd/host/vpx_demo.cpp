@@ -19,7 +19,10 @@
 //   centre, printing index, t, normal and material of each, and IsOccludedPlayerClimbable of
 //   the same ray, as one JSON line; 'm' renders nothing either: it runs five ModifyingProp edits,
 //   a LoadModel and a LoadModelRandomMaterials of a synthetic model through the mirror
-//   (prop_edits below) and prints the grid checksum after each as one JSON line; '-' none.
+//   (prop_edits below) and prints the grid checksum after each as one JSON line; 'g' renders
+//   nothing: GenerateSomeNoise(0.03f) and GenerateSomeSmoke(0.167f) through the mirror on an n^3
+//   grid (n: the first argument), the checksum, the draws and the seed after each as one JSON
+//   line; '-' none.
 //   devices: comma-separated HIP devices, e.g. 0,1,2,3 — a device set (vpx_create_multi:
 //   tiles over the devices, RCCL gather to the first); default: device 0 alone.
 #include <chrono>
@@ -182,6 +185,27 @@ static int prop_edits(vpxhost::Renderer& r) {
     return 0;
 }
 
+// Mode 'g': the noise generators through the C++ mirror, nothing rendered: the noise world, then
+// the checkpoint's smoke on the same Scene, each drawing from the seed the one before left.
+static int generators(vpxhost::Renderer& r, uint32_t n) {
+    r.CreateGrid(0, n);
+    vpx_volume vol{};
+    const float zero[3] = {0, 0, 0}, one[3] = {1, 1, 1};
+    CHECK(vpx_volume_set_transform(zero, one, zero, &vol));
+    CHECK(r.SetVolumes({vol}));
+    vpx_noise_result noise{}, smoke{};
+    uint64_t noise_sum = 0, smoke_sum = 0;
+    CHECK(r.GenerateSomeNoise(0, 0.03f, &noise));
+    CHECK(vpx_grid_checksum(r.Context(), 0, &noise_sum));
+    CHECK(r.GenerateSomeSmoke(0, 0.167f, &smoke));
+    CHECK(vpx_grid_checksum(r.Context(), 0, &smoke_sum));
+    std::printf("{\"n\": %u, \"noise\": {\"checksum\": \"%llu\", \"draws\": %llu, \"seed\": %u}, "
+                "\"smoke\": {\"checksum\": \"%llu\", \"draws\": %llu, \"seed\": %u}}\n",
+                n, (unsigned long long)noise_sum, (unsigned long long)noise.draws, noise.seed,
+                (unsigned long long)smoke_sum, (unsigned long long)smoke.draws, smoke.seed);
+    return 0;
+}
+
 int main(int argc, char** argv) {
     const uint32_t n = argc > 1 ? (uint32_t)atoi(argv[1]) : 256;
     const uint32_t W = argc > 2 ? (uint32_t)atoi(argv[2]) : 640;
@@ -190,9 +214,11 @@ int main(int argc, char** argv) {
     const int bounces = argc > 5 ? atoi(argv[5]) : 0;
     const char* out = argc > 6 && argv[6][0] != '-' ? argv[6] : nullptr;
     const char* mode = argc > 7 ? argv[7] : "";
-    bool is_static = false, sky = false, player_light = false, player_cast = false, prop_edit = false;
+    bool is_static = false, sky = false, player_light = false, player_cast = false, prop_edit = false,
+         generate = false;
     for (const char* m = mode; *m; ++m)
-        is_static |= *m == 's', sky |= *m == 'k', player_light |= *m == 'p', player_cast |= *m == 'w', prop_edit |= *m == 'm';
+        is_static |= *m == 's', sky |= *m == 'k', player_light |= *m == 'p', player_cast |= *m == 'w', prop_edit |= *m == 'm',
+            generate |= *m == 'g';
     std::vector<int> devices;
     if (argc > 8)
         for (const char* d = argv[8]; *d;) {
@@ -205,6 +231,7 @@ int main(int argc, char** argv) {
     CHECK(r.Init(W, H));
     if (player_cast) return player_rays(r);
     if (prop_edit) return prop_edits(r);
+    if (generate) return generators(r, n);
     std::vector<uint8_t> grid = pillars(n);
     if (player_light)  // the player: a block of smoke in the world, which is volume 0
         for (uint32_t z = n / 4; z < 3 * n / 8; ++z)

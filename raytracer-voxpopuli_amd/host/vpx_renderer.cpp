@@ -133,6 +133,31 @@ int Renderer::LoadModelRandomMaterials(uint32_t volume, uint32_t model_id) {
     return rc;
 }
 
+// Scene::GenerateSomeNoise / GenerateSomeSmoke on the Scene of `volume`: its grid and its size;
+// the draws come from, and advance, `seed`.
+int Renderer::Generate(uint32_t volume, uint32_t mode, float frequency, vpx_noise_result* out) {
+    if (status_) return status_;
+    if (volume >= volumes_.size()) return VPX_E_INVALID;
+    const uint32_t gid = volumes_[volume].grid_id;
+    if (gid >= gridSize_.size() || !gridSize_[gid]) return VPX_E_STATE;  // CreateGrid / UploadGrid first
+    vpx_noise_gen in{};
+    in.mode = mode, in.frequency = frequency, in.seed = seed;
+    vpx_noise_result res{};
+    const int rc = vpx_grid_generate_noise(ctx_, gid, gridSize_[gid], &in, &res);
+    if (rc) return rc;
+    seed = res.seed;
+    if (out) *out = res;
+    return VPX_OK;
+}
+
+int Renderer::GenerateSomeNoise(uint32_t volume, float frequency, vpx_noise_result* out) {
+    return Generate(volume, VPX_GEN_NOISE, frequency, out);
+}
+
+int Renderer::GenerateSomeSmoke(uint32_t volume, float frequency, vpx_noise_result* out) {
+    return Generate(volume, VPX_GEN_SMOKE, frequency, out);
+}
+
 int Renderer::SetLights(const std::vector<vpx_point_light>& p, const std::vector<vpx_spot_light>& s,
                         const std::vector<vpx_area_light>& a, const vpx_dir_light& d) {
     if (status_) return status_;

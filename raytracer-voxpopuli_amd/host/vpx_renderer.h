@@ -84,6 +84,11 @@ public:
     int LoadModelRandomMaterials(uint32_t volume, uint32_t model_id);
     // Scene::scaleModel of a volume ((1, 1, 1) until a loader multiplies it).
     const float* ScaleModel(uint32_t volume);
+    // Scene::GenerateSomeNoise (template/scene.cpp:226-282) and GenerateSomeSmoke (:285-356) into the
+    // volume's grid on the device, as voxelVolumes[5].GenerateSomeSmoke(0.167f) (renderer.cpp:626,
+    // 2174) and the volume UI (:2883-2898); the draws come from, and advance, `seed`.
+    int GenerateSomeNoise(uint32_t volume, float frequency = 0.03f, vpx_noise_result* out = nullptr);
+    int GenerateSomeSmoke(uint32_t volume, float frequency = 0.001f, vpx_noise_result* out = nullptr);
 
     // --- per frame -----------------------------------------------------------------------
     void ResetAccumulator() { numRenderedFrames = 0; }  // renderer.cpp:343-346
@@ -133,10 +138,11 @@ public:
     bool trackPlayerLight = false;
     vpx_player_light playerLight{};  // the last tracked Tick's record
     int32_t currentChunk = 0;        // read by FindNearestPlayer (renderer.cpp:1068)
-    uint32_t seed = 0x12345678u;     // the xorshift32 state of LoadModelRandomMaterials (tmpl8math.cpp:16)
+    uint32_t seed = 0x12345678u;     // the xorshift32 state the loaders and generators draw from (tmpl8math.cpp:16)
 
 private:
     int Load(uint32_t volume, uint32_t model_id, vpx_model_load in, vpx_model_result* out);
+    int Generate(uint32_t volume, uint32_t mode, float frequency, vpx_noise_result* out);
     struct Model { std::vector<uint8_t> voxels, palette; };
     std::vector<Model> models_;
     std::vector<vpx_volume> volumes_;      // voxelVolumes as SetVolumes left them

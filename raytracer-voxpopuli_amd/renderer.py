@@ -209,6 +209,23 @@ class Renderer:
         come from, and advance, self.seed (the thread's xorshift32 state, tmpl8math.cpp:16)."""
         self.seed = self._load(volume, model_id, mode=abi.LOAD_RANDOM, seed=self.seed, rand_lo=12.0, rand_hi=13.0).seed
 
+    # ------------------------------------------------------------ noise generators
+    def _generate(self, volume, mode, frequency):
+        gid = self.scene.volumes[volume].grid_id
+        res = self.ctx.grid_generate_noise(gid, self.scene.grids[gid].n, mode, frequency, self.seed)
+        self.seed = res.seed
+        return res
+
+    def GenerateSomeNoise(self, volume, frequency=0.03):
+        """Scene::GenerateSomeNoise (template/scene.cpp:226-282) on the device, on the Scene of
+        `volume`: the draws come from, and advance, self.seed."""
+        return self._generate(volume, abi.GEN_NOISE, frequency)
+
+    def GenerateSomeSmoke(self, volume, frequency=0.001):
+        """Scene::GenerateSomeSmoke (template/scene.cpp:285-356) on the device, as
+        voxelVolumes[5].GenerateSomeSmoke(0.167f) of renderer.cpp:626 and :2174."""
+        return self._generate(volume, abi.GEN_SMOKE, frequency)
+
     def history_host(self):
         self.synchronize()
         return self.illuminationHistory.cpu().numpy().reshape(self.scene.height, self.scene.width, 4)

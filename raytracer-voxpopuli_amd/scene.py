@@ -14,6 +14,8 @@ Everything here is HOST-side input preparation restating the reference's scene s
   - `load_model_random` Scene::LoadModelRandomMaterials template/scene.cpp:606-683
     (the device does all three from a resident model: Context.grid_load_model)
   - `palette_materials` LoadModel's palette override    template/scene.cpp:516-520
+  - `generate_some_noise` / `generate_some_smoke`  Scene::GenerateSomeNoise / GenerateSomeSmoke
+    template/scene.cpp:226-356 (over vpx_noise_generate_host; the device: Context.grid_generate_noise)
   - lights / materials / camera defaults                renderer.cpp:93-100,357-443; camera.h
   - the build-defined tiled worlds of SURVEY.md §8(d) (C1/C2/C3/C4): the reference has no
     world larger than 128^3 of its own (every .vox is <= 126 voxels a side).
@@ -158,6 +160,27 @@ def load_model_random(size, voxels, n, seed, lo=12.0, hi=13.0, scale_model=(1.0,
     r = u.astype(np.float32) * np.float32(2.3283064365387e-10)
     mats = (np.float32(lo) + r * (np.float32(hi) - np.float32(lo))).astype(np.uint8)
     return load_model_grid(size, voxels, n, scale_model, values=mats), int(u[-1]) if count else int(seed)
+
+
+def _generate(mode, n, frequency, seed):
+    lib = abi.load_library()
+    cells = np.empty(int(n) ** 3, np.uint8)
+    res = abi.NoiseResult()
+    abi.check(lib, None, lib.vpx_noise_generate_host(int(n), C.byref(abi.noise_gen(mode, frequency, seed)),
+                                                     cells.ctypes.data, C.byref(res)), "vpx_noise_generate_host")
+    return cells, res
+
+
+def generate_some_noise(n, frequency=0.03, seed=0x12345678):
+    """Scene::GenerateSomeNoise(frequency) of an n^3 Scene (template/scene.cpp:226-282) from the
+    xorshift32 state `seed`: (grid, abi.NoiseResult).  The noise values are the project's own
+    field (vpx_perlin3), the thresholds and the order of the draws the reference's."""
+    return _generate(abi.GEN_NOISE, n, frequency, seed)
+
+
+def generate_some_smoke(n, frequency=0.001, seed=0x12345678):
+    """Scene::GenerateSomeSmoke(frequency) (template/scene.cpp:285-356): (grid, abi.NoiseResult)."""
+    return _generate(abi.GEN_SMOKE, n, frequency, seed)
 
 
 def default_materials():
@@ -458,7 +481,7 @@ def _cos_degrees(d):
     return float(np.float32(math.cos(float(r))))
 
 
-def zone_scene(width=1920, height=1080, max_bounces=14, sky=True):
+def zone_scene(width=1920, height=1080, max_bounces=14, sky=True, smoke="ball", seed=0x12345678):
     """The reference's own scene shape: Renderer::SetUpFirstZone (renderer.cpp:592-657) with
     its CreateBridge (:482-529) and CreateBridgeBlind (:531-590), CreateTrianglePattern
     (:460-469) and SetUpLights (:93-100: 1 point light, 5 spot lights, the directional light
@@ -469,7 +492,11 @@ def zone_scene(width=1920, height=1080, max_bounces=14, sky=True):
     triangles.  Build-defined where the reference draws at run time: the Rand() material picks
     (fixed values from the same ranges), the FastNoise2 smoke of the 64^3 checkpoint volume
     (GenerateSomeSmoke) — a deterministic smoke ball instead — and the Text model's random
-    materials (LoadModelRandomMaterials) — its palette materials instead."""
+    materials (LoadModelRandomMaterials) — its palette materials instead.
+    smoke="noise": the checkpoint volume gets voxelVolumes[5].GenerateSomeSmoke(0.167f)
+    (renderer.cpp:626) from the xorshift32 state `seed`, with the project's noise field; the
+    default "ball" is the scene as it always was (the Z1 bench config)."""
+    assert smoke in ("ball", "noise"), smoke
     MET_LOW, GLASS, PINK = 7, 8, 4
     mats = default_materials()
     psize, pvox, ppal = load_model("player")
@@ -490,7 +517,8 @@ def zone_scene(width=1920, height=1080, max_bounces=14, sky=True):
     n = 64  # the checkpoint's smoke: a ball of smoke cells (SMOKE_LOW_DENSITY..SMOKE_PLAYER - 1)
     z, y, x = np.meshgrid(*(np.arange(n, dtype=np.float32),) * 3, indexing="ij")
     r = np.sqrt((x - 31.5) ** 2 + (y - 31.5) ** 2 + (z - 31.5) ** 2)
-    smoke = np.where(r < 20.0, (9 + (r.astype(np.int64) % 5)).astype(np.uint8), np.uint8(NONE)).reshape(-1)
+    ball = np.where(r < 20.0, (9 + (r.astype(np.int64) % 5)).astype(np.uint8), np.uint8(NONE)).reshape(-1)
+    checkpoint = ball if smoke == "ball" else generate_some_smoke(n, 0.167, seed)[0]
     vols = []
 
     def vol(pos, scl, g):
@@ -501,7 +529,7 @@ def zone_scene(width=1920, height=1080, max_bounces=14, sky=True):
     vol((6.0, 0.0, 0.0), (5.0, 5.0, 5.0), solid(MET_LOW))
     vol((-10.0, 2.0, 0.0), (5.0, 5.0, 5.0), solid(MET_LOW))
     vol((0.0, 4.0, 0.0), (10.0, 1.0, 10.0), solid(MET_LOW))
-    vol((0.0, 0.3, 0.0), (3.0, 3.0, 3.0), grid("smoke", 64, smoke))  # checkpoint
+    vol((0.0, 0.3, 0.0), (3.0, 3.0, 3.0), grid("smoke", 64, checkpoint))  # checkpoint
     vol((0.0, 3.0, -3.0), (5.0, 5.0, 5.0), grid("text", 32, load_model_grid(tsize, tvox, 32)))  # Text
     none64 = grid("none64", 64, np.full(64 ** 3, NONE, np.uint8))
     # CreateBridge({0, 0, 0}) (enterOffset {0}, door GLASS)
