@@ -40,6 +40,7 @@
  *                           (renderer.cpp:628, 2190)
  *   vpx_grid_generate_noise  Scene::GenerateSomeNoise    template/scene.cpp:226-282 (renderer.cpp:2883-2898)
  *                            Scene::GenerateSomeSmoke    template/scene.cpp:285-356 (renderer.cpp:626, 2174)
+ *   vpx_grid_brush        Scene::Set over a sphere / box   template/scene.h (Set), edits of a few voxels
  *   vpx_grid_read_box     Scene::grid read back (debug)  template/scene.h:258
  *   vpx_set_volumes       Renderer::voxelVolumes      renderer.h:211
  *   vpx_set_materials     Renderer::materials         renderer.h:190, MaterialSetUp renderer.cpp:357-443
@@ -62,6 +63,7 @@
  *   vpx_model_palette_materials  LoadModel's palette override   template/scene.cpp:516-520
  *   vpx_noise_generate_host  the two generators' loops          template/scene.cpp:226-356
  *   vpx_perlin3              the noise field (this project's definition, DESIGN parity decision 9)
+ *   vpx_brush_apply_host     vpx_grid_brush's cells on a host grid
  */
 #ifndef VPX_H_
 #define VPX_H_
@@ -365,6 +367,42 @@ typedef struct vpx_noise_result {    /* 16 bytes */
    be had.  Like every world edit the call waits for the frames in flight. */
 int vpx_grid_generate_noise(vpx_ctx* ctx, uint32_t grid_id, uint32_t n, const vpx_noise_gen* in,
                             vpx_noise_result* out /* may be NULL */);
+#define VPX_BRUSH_SPHERE 0u  /* cells with dx*dx + dy*dy + dz*dz <= r2 (int64), d = cell - center */
+#define VPX_BRUSH_BOX    1u  /* cells with lo <= cell <= hi per axis */
+typedef struct vpx_brush {           /* 48 bytes */
+    uint32_t shape;                  /* VPX_BRUSH_* */
+    int32_t  center[3];              /* SPHERE; may lie outside the grid */
+    uint32_t r2;                     /* SPHERE: squared radius in cells */
+    int32_t  lo[3], hi[3];           /* BOX, inclusive; clipped to the grid; lo > hi on an axis: empty */
+    uint8_t  value;                  /* byte written; 255 (NONE) digs */
+    uint8_t  match_lo, match_hi;     /* only cells whose current byte m has match_lo <= m <= match_hi are
+                                        written: 0..255 all, 255..255 place into empty cells only,
+                                        0..254 repaint solid only */
+    uint8_t  reserved;               /* 0 */
+} vpx_brush;
+typedef struct vpx_brush_result {    /* 16 bytes */
+    uint64_t changed;                /* cells whose byte changed, over all brushes of the call */
+    uint32_t flipped;                /* 4^3 bricks whose emptiness changed (0: no distance-field work was needed) */
+    uint32_t reserved;
+} vpx_brush_result;
+/* Device-side edit: `count` (1..256) brushes applied in order, one launch each over the brush's
+   clipped bounding box, so a later brush's filter sees the bytes an earlier one left; all
+   arithmetic is integer.  Then ONE region-local refresh of the occupancy levels and the distance
+   field for the whole call (DESIGN §4 "Brush edits"): the cell masks of the touched bricks, and
+   when a brick's emptiness flipped, only the distance-field bytes, lengths and widths that the
+   flipped bricks can reach — the words a full rebuild would leave, bit for bit.  The call
+   allocates nothing (its few hundred bytes of scratch come with the context's first brush call).
+   VPX_E_INVALID: brushes == NULL, count outside 1..256, unknown shape, reserved != 0,
+   match_lo > match_hi, unknown grid.  Like every world edit the call waits for the frames in
+   flight; a device set applies it to every member.  Picking the cell from a vpx_hit is the
+   host's business. */
+int vpx_grid_brush(vpx_ctx* ctx, uint32_t grid_id, const vpx_brush* brushes, uint32_t count,
+                   vpx_brush_result* out /* may be NULL */);
+/* The same brushes on a host grid of n^3 bytes (host only, the code the device runs);
+   `flipped` from the host level builder before and after.  VPX_E_INVALID as above, and for
+   cells == NULL or n outside vpx_upload_grid's range. */
+int vpx_brush_apply_host(uint8_t* cells, uint32_t n, const vpx_brush* brushes, uint32_t count,
+                         vpx_brush_result* out /* may be NULL */);
 /* Debug read-back of a box of cells, host bytes x fastest: the inverse of vpx_grid_write_box
    (a device set reads its first member). */
 int vpx_grid_read_box(vpx_ctx* ctx, uint32_t grid_id, uint8_t* dst, uint32_t x0, uint32_t y0, uint32_t z0,
@@ -377,6 +415,10 @@ int vpx_grid_checksum(vpx_ctx* ctx, uint32_t grid_id, uint64_t* out);
 int vpx_grid_wide_planes(vpx_ctx* ctx, uint32_t grid_id, uint32_t* out, uint64_t count);
 /* The same words' low halves, k | L << 8 (GridView::dfa). */
 int vpx_grid_axis_planes(vpx_ctx* ctx, uint32_t grid_id, uint16_t* out, uint64_t count);
+/* Debug read-back of the mask levels (GridView::l1 for level 1, l2 for level 2): `count` 64-bit
+   words from the first on, at most 64 * ceil(ceil(N / 4) / 4)^3 (level 1) or
+   64 * ceil(ceil(ceil(N / 4) / 4) / 4)^3 (level 2).  VPX_E_INVALID for another level. */
+int vpx_grid_level_words(vpx_ctx* ctx, uint32_t grid_id, uint32_t level, uint64_t* out, uint64_t count);
 int vpx_set_volumes(vpx_ctx* ctx, const vpx_volume* volumes, uint32_t count);
 int vpx_set_materials(vpx_ctx* ctx, const vpx_material* materials, uint32_t count);
 int vpx_set_lights(vpx_ctx* ctx,

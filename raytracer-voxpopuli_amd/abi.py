@@ -147,6 +147,19 @@ def noise_gen(mode=GEN_NOISE, frequency=0.03, seed=0x12345678):
     return NoiseGen(int(mode), float(frequency), int(seed) & 0xFFFFFFFF, 0)
 
 
+BRUSH_SPHERE, BRUSH_BOX = 0, 1  # VPX_BRUSH_*
+
+
+class Brush(C.Structure):  # vpx_brush: one sphere or box of cells, the byte written and the filter (vpx_grid_brush)
+    _fields_ = [("shape", C.c_uint32), ("center", C.c_int32 * 3), ("r2", C.c_uint32), ("lo", C.c_int32 * 3),
+                ("hi", C.c_int32 * 3), ("value", C.c_uint8), ("match_lo", C.c_uint8), ("match_hi", C.c_uint8),
+                ("reserved", C.c_uint8)]
+
+
+class BrushResult(C.Structure):  # vpx_brush_result: cells changed, bricks whose emptiness flipped
+    _fields_ = [("changed", C.c_uint64), ("flipped", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class PrevCamera(C.Structure):
     _fields_ = [("cam_pos", f3), ("left_normal", f3), ("right_normal", f3), ("top_normal", f3),
                 ("bottom_normal", f3), ("pad", C.c_float)]
@@ -174,7 +187,7 @@ STAGES = ("primary", "shade", "shadow", "resolve", "bounce", "finish", "frame", 
 STRUCT_SIZES = {PrevCamera: 64, Profile: 160, Volume: 160, Material: 32, PointLight: 24, SpotLight: 40, AreaLight: 32, DirLight: 24,
                 Sphere: 32, Triangle: 64, Camera: 80, FrameParams: 48, Ray: 32, Hit: 32, Stats: 40,
                 BvhTri: 36, BvhNode: 32, PlayerLight: 24, RayProbe: 16, RayFilter: 16, ModelLoad: 40, ModelResult: 16,
-                NoiseGen: 16, NoiseResult: 16}
+                NoiseGen: 16, NoiseResult: 16, Brush: 48, BrushResult: 16}
 
 
 def np_dtype(struct):
@@ -279,6 +292,9 @@ SIGNATURES = {
     "vpx_grid_generate_noise": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(NoiseGen), C.POINTER(NoiseResult)]),
     "vpx_noise_generate_host": (C.c_int, [C.c_uint32, C.POINTER(NoiseGen), C.c_void_p, C.POINTER(NoiseResult)]),
     "vpx_perlin3": (C.c_float, [C.c_int32, C.c_float, C.c_float, C.c_float]),
+    "vpx_grid_brush": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(Brush), C.c_uint32, C.POINTER(BrushResult)]),
+    "vpx_brush_apply_host": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(Brush), C.c_uint32, C.POINTER(BrushResult)]),
+    "vpx_grid_level_words": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64]),
 }
 
 _LIB = None

@@ -122,6 +122,15 @@ class Context:
         self._chk(self.lib.vpx_grid_emissive_sphere(self.h, grid_id, int(mat), float(radius)),
                   "vpx_grid_emissive_sphere")
 
+    def grid_brush(self, grid_id, brushes):
+        """Device-side edit (vpx_grid_brush): a list of abi.Brush (scene.sphere_brush / box_brush)
+        applied in order, then one region-local refresh of the levels.  Returns the
+        abi.BrushResult: cells changed, bricks whose emptiness flipped."""
+        arr = (abi.Brush * max(1, len(brushes)))(*brushes)
+        res = abi.BrushResult()
+        self._chk(self.lib.vpx_grid_brush(self.h, grid_id, arr, len(brushes), C.byref(res)), "vpx_grid_brush")
+        return res
+
     def model_upload(self, model_id, size, voxels):
         """A resident model (vpx_model_upload): ogt_vox's voxel_data as scene.load_model returns
         it, size = (sx, sy, sz); voxels None removes it."""
@@ -186,6 +195,17 @@ class Context:
         out = np.zeros((24, 64 * nb2 ** 3), np.uint32)
         self._chk(self.lib.vpx_grid_wide_planes(self.h, grid_id, out.ctypes.data_as(C.c_void_p), out.size),
                   "vpx_grid_wide_planes")
+        return out
+
+    def grid_level_words(self, grid_id, n, level):
+        """The mask level 1 (bricks; an empty brick's word holds its distance-field bytes) or 2
+        (macros) of an n^3 grid (debug read-back): uint64 words in blocked order."""
+        nb = ((n + 3) // 4 + 3) // 4
+        if level == 2:
+            nb = (nb + 3) // 4
+        out = np.zeros(64 * nb ** 3, np.uint64)
+        self._chk(self.lib.vpx_grid_level_words(self.h, grid_id, int(level), out.ctypes.data_as(C.c_void_p), out.size),
+                  "vpx_grid_level_words")
         return out
 
     # ---------------------------------------------------------------- hot path

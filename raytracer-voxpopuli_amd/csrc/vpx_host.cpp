@@ -13,6 +13,8 @@
 #include "../../include/vpx.h"
 #include "vpx_model.hpp"
 #include "vpx_noise.hpp"
+#include "vpx_brush.hpp"
+#include "vpx_skip.hpp"
 
 namespace {
 
@@ -257,6 +259,7 @@ static_assert(sizeof(vpx_player_light) == 24 && sizeof(vpx_ray_probe) == 16, "pl
 static_assert(sizeof(vpx_ray_filter) == 16, "ray filter layout");
 static_assert(sizeof(vpx_model_load) == 40 && sizeof(vpx_model_result) == 16, "model load layout");
 static_assert(sizeof(vpx_noise_gen) == 16 && sizeof(vpx_noise_result) == 16, "noise generator layout");
+static_assert(sizeof(vpx_brush) == 48 && sizeof(vpx_brush_result) == 16, "brush layout");
 static_assert(sizeof(vpx_area_light) == 32 && sizeof(vpx_dir_light) == 24, "light layout");
 static_assert(sizeof(vpx_sphere) == 32 && sizeof(vpx_triangle) == 64, "shape layout");
 static_assert(sizeof(vpx_camera) == 80 && sizeof(vpx_frame_params) == 48, "camera/frame layout");
@@ -571,5 +574,29 @@ int vpx_noise_generate_host(uint32_t n, const vpx_noise_gen* in, uint8_t* cells,
 }
 
 float vpx_perlin3(int32_t seed, float x, float y, float z) { return vpx::noise::perlin3(seed, x, y, z); }
+
+}  // extern "C"
+
+// ------------------------------------------------------------------ brush edits
+// vpx_grid_brush's cells on the host, through the tests the device runs (vpx_brush.hpp); the
+// flipped bricks from the host level builder's l2 before and after.
+extern "C" {
+
+int vpx_brush_apply_host(uint8_t* cells, uint32_t n, const vpx_brush* brushes, uint32_t count, vpx_brush_result* out) {
+    if (!cells || n == 0 || n > 4096 || vpx::brush::check_brushes(brushes, count)) return VPX_E_INVALID;
+#if !defined(__HIP_DEVICE_COMPILE__)  // the host builders exist in the host pass only
+    const uint32_t nb1 = (n + 3) / 4, nb2 = (nb1 + 3) / 4, nb3 = (nb2 + 3) / 4;
+    std::vector<uint64_t> l1(64ull * nb2 * nb2 * nb2), before(64ull * nb3 * nb3 * nb3), after(before.size());
+    if (out) vpx::skip::build_masks_host(cells, n, l1.data(), before.data());
+    vpx_brush_result res{};
+    for (uint32_t i = 0; i < count; ++i) res.changed += vpx::brush::apply_host(cells, n, brushes[i]);
+    if (out) {
+        vpx::skip::build_masks_host(cells, n, l1.data(), after.data());
+        for (size_t i = 0; i < after.size(); ++i) res.flipped += (uint32_t)__builtin_popcountll(before[i] ^ after[i]);
+        *out = res;
+    }
+#endif
+    return VPX_OK;
+}
 
 }  // extern "C"

@@ -10,6 +10,9 @@
 //   tiled_world_k / checksum_k    world generator and grid checksum.
 //   model_gather_k / model_random_k   the model loaders' placement (vpx_model.hpp).
 //   smoke_gen_k / noise_mark_k / noise_scan_k / noise_draw_k   the noise generators (vpx_noise.hpp).
+//   brush_k                       one brush edit (vpx_brush.hpp).
+//   refresh_l1_k / df_mark_k / df_diag_k / df_planes_box_k / axis_box_k / wide_box_k   the
+//                                 region-local level refresh after an edit (refresh_levels).
 #include <hip/hip_runtime.h>
 #include <hip/hip_gl_interop.h>
 #include <rccl/rccl.h>
@@ -27,6 +30,7 @@
 #include "vpx_wavefront.hpp"
 #include "vpx_model.hpp"
 #include "vpx_noise.hpp"
+#include "vpx_brush.hpp"
 
 using namespace vpx;
 
@@ -608,43 +612,6 @@ __global__ void build_up_k(const uint64_t* __restrict__ child, uint32_t np, uint
     }
 }
 
-// Region rebuild after an edit: the l1 words of bricks [b0, b0 + cnt) (per axis), then
-// the l2 / l3 words of their parents.  Same words as build_l1_k / build_up_k compute.
-__global__ void build_l1_box_k(const uint8_t* __restrict__ cells, uint32_t n, uint32_t nb2, uint64_t* __restrict__ l1,
-                               uint32_t bx0, uint32_t by0, uint32_t bz0, uint32_t cx, uint32_t cy, uint32_t cz) {
-    const uint64_t total = (uint64_t)cx * cy * cz;
-    const uint64_t n64 = n;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (uint64_t)gridDim.x * blockDim.x) {
-        const uint32_t bx = bx0 + (uint32_t)(i % cx), by = by0 + (uint32_t)((i / cx) % cy),
-                       bz = bz0 + (uint32_t)(i / ((uint64_t)cx * cy));
-        uint64_t m = 0;
-        for (uint32_t lz = 0; lz < 4; ++lz)
-            for (uint32_t ly = 0; ly < 4; ++ly) {
-                const uint32_t y = by * 4 + ly, z = bz * 4 + lz;
-                if (y >= n || z >= n) continue;
-                const uint8_t* row = cells + (uint64_t)y * n64 + (uint64_t)z * n64 * n64;
-                for (uint32_t lx = 0; lx < 4; ++lx) {
-                    const uint32_t x = bx * 4 + lx;
-                    if (x < n && row[x] != kNone) m |= 1ull << (lx + 4 * ly + 16 * lz);
-                }
-            }
-        l1[skip::blk_index(bx, by, bz, nb2)] = m;
-    }
-}
-
-__global__ void build_up_box_k(const uint64_t* __restrict__ child, uint32_t np, uint32_t ngp, uint64_t* __restrict__ out,
-                               uint32_t px0, uint32_t py0, uint32_t pz0, uint32_t cx, uint32_t cy, uint32_t cz) {
-    const uint64_t total = (uint64_t)cx * cy * cz;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (uint64_t)gridDim.x * blockDim.x) {
-        const uint32_t px = px0 + (uint32_t)(i % cx), py = py0 + (uint32_t)((i / cx) % cy),
-                       pz = pz0 + (uint32_t)(i / ((uint64_t)cx * cy));
-        const uint64_t* c = child + (((uint64_t)pz * np + py) * np + px) * 64;
-        uint64_t m = 0;
-        for (uint32_t j = 0; j < 64; ++j) m |= (c[j] != 0ull ? 1ull : 0ull) << j;
-        out[skip::blk_index(px, py, pz, ngp)] = m;
-    }
-}
-
 // One plane fx + fy + fz = s of the distance-field sweep (build_df), thread = (fx, fy,
 // octant o); (fx, fy, fz) are brick coordinates flipped so that octant o's "ahead" is +1.
 // Reads bytes o of the words on planes s+1..s+3 (earlier launches), writes plane s.
@@ -731,6 +698,253 @@ __global__ void build_wide_k(uint16_t* dfh, uint32_t nb1, uint32_t nb2) {
     }
 }
 
+// ------------------------------------------------------- region-local level refresh
+// What an edit leaves to do (refresh_levels, DESIGN §4 "Brush edits"): the stages of the full
+// build over the boxes that the flipped bricks can reach, marked with vpx_skip.hpp's predicates
+// from the words' old values.  The boxes travel between the stages in RefreshDev.
+struct RefreshDev {
+    unsigned long long changed;  // cells the call's brushes changed
+    uint32_t flipped, pad;       // bricks whose emptiness flipped
+    skip::Box3 E;                // their box
+    skip::Box3 C[8];             // per octant: the cube bytes recomputed (stage 1)
+    skip::Box3 D[24];            // per plane: the low halves recomputed (stage 3)
+};
+struct Boxes8 {
+    skip::Box3 b[8];
+};
+
+__device__ __forceinline__ uint64_t box_dims(const skip::Box3& b, uint32_t c[3]) {
+    const bool none = skip::box_empty(b);
+    for (int q = 0; q < 3; ++q) c[q] = none ? 0u : (uint32_t)(b.hi[q] - b.lo[q] + 1);
+    return (uint64_t)c[0] * c[1] * c[2];
+}
+__device__ __forceinline__ void box_brick(const skip::Box3& b, const uint32_t c[3], uint64_t i, uint32_t p[3]) {
+    p[0] = (uint32_t)b.lo[0] + (uint32_t)(i % c[0]);
+    p[1] = (uint32_t)b.lo[1] + (uint32_t)((i / c[0]) % c[1]);
+    p[2] = (uint32_t)b.lo[2] + (uint32_t)(i / ((uint64_t)c[0] * c[1]));
+}
+// Grow a box in device memory by the bricks p of the lanes with `on`: a reduction over the wave,
+// then at most six atomics from its first lane.  Every lane of the wave must call it.
+__device__ __forceinline__ void wave_box_add(skip::Box3* box, bool on, const uint32_t p[3]) {
+    if (!__any(on)) return;
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+        int32_t lo = on ? (int32_t)p[q] : skip::kBoxNone, hi = on ? (int32_t)p[q] : -1;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            lo = min(lo, __shfl_xor(lo, o, 64));
+            hi = max(hi, __shfl_xor(hi, o, 64));
+        }
+        if ((threadIdx.x & 63) == 0) {
+            atomicMin(&box->lo[q], lo);
+            atomicMax(&box->hi[q], hi);
+        }
+    }
+}
+
+// One brush over its clipped bounding box (cells lo .. lo + c - 1, x fastest), vpx_brush.hpp's
+// tests; the changed cells are counted per wave.
+__global__ __launch_bounds__(256) void brush_k(uint8_t* __restrict__ grid, uint32_t n, vpx_brush b, uint32_t x0, uint32_t y0,
+                                               uint32_t z0, uint32_t cx, uint32_t cy, uint32_t cz, RefreshDev* rd) {
+    const uint64_t total = (uint64_t)cx * cy * cz, n64 = n;
+    for (uint64_t base = (uint64_t)blockIdx.x * blockDim.x; base < total; base += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t i = base + threadIdx.x;
+        bool ch = false;
+        if (i < total) {
+            const uint32_t x = x0 + (uint32_t)(i % cx), y = y0 + (uint32_t)((i / cx) % cy), z = z0 + (uint32_t)(i / ((uint64_t)cx * cy));
+            uint8_t* cell = grid + (x + y * n64 + z * n64 * n64);
+            ch = brush::in_shape(b, x, y, z) && brush::writes(b, *cell);
+            if (ch) *cell = b.value;
+        }
+        const uint64_t m = __ballot(ch);
+        if (m && (threadIdx.x & 63) == 0) atomicAdd(&rd->changed, (unsigned long long)__popcll(m));
+    }
+}
+
+// Stage 0: the cell masks of the bricks [b0, b0 + c) from the edited cells, and l2's bits.  The
+// l1 word of an empty brick holds its distance-field bytes: a brick that stays empty keeps them,
+// one that empties gets 0 until stage 1 (it lies in E).  Flips are counted and boxed in rd.
+__global__ __launch_bounds__(256) void refresh_l1_k(const uint8_t* __restrict__ cells, uint32_t n, uint32_t nb2, uint32_t nb3,
+                                                    uint64_t* __restrict__ l1, uint64_t* l2, uint32_t bx0, uint32_t by0, uint32_t bz0,
+                                                    uint32_t cx, uint32_t cy, uint32_t cz, RefreshDev* rd) {
+    const uint64_t total = (uint64_t)cx * cy * cz, n64 = n;
+    for (uint64_t base = (uint64_t)blockIdx.x * blockDim.x; base < total; base += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t i = base + threadIdx.x;
+        bool flip = false;
+        uint32_t p[3] = {0u, 0u, 0u};
+        if (i < total) {
+            p[0] = bx0 + (uint32_t)(i % cx), p[1] = by0 + (uint32_t)((i / cx) % cy), p[2] = bz0 + (uint32_t)(i / ((uint64_t)cx * cy));
+            uint64_t m = 0;
+            for (uint32_t lz = 0; lz < 4; ++lz)
+                for (uint32_t ly = 0; ly < 4; ++ly) {
+                    const uint32_t y = p[1] * 4 + ly, z = p[2] * 4 + lz;
+                    if (y >= n || z >= n) continue;
+                    const uint8_t* row = cells + (uint64_t)y * n64 + (uint64_t)z * n64 * n64;
+                    for (uint32_t lx = 0; lx < 4; ++lx) {
+                        const uint32_t x = p[0] * 4 + lx;
+                        if (x < n && row[x] != kNone) m |= 1ull << (lx + 4 * ly + 16 * lz);
+                    }
+                }
+            unsigned long long* w2 = (unsigned long long*)l2 + skip::blk_index(p[0] >> 2, p[1] >> 2, p[2] >> 2, nb3);
+            const unsigned long long bit = 1ull << ((p[0] & 3u) | ((p[1] & 3u) << 2) | ((p[2] & 3u) << 4));
+            const bool was = *w2 & bit, is = m != 0ull;
+            if (is || was) l1[skip::blk_index(p[0], p[1], p[2], nb2)] = m;
+            flip = is != was;
+            if (flip) atomicXor(w2, bit);  // other lanes own the word's other bits
+        }
+        const uint64_t fm = __ballot(flip);
+        if (fm && (threadIdx.x & 63) == 0) atomicAdd(&rd->flipped, (uint32_t)__popcll(fm));
+        wave_box_add(&rd->E, flip, p);
+    }
+}
+
+// Stage 1, marking: blockIdx.y = octant o; the candidates cand.b[o] (E grown backward by the
+// reach) test their old cube byte, which the octant planes still hold, and box the marked in rd->C[o].
+__global__ __launch_bounds__(256) void df_mark_k(const uint8_t* __restrict__ dfp, uint64_t plane, uint32_t nb2, Boxes8 cand,
+                                                 skip::Box3 E, RefreshDev* rd) {
+    const uint32_t o = blockIdx.y;
+    uint32_t c[3];
+    const uint64_t total = box_dims(cand.b[o], c);
+    for (uint64_t base = (uint64_t)blockIdx.x * blockDim.x; base < total; base += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t i = base + threadIdx.x;
+        bool dirty = false;
+        uint32_t p[3] = {0u, 0u, 0u};
+        if (i < total) {
+            box_brick(cand.b[o], c, i, p);
+            dirty = skip::cube_dirty(p, o, dfp[o * plane + skip::blk_index(p[0], p[1], p[2], nb2)], E);
+        }
+        wave_box_add(&rd->C[o], dirty, p);
+    }
+}
+
+// Stage 1, sweep: one anti-diagonal fx + fy + fz = s of every octant's box C.b[o] (blockIdx.y =
+// o), f counted from the box's corner furthest ahead, as df_plane_k does for the whole grid: the
+// neighbours ahead lie on earlier diagonals or outside the box, where no byte changes.
+__global__ __launch_bounds__(256) void df_diag_k(uint8_t* l1b, const uint64_t* __restrict__ l2, uint32_t nb1, uint32_t nb2,
+                                                 uint32_t nb3, Boxes8 C, uint32_t s) {
+    const uint32_t o = blockIdx.y;
+    uint32_t c[3];
+    const uint64_t q = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (!box_dims(C.b[o], c)) return;
+    const uint32_t fx = (uint32_t)(q % c[0]);
+    const uint64_t fy = q / c[0];
+    if (fy >= c[1] || fx + fy > s || s - fx - fy >= c[2]) return;
+    const uint32_t fz = s - fx - (uint32_t)fy;
+    const skip::Box3& b = C.b[o];
+    const uint32_t x = (o & 1u) ? (uint32_t)b.lo[0] + fx : (uint32_t)b.hi[0] - fx, y = (o & 2u) ? (uint32_t)b.lo[1] + (uint32_t)fy : (uint32_t)b.hi[1] - (uint32_t)fy,
+                   z = (o & 4u) ? (uint32_t)b.lo[2] + fz : (uint32_t)b.hi[2] - fz;
+    auto occ = [&](uint32_t a, uint32_t bb, uint32_t cc) -> bool {
+        return (l2[skip::blk_index(a >> 2, bb >> 2, cc >> 2, nb3)] >> ((a & 3u) | ((bb & 3u) << 2) | ((cc & 3u) << 4))) & 1ull;
+    };
+    if (occ(x, y, z)) return;
+    auto get = [&](uint32_t a, uint32_t bb, uint32_t cc, uint32_t oo) -> uint32_t {
+        return l1b[(size_t)skip::blk_index(a, bb, cc, nb2) * 8 + oo];
+    };
+    l1b[(size_t)skip::blk_index(x, y, z, nb2) * 8 + o] = skip::df_value(x, y, z, o, nb1, occ, get);
+}
+
+// Stage 2: build_planes_k limited to the boxes: byte o of the bricks of C.b[o] into plane o, 0
+// for an occupied brick (one that filled included).
+__global__ __launch_bounds__(256) void df_planes_box_k(const uint8_t* __restrict__ l1b, const uint64_t* __restrict__ l2, uint32_t nb2,
+                                                       uint32_t nb3, uint8_t* __restrict__ dfp, uint64_t plane, Boxes8 C) {
+    const uint32_t o = blockIdx.y;
+    uint32_t c[3];
+    const uint64_t total = box_dims(C.b[o], c);
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (uint64_t)gridDim.x * blockDim.x) {
+        uint32_t p[3];
+        box_brick(C.b[o], c, i, p);
+        const bool occ = (l2[skip::blk_index(p[0] >> 2, p[1] >> 2, p[2] >> 2, nb3)] >> ((p[0] & 3u) | ((p[1] & 3u) << 2) | ((p[2] & 3u) << 4))) & 1ull;
+        const uint32_t s = skip::blk_index(p[0], p[1], p[2], nb2);
+        dfp[o * plane + s] = occ ? (uint8_t)0 : l1b[(size_t)s * 8 + o];
+    }
+}
+
+// Stage 3: blockIdx.y = plane (o, a); the candidates are C.b[o] grown backward along a.  A
+// thread tests its own old word (skip::len_dirty), recomputes the low half with axis_len from the
+// refreshed octant plane and boxes what it recomputed in rd->D.  A brick that filled gets 0.
+__global__ __launch_bounds__(256) void axis_box_k(const uint8_t* __restrict__ dfp, uint32_t nb1, uint32_t nb2, uint32_t* dfw, Boxes8 C,
+                                                  RefreshDev* rd) {
+    const uint32_t oa = blockIdx.y, o = oa / 3u, a = oa - o * 3u;
+    const uint64_t plane = (uint64_t)nb2 * nb2 * nb2 * 64;
+    uint32_t ext[3] = {1u, 1u, 1u};
+    ext[a] = skip::kReach;
+    const skip::Box3 cand = skip::box_behind(C.b[o], o, ext, nb1);
+    uint32_t c[3];
+    const uint64_t total = box_dims(cand, c);
+    const uint8_t* pl = dfp + (uint64_t)o * plane;
+    auto cube = [&](uint32_t x, uint32_t y, uint32_t z) -> uint32_t { return pl[skip::blk_index(x, y, z, nb2)]; };
+    for (uint64_t base = (uint64_t)blockIdx.x * blockDim.x; base < total; base += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t i = base + threadIdx.x;
+        bool dirty = false;
+        uint32_t p[3] = {0u, 0u, 0u};
+        if (i < total) {
+            box_brick(cand, c, i, p);
+            const uint32_t s = skip::blk_index(p[0], p[1], p[2], nb2);
+            uint32_t* w = dfw + (uint64_t)oa * plane + s;
+            const uint32_t old = *w;
+            dirty = skip::len_dirty(p, o, a, old & 255u, (old >> 8) & 255u, C.b[o]);
+            if (dirty) {
+                const uint32_t k = pl[s];
+                if (k) *(uint16_t*)w = (uint16_t)(k | skip::axis_len(p[0], p[1], p[2], o, a, k, nb1, cube) << 8);
+                else *w = 0u;
+            }
+        }
+        wave_box_add(&rd->D[oa], dirty, p);
+    }
+}
+
+// Stage 4: blockIdx.y = plane (o, a); the candidates are the cone behind rd->D[oa], read from
+// device memory (stage 3 left it there), taken macro by macro: a wave reads the 64 contiguous
+// words of one 4^3 group of bricks, a workgroup kWideMacros of them per round.  A thread tests
+// its own word (skip::wid_dirty: the low half is final, and old outside D; the high half is
+// still the old one) and queues it in LDS when it is dirty; the workgroup then recomputes the
+// queued words' widths with axis_wids, one per thread, so the few dirty words of a sparse cone
+// do not each hold a wave.  As in build_wide_k other threads read low halves while high halves
+// are written, so both sides go through 16-bit accesses.  Bricks of a macro outside the cone
+// fail the test, and padding bricks hold 0.
+constexpr uint32_t kWideMacros = 32;
+__global__ __launch_bounds__(256) void wide_box_k(uint16_t* dfh, uint32_t nb1, uint32_t nb2, const RefreshDev* rd) {
+    __shared__ uint32_t queue[kWideMacros * 64];
+    __shared__ uint32_t queued;
+    const uint32_t oa = blockIdx.y, o = oa / 3u, a = oa - o * 3u;
+    const uint64_t plane = (uint64_t)nb2 * nb2 * nb2 * 64;
+    const skip::Box3 D = rd->D[oa];
+    if (skip::box_empty(D)) return;
+    const uint32_t reach[3] = {skip::kReach, skip::kReach, skip::kReach};
+    const skip::Box3 cand = skip::box_behind(D, o, reach, nb1);
+    const uint32_t m0[3] = {(uint32_t)cand.lo[0] >> 2, (uint32_t)cand.lo[1] >> 2, (uint32_t)cand.lo[2] >> 2};
+    const uint32_t mc[3] = {((uint32_t)cand.hi[0] >> 2) - m0[0] + 1u, ((uint32_t)cand.hi[1] >> 2) - m0[1] + 1u,
+                            ((uint32_t)cand.hi[2] >> 2) - m0[2] + 1u};
+    const uint32_t macros = mc[0] * mc[1] * mc[2], rounds = (macros + kWideMacros - 1u) / kWideMacros;
+    uint16_t* pl = dfh + 2 * (uint64_t)oa * plane;
+    auto word = [&](uint32_t x, uint32_t y, uint32_t z) -> uint32_t { return pl[2 * (uint64_t)skip::blk_index(x, y, z, nb2)]; };
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    for (uint32_t r = blockIdx.x; r < rounds; r += gridDim.x) {
+        if (threadIdx.x == 0) queued = 0u;
+        __syncthreads();
+        for (uint32_t j = wave; j < kWideMacros; j += 4u) {
+            const uint32_t mi = r * kWideMacros + j;
+            if (mi >= macros) break;
+            const uint32_t P[3] = {m0[0] + mi % mc[0], m0[1] + (mi / mc[0]) % mc[1], m0[2] + mi / (mc[0] * mc[1])};
+            const uint32_t p[3] = {P[0] * 4u + (lane & 3u), P[1] * 4u + ((lane >> 2) & 3u), P[2] * 4u + (lane >> 4)};
+            const uint32_t s = (((P[2] * nb2 + P[1]) * nb2 + P[0]) << 6) | lane;
+            const uint32_t kl = pl[2 * (uint64_t)s];
+            if (!kl) continue;
+            const uint32_t m = pl[2 * (uint64_t)s + 1];
+            if (skip::wid_dirty(p, o, a, kl & 255u, kl >> 8, m & 255u, m >> 8, D)) queue[atomicAdd(&queued, 1u)] = s;
+        }
+        __syncthreads();
+        for (uint32_t e = threadIdx.x; e < queued; e += blockDim.x) {
+            const uint32_t s = queue[e], parent = s >> 6;
+            const uint32_t x = (parent % nb2) * 4u + (s & 3u), y = ((parent / nb2) % nb2) * 4u + ((s >> 2) & 3u),
+                           z = (parent / (nb2 * nb2)) * 4u + ((s >> 4) & 3u);
+            const uint32_t kl = pl[2 * (uint64_t)s];
+            pl[2 * (uint64_t)s + 1] = (uint16_t)skip::axis_wids(x, y, z, o, a, kl & 255u, kl >> 8, nb1, word);
+        }
+        __syncthreads();
+    }
+}
+
 // Scatter a staged box (x fastest) into the grid.
 __global__ void write_box_k(uint8_t* __restrict__ grid, uint32_t n, const uint8_t* __restrict__ src, uint32_t x0,
                             uint32_t y0, uint32_t z0, uint32_t dx, uint32_t dy, uint32_t dz) {
@@ -804,6 +1018,10 @@ struct vpx_ctx {
     std::vector<ModelBuf> models;
     uint8_t* d_model_aux = nullptr;
     uint8_t* h_plan = nullptr;
+    // the level refresh's record (refresh_begin), allocated with the context's first edit: the
+    // device copy, and pinned [0] its initial state, [1] the read-back
+    RefreshDev* d_refresh = nullptr;
+    RefreshDev* h_refresh = nullptr;
     DevGrid* d_grids = nullptr;
     uint32_t d_grids_cap = 0;
     std::vector<vpx_volume> volumes;
@@ -1626,6 +1844,8 @@ int vpx_destroy(vpx_ctx* c) {
     }
     if (c->d_model_aux) (void)hipFree(c->d_model_aux);
     if (c->h_plan) (void)hipHostFree(c->h_plan);
+    if (c->d_refresh) (void)hipFree(c->d_refresh);
+    if (c->h_refresh) (void)hipHostFree(c->h_refresh);
     void* ptrs[] = {c->d_grids, c->d_volumes, c->d_vbounds, c->d_tlas, c->d_bvh, c->d_materials, c->d_points, c->d_spots, c->d_areas,
                     c->d_spheres, c->d_triangles, c->d_ctr, c->d_sum, c->d_scratch, c->wave.d, c->d_sky, c->d_x86};
     for (void* p : ptrs)
@@ -1818,28 +2038,131 @@ static int build_masks(vpx_ctx* c, uint32_t id) {
     return VPX_OK;
 }
 
-// Refresh the occupancy levels for the macros that hold the cells [x0, x1) x [y0, y1) x
-// [z0, z1) (their bricks' words are recomputed whole, so the l2 words see fresh masks
-// only), then the distance field (an edit can change it far behind the box).
+// The refresh's record, reset on the stream; before the first launch that counts into it.
+static int refresh_begin(vpx_ctx* c) {
+    if (!c->d_refresh) {
+        VPX_HIP(c, hipHostMalloc((void**)&c->h_refresh, 2 * sizeof(RefreshDev)));
+        VPX_HIP(c, hipMalloc(&c->d_refresh, sizeof(RefreshDev)));
+        RefreshDev& init = c->h_refresh[0];
+        std::memset(&init, 0, sizeof(init));
+        init.E = skip::box_none();
+        for (auto& b : init.C) b = skip::box_none();
+        for (auto& b : init.D) b = skip::box_none();
+    }
+    VPX_HIP(c, hipMemcpyAsync(c->d_refresh, &c->h_refresh[0], sizeof(RefreshDev), hipMemcpyHostToDevice, c->stream));
+    return VPX_OK;
+}
+
+// The levels after the cells of `count` boxes (inclusive cell coordinates, inside the grid)
+// changed: the region-local refresh (DESIGN §4 "Brush edits"; the host restatement is
+// skip::refresh_masks_host / refresh_levels_host).  Stage 0 takes one launch per box; where no
+// brick's emptiness flipped the call ends there, after one read-back.  Otherwise: one marking
+// launch and a second read-back (the boxes of stage 1 set the number of launches), one launch
+// per anti-diagonal of the largest box, then one each for the planes, the low halves and the
+// widths.  Ends synchronised, like build_masks.
+static int refresh_levels(vpx_ctx* c, const vpx_ctx::GridBuf& g, const skip::Box3* cells, uint32_t count, vpx_brush_result* res) {
+    RefreshDev* rd = c->d_refresh;
+    RefreshDev& back = c->h_refresh[1];
+    auto blocks = [](uint64_t threads, uint64_t cap) { return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(cap, (threads + 255) / 256)); };
+    auto volume = [](const skip::Box3& b) -> uint64_t {
+        return skip::box_empty(b) ? (uint64_t)0 : (uint64_t)(b.hi[0] - b.lo[0] + 1) * (uint64_t)(b.hi[1] - b.lo[1] + 1) * (uint64_t)(b.hi[2] - b.lo[2] + 1);
+    };
+    for (uint32_t i = 0; i < count; ++i) {
+        const uint32_t b0[3] = {(uint32_t)cells[i].lo[0] >> 2, (uint32_t)cells[i].lo[1] >> 2, (uint32_t)cells[i].lo[2] >> 2};
+        const uint32_t cx = ((uint32_t)cells[i].hi[0] >> 2) - b0[0] + 1, cy = ((uint32_t)cells[i].hi[1] >> 2) - b0[1] + 1,
+                       cz = ((uint32_t)cells[i].hi[2] >> 2) - b0[2] + 1;
+        hipLaunchKernelGGL(refresh_l1_k, dim3(blocks((uint64_t)cx * cy * cz, 4096)), dim3(256), 0, c->stream, g.ptr, g.n, g.nb2, g.nb3,
+                           g.l1, g.l2, b0[0], b0[1], b0[2], cx, cy, cz, rd);
+        VPX_HIP(c, hipGetLastError());
+    }
+    VPX_HIP(c, hipMemcpyAsync(&back, rd, offsetof(RefreshDev, C), hipMemcpyDeviceToHost, c->stream));
+    VPX_HIP(c, hipStreamSynchronize(c->stream));
+    if (res) res->changed = back.changed, res->flipped = back.flipped;
+    if (!back.flipped) return VPX_OK;  // only cell masks changed: no distance-field word can
+
+    const skip::Box3 E = back.E;
+    const uint32_t reach[3] = {skip::kReach, skip::kReach, skip::kReach};
+    const uint64_t plane = g.plane();
+    uint32_t* dfw = (uint32_t*)(g.dfp + 8 * plane);
+    Boxes8 cand;
+    uint64_t most = 0;
+    for (uint32_t o = 0; o < 8; ++o) {
+        cand.b[o] = skip::box_behind(E, o, reach, g.nb1);
+        most = std::max(most, volume(cand.b[o]));
+    }
+    hipLaunchKernelGGL(df_mark_k, dim3(blocks(most, 2048), 8), dim3(256), 0, c->stream, (const uint8_t*)g.dfp, plane, g.nb2, cand, E, rd);
+    VPX_HIP(c, hipGetLastError());
+    VPX_HIP(c, hipMemcpyAsync(back.C, (const uint8_t*)rd + offsetof(RefreshDev, C), sizeof(back.C), hipMemcpyDeviceToHost, c->stream));
+    VPX_HIP(c, hipStreamSynchronize(c->stream));
+
+    Boxes8 C;
+    uint32_t diagonals = 0;
+    uint64_t face = 0, most_c = 0, most_a = 0, most_w = 0;
+    for (uint32_t o = 0; o < 8; ++o) {
+        const skip::Box3& b = C.b[o] = back.C[o];
+        if (skip::box_empty(b)) continue;
+        const uint32_t cx = (uint32_t)(b.hi[0] - b.lo[0] + 1), cy = (uint32_t)(b.hi[1] - b.lo[1] + 1), cz = (uint32_t)(b.hi[2] - b.lo[2] + 1);
+        diagonals = std::max(diagonals, cx + cy + cz - 2);
+        face = std::max<uint64_t>(face, (uint64_t)cx * cy);
+        most_c = std::max(most_c, volume(b));
+        for (uint32_t a = 0; a < 3; ++a) {  // stage 3's candidates, and the cone behind them that bounds stage 4's
+            uint32_t ext[3] = {1u, 1u, 1u};
+            ext[a] = skip::kReach;
+            const skip::Box3 ca = skip::box_behind(b, o, ext, g.nb1);
+            most_a = std::max(most_a, volume(ca));
+            most_w = std::max(most_w, volume(skip::box_behind(ca, o, reach, g.nb1)));
+        }
+    }
+    for (uint32_t s = 0; s < diagonals; ++s) {
+        hipLaunchKernelGGL(df_diag_k, dim3(blocks(face, ~0ull), 8), dim3(256), 0, c->stream, (uint8_t*)g.l1, g.l2, g.nb1, g.nb2, g.nb3, C, s);
+        VPX_HIP(c, hipGetLastError());
+    }
+    hipLaunchKernelGGL(df_planes_box_k, dim3(blocks(most_c, 2048), 8), dim3(256), 0, c->stream, (const uint8_t*)g.l1, g.l2, g.nb2, g.nb3,
+                       g.dfp, plane, C);
+    VPX_HIP(c, hipGetLastError());
+    hipLaunchKernelGGL(axis_box_k, dim3(blocks(most_a, 1024), 24), dim3(256), 0, c->stream, (const uint8_t*)g.dfp, g.nb1, g.nb2, dfw, C, rd);
+    VPX_HIP(c, hipGetLastError());
+    hipLaunchKernelGGL(wide_box_k, dim3(blocks(most_w / 8, 4096), 24), dim3(256), 0, c->stream, (uint16_t*)dfw, g.nb1, g.nb2,
+                       (const RefreshDev*)rd);
+    VPX_HIP(c, hipGetLastError());
+    VPX_HIP(c, sync_all(c));
+    return VPX_OK;
+}
+
+// After an edit of the cells [x0, x1) x [y0, y1) x [z0, z1): the cell masks of their bricks,
+// then the distance field where the edit can reach it (refresh_levels).  The loaders, the
+// generators, vpx_upload_grid and vpx_grid_fill rebuild everything (build_masks).
 static int build_masks_box(vpx_ctx* c, uint32_t id, uint32_t x0, uint32_t y0, uint32_t z0, uint32_t x1, uint32_t y1,
                            uint32_t z1) {
-    auto& g = c->grids[id];
     if (x0 >= x1 || y0 >= y1 || z0 >= z1) return VPX_OK;
-    uint32_t lo[3] = {(x0 >> 4) * 4, (y0 >> 4) * 4, (z0 >> 4) * 4};
-    uint32_t hi[3] = {((x1 - 1) >> 4) * 4 + 3, ((y1 - 1) >> 4) * 4 + 3, ((z1 - 1) >> 4) * 4 + 3};
-    for (int k = 0; k < 3; ++k) hi[k] = hi[k] < g.nb1 - 1 ? hi[k] : g.nb1 - 1;
-    auto blocks = [](uint64_t a, uint64_t b, uint64_t cc) { return (unsigned)std::min<uint64_t>(4096, (a * b * cc + 255) / 256); };
-    hipLaunchKernelGGL(build_l1_box_k, dim3(blocks(hi[0] - lo[0] + 1, hi[1] - lo[1] + 1, hi[2] - lo[2] + 1)), dim3(256), 0,
-                       c->stream, g.ptr, g.n, g.nb2, g.l1, lo[0], lo[1], lo[2], hi[0] - lo[0] + 1, hi[1] - lo[1] + 1,
-                       hi[2] - lo[2] + 1);
-    VPX_HIP(c, hipGetLastError());
-    for (int k = 0; k < 3; ++k) lo[k] >>= 2, hi[k] >>= 2;  // macros
-    hipLaunchKernelGGL(build_up_box_k, dim3(blocks(hi[0] - lo[0] + 1, hi[1] - lo[1] + 1, hi[2] - lo[2] + 1)), dim3(256), 0,
-                       c->stream, g.l1, g.nb2, g.nb3, g.l2, lo[0], lo[1], lo[2], hi[0] - lo[0] + 1, hi[1] - lo[1] + 1,
-                       hi[2] - lo[2] + 1);
-    VPX_HIP(c, hipGetLastError());
-    if (int r = build_df(c, g)) return r;
-    VPX_HIP(c, sync_all(c));
+    if (int r = refresh_begin(c)) return r;
+    const skip::Box3 cells{{(int32_t)x0, (int32_t)y0, (int32_t)z0}, {(int32_t)x1 - 1, (int32_t)y1 - 1, (int32_t)z1 - 1}};
+    return refresh_levels(c, c->grids[id], &cells, 1, nullptr);
+}
+
+int vpx_grid_brush(vpx_ctx* c, uint32_t id, const vpx_brush* brushes, uint32_t count, vpx_brush_result* out) {
+    VPX_GROUP_ALL(c, vpx_grid_brush(m_, id, brushes, count, out));
+    if (!c) return VPX_E_INVALID;
+    if (const char* why = brush::check_brushes(brushes, count)) return fail(c, VPX_E_INVALID, why);
+    if (id >= c->grids.size() || !c->grids[id].ptr) return fail(c, VPX_E_INVALID, "unknown grid");
+    auto& g = c->grids[id];
+    VPX_HIP(c, hipSetDevice(c->device));
+    VPX_HIP(c, sync_all(c));  // frames in flight still read the grid
+    if (int r = refresh_begin(c)) return r;
+    skip::Box3 boxes[brush::kMaxBrushes];
+    uint32_t n_boxes = 0;
+    for (uint32_t i = 0; i < count; ++i) {
+        uint32_t lo[3], hi[3];
+        if (!brush::clipped_box(brushes[i], g.n, lo, hi)) continue;
+        const uint32_t cx = hi[0] - lo[0] + 1, cy = hi[1] - lo[1] + 1, cz = hi[2] - lo[2] + 1;
+        hipLaunchKernelGGL(brush_k, dim3((unsigned)std::min<uint64_t>(4096, ((uint64_t)cx * cy * cz + 255) / 256)), dim3(256), 0,
+                           c->stream, g.ptr, g.n, brushes[i], lo[0], lo[1], lo[2], cx, cy, cz, c->d_refresh);
+        VPX_HIP(c, hipGetLastError());
+        boxes[n_boxes++] = skip::Box3{{(int32_t)lo[0], (int32_t)lo[1], (int32_t)lo[2]}, {(int32_t)hi[0], (int32_t)hi[1], (int32_t)hi[2]}};
+    }
+    vpx_brush_result res{};
+    if (int r = refresh_levels(c, g, boxes, n_boxes, &res)) return r;
+    if (out) *out = res;
     return VPX_OK;
 }
 
@@ -2115,6 +2438,19 @@ int vpx_grid_axis_planes(vpx_ctx* c, uint32_t id, uint16_t* out, uint64_t count)
     std::vector<uint32_t> words(count);
     if (int r = vpx_grid_wide_planes(c, id, words.data(), count)) return r;
     for (uint64_t i = 0; i < count; ++i) out[i] = (uint16_t)words[i];
+    return VPX_OK;
+}
+
+int vpx_grid_level_words(vpx_ctx* c, uint32_t id, uint32_t level, uint64_t* out, uint64_t count) {
+    VPX_GROUP_FIRST(c, vpx_grid_level_words(m_, id, level, out, count));
+    if (!c || !out) return fail(c, VPX_E_INVALID, "null argument");
+    if (id >= c->grids.size() || !c->grids[id].ptr) return fail(c, VPX_E_INVALID, "unknown grid");
+    if (level != 1u && level != 2u) return fail(c, VPX_E_INVALID, "level must be 1 or 2");
+    const auto& g = c->grids[id];
+    const uint64_t words = level == 1u ? g.plane() : 64ull * g.nb3 * g.nb3 * g.nb3;
+    if (count > words) return fail(c, VPX_E_INVALID, "more words than the level holds");
+    VPX_HIP(c, hipMemcpyAsync(out, level == 1u ? g.l1 : g.l2, count * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    VPX_HIP(c, sync_all(c));
     return VPX_OK;
 }
 

@@ -1051,6 +1051,83 @@ VPX_HD uint32_t axis_wids(uint32_t x, uint32_t y, uint32_t z, uint32_t o, uint32
     return axis_wid(p, o, a, b, c, k, L, nb1, word) | axis_wid(p, o, a, c, b, k, L, nb1, word) << 8;
 }
 
+// ---------------------------------------------------------------- region-local refresh
+// After an edit the levels are refreshed only where they can change (DESIGN §4 "Brush edits").
+// Every level is a function of the stage below it, so each stage recomputes, with the builders'
+// own df_value / axis_len / axis_wids, a superset of the words that its inputs' changes can
+// reach; the predicates below say which, from a word's OLD value and the box of what changed
+// one stage down.  Boxes are inclusive brick coordinates; lo > hi: empty.
+struct Box3 {
+    int32_t lo[3], hi[3];
+};
+constexpr int32_t kBoxNone = 0x7fffffff;
+VPX_HD Box3 box_none() { return Box3{{kBoxNone, kBoxNone, kBoxNone}, {-1, -1, -1}}; }
+VPX_HD bool box_empty(const Box3& b) { return b.lo[0] > b.hi[0] || b.lo[1] > b.hi[1] || b.lo[2] > b.hi[2]; }
+VPX_HD bool box_has(const Box3& b, const uint32_t p[3]) {
+    return (int32_t)p[0] >= b.lo[0] && (int32_t)p[0] <= b.hi[0] && (int32_t)p[1] >= b.lo[1] && (int32_t)p[1] <= b.hi[1] &&
+           (int32_t)p[2] >= b.lo[2] && (int32_t)p[2] <= b.hi[2];
+}
+VPX_HD void box_add(Box3& b, const uint32_t p[3]) {
+    for (int q = 0; q < 3; ++q) {
+        b.lo[q] = (int32_t)p[q] < b.lo[q] ? (int32_t)p[q] : b.lo[q];
+        b.hi[q] = (int32_t)p[q] > b.hi[q] ? (int32_t)p[q] : b.hi[q];
+    }
+}
+// The bricks p + s_q * i_q, first[q] <= i_q < first[q] + ext[q], s the signs of octant o, meet b.
+VPX_HD bool ahead_meets(const uint32_t p[3], uint32_t o, const uint32_t first[3], const uint32_t ext[3], const Box3& b) {
+    bool hit = true;
+    for (uint32_t q = 0; q < 3; ++q) {
+        const int32_t near = (int32_t)first[q], far = (int32_t)(first[q] + ext[q]) - 1;
+        const bool neg = (o >> q) & 1u;
+        const int32_t l = neg ? (int32_t)p[q] - far : (int32_t)p[q] + near, h = neg ? (int32_t)p[q] - near : (int32_t)p[q] + far;
+        hit = hit && ext[q] != 0u && l <= b.hi[q] && h >= b.lo[q];
+    }
+    return hit;
+}
+// The bricks from which a box of at most ext[q] bricks per axis toward octant o can meet b: b
+// grown backward, clipped to the grid (the candidates of a stage).
+VPX_HD Box3 box_behind(const Box3& b, uint32_t o, const uint32_t ext[3], uint32_t nb1) {
+    Box3 r = b;
+    if (box_empty(b)) return r;
+    for (uint32_t q = 0; q < 3; ++q) {
+        if ((o >> q) & 1u) r.hi[q] = b.hi[q] + (int32_t)ext[q] - 1;
+        else r.lo[q] = b.lo[q] - ((int32_t)ext[q] - 1);
+        r.lo[q] = r.lo[q] < 0 ? 0 : r.lo[q];
+        r.hi[q] = r.hi[q] > (int32_t)nb1 - 1 ? (int32_t)nb1 - 1 : r.hi[q];
+    }
+    return r;
+}
+constexpr uint32_t kReach = 256;  // no cube, length or width reads further ahead than 255 bricks and its own
+// Stage 1: the cube byte k_old (0: occupied) of brick p for octant o can change when bricks in E
+// flip their emptiness.  It falls when a brick of the k_old^3 cube fills, and rises only when
+// every occupied brick of the (k_old + 1)^3 cube empties: either way that cube meets E.
+VPX_HD bool cube_dirty(const uint32_t p[3], uint32_t o, uint32_t k_old, const Box3& E) {
+    const uint32_t first[3] = {0u, 0u, 0u}, ext[3] = {k_old + 1u, k_old + 1u, k_old + 1u};
+    return ahead_meets(p, o, first, ext, E);
+}
+// Stage 3: the low half k | L << 8 of p's word in plane (o, a) can change when the cube bytes
+// inside C did: its own, or one of the bricks p + i e_a, 1 <= i <= L - k + 1, that axis_len read
+// (the run and the brick that ended it).
+VPX_HD bool len_dirty(const uint32_t p[3], uint32_t o, uint32_t a, uint32_t k_old, uint32_t L_old, const Box3& C) {
+    if (box_has(C, p)) return true;
+    uint32_t first[3] = {0u, 0u, 0u}, ext[3] = {1u, 1u, 1u};
+    first[a] = 1u, ext[a] = L_old - k_old + 1u;
+    return ahead_meets(p, o, first, ext, C);
+}
+// Stage 4: the widths Mb | Mc << 8 of p's word can change when low halves inside D did: its own,
+// or one in the two boxes axis_wid read, L x (Mb + 1) x k and L x k x (Mc + 1) (a, b, c; the
+// extra layer is the one that ended the growth).  k, L, Mb, Mc: the word before the refresh.
+VPX_HD bool wid_dirty(const uint32_t p[3], uint32_t o, uint32_t a, uint32_t k, uint32_t L, uint32_t Mb, uint32_t Mc, const Box3& D) {
+    if (box_has(D, p)) return true;
+    if (!k) return false;
+    const uint32_t b = a == 0u ? 1u : 0u, c = a == 2u ? 1u : 2u;
+    const uint32_t first[3] = {0u, 0u, 0u};
+    uint32_t e1[3], e2[3];
+    e1[a] = L, e1[b] = Mb + 1u, e1[c] = k;
+    e2[a] = L, e2[b] = k, e2[c] = Mc + 1u;
+    return ahead_meets(p, o, first, e1, D) || ahead_meets(p, o, first, e2, D);
+}
+
 #if !defined(__HIP_DEVICE_COMPILE__)
 // Host builder of the same levels (tests and tools).  Sizes: l1 nb2^3*64 words, l2
 // nb3^3*64 words (nb1 = ceil(n/4), nb2 = ceil(nb1/4), nb3 = ceil(nb2/4)).
@@ -1145,6 +1222,124 @@ inline void build_wide_planes_host(const uint8_t* dfp, uint32_t n, uint32_t* dfw
                     if (kl) pl[b] = kl | axis_wids(x, y, z, oa / 3u, oa % 3u, kl & 255u, kl >> 8, nb1, word) << 16;
                 }
     }
+}
+
+// The region-local refresh on the host, stage by stage as the device runs it (vpx_kernels.hip
+// refresh_levels), from the same predicates.
+// Stage 0: the l1 cell masks of the bricks T (the bricks an edit touched) from the edited cells,
+// and l2's bits; returns the box E of the bricks whose emptiness flipped and counts them.  An
+// empty brick's l1 word holds its distance-field bytes: one that stays empty keeps them, one
+// that empties gets 0 until stage 1.
+inline Box3 refresh_masks_host(const uint8_t* cells, uint32_t n, const Box3& T, uint64_t* l1, uint64_t* l2, uint32_t* flipped) {
+    const uint32_t nb1 = (n + 3) / 4, nb2 = (nb1 + 3) / 4, nb3 = (nb2 + 3) / 4;
+    Box3 E = box_none();
+    uint32_t flips = 0;
+    if (!box_empty(T))
+        for (uint32_t bz = (uint32_t)T.lo[2]; bz <= (uint32_t)T.hi[2]; ++bz)
+            for (uint32_t by = (uint32_t)T.lo[1]; by <= (uint32_t)T.hi[1]; ++by)
+                for (uint32_t bx = (uint32_t)T.lo[0]; bx <= (uint32_t)T.hi[0]; ++bx) {
+                    uint64_t m = 0;
+                    for (uint32_t l = 0; l < 64; ++l) {
+                        const uint64_t x = bx * 4 + (l & 3u), y = by * 4 + ((l >> 2) & 3u), z = bz * 4 + (l >> 4);
+                        if (x < n && y < n && z < n && cells[x + y * n + z * n * n] != 255) m |= 1ull << l;
+                    }
+                    uint64_t& w2 = l2[blk_index(bx >> 2, by >> 2, bz >> 2, nb3)];
+                    const uint64_t bit = 1ull << ((bx & 3u) | ((by & 3u) << 2) | ((bz & 3u) << 4));
+                    const bool was = w2 & bit, is = m != 0;
+                    if (is || was) l1[blk_index(bx, by, bz, nb2)] = m;
+                    if (is == was) continue;
+                    w2 ^= bit;
+                    const uint32_t p[3] = {bx, by, bz};
+                    box_add(E, p);
+                    ++flips;
+                }
+    if (flipped) *flipped = flips;
+    return E;
+}
+
+struct RefreshCount {
+    uint64_t bytes = 0, halves = 0, widths = 0;  // recomputed per stage: cube bytes, low halves, high halves
+};
+
+// Stages 1-4 after refresh_masks_host: the distance-field bytes in l1, the octant planes dfp and
+// the axis planes dfw (24 * nb2^3 * 64 words), updated in place where the flipped bricks E can
+// reach.  Afterwards all of them equal what the full builders make of the edited cells.
+inline RefreshCount refresh_levels_host(const uint8_t* /*cells_after*/, uint32_t n, const Box3& E, uint64_t* l1, const uint64_t* l2,
+                                        uint8_t* dfp, uint32_t* dfw) {
+    RefreshCount cnt;
+    if (box_empty(E)) return cnt;
+    const uint32_t nb1 = (n + 3) / 4, nb2 = (nb1 + 3) / 4, nb3 = (nb2 + 3) / 4;
+    const uint64_t plane = 64ull * nb2 * nb2 * nb2;
+    auto occ = [&](uint32_t x, uint32_t y, uint32_t z) {
+        return (l2[blk_index(x >> 2, y >> 2, z >> 2, nb3)] >> ((x & 3) + 4 * (y & 3) + 16 * (z & 3))) & 1ull;
+    };
+    uint8_t* bytes = reinterpret_cast<uint8_t*>(l1);
+    auto get = [&](uint32_t x, uint32_t y, uint32_t z, uint32_t o) -> uint32_t {
+        return bytes[(size_t)blk_index(x, y, z, nb2) * 8 + o];
+    };
+    const uint32_t reach[3] = {kReach, kReach, kReach};
+    // visit the bricks of a box, those furthest ahead in octant o first
+    auto sweep = [&](const Box3& b, uint32_t o, auto&& f) {
+        if (box_empty(b)) return;
+        const uint32_t c[3] = {(uint32_t)(b.hi[0] - b.lo[0] + 1), (uint32_t)(b.hi[1] - b.lo[1] + 1), (uint32_t)(b.hi[2] - b.lo[2] + 1)};
+        for (uint32_t fz = 0; fz < c[2]; ++fz)
+            for (uint32_t fy = 0; fy < c[1]; ++fy)
+                for (uint32_t fx = 0; fx < c[0]; ++fx) {
+                    const uint32_t p[3] = {(o & 1u) ? (uint32_t)b.lo[0] + fx : (uint32_t)b.hi[0] - fx,
+                                           (o & 2u) ? (uint32_t)b.lo[1] + fy : (uint32_t)b.hi[1] - fy,
+                                           (o & 4u) ? (uint32_t)b.lo[2] + fz : (uint32_t)b.hi[2] - fz};
+                    f(p);
+                }
+    };
+    Box3 C[8];
+    for (uint32_t o = 0; o < 8; ++o) {
+        // stage 1: mark from the old cube bytes (the octant planes still hold them), then recompute the marked box
+        C[o] = box_none();
+        sweep(box_behind(E, o, reach, nb1), o, [&](const uint32_t p[3]) {
+            if (cube_dirty(p, o, dfp[o * plane + blk_index(p[0], p[1], p[2], nb2)], E)) box_add(C[o], p);
+        });
+        sweep(C[o], o, [&](const uint32_t p[3]) {
+            if (occ(p[0], p[1], p[2])) return;
+            bytes[(size_t)blk_index(p[0], p[1], p[2], nb2) * 8 + o] = df_value(p[0], p[1], p[2], o, nb1, occ, get);
+            ++cnt.bytes;
+        });
+    }
+    for (uint32_t o = 0; o < 8; ++o)  // stage 2: the octant planes of the boxes
+        sweep(C[o], o, [&](const uint32_t p[3]) {
+            const uint32_t b = blk_index(p[0], p[1], p[2], nb2);
+            dfp[o * plane + b] = occ(p[0], p[1], p[2]) ? 0 : bytes[(size_t)b * 8 + o];
+        });
+    Box3 D[24];
+    for (uint32_t oa = 0; oa < 24; ++oa) {  // stage 3: the low halves, each from its own old word
+        const uint32_t o = oa / 3u, a = oa % 3u;
+        const uint8_t* pl = dfp + o * plane;
+        auto cube = [&](uint32_t x, uint32_t y, uint32_t z) -> uint32_t { return pl[blk_index(x, y, z, nb2)]; };
+        uint32_t ext[3] = {1u, 1u, 1u};
+        ext[a] = kReach;
+        D[oa] = box_none();
+        sweep(box_behind(C[o], o, ext, nb1), o, [&](const uint32_t p[3]) {
+            const uint32_t b = blk_index(p[0], p[1], p[2], nb2);
+            uint32_t& w = dfw[oa * plane + b];
+            if (!len_dirty(p, o, a, w & 255u, (w >> 8) & 255u, C[o])) return;
+            const uint32_t k = pl[b];
+            w = k ? ((w & 0xffff0000u) | k | axis_len(p[0], p[1], p[2], o, a, k, nb1, cube) << 8) : 0u;
+            box_add(D[oa], p);
+            ++cnt.halves;
+        });
+    }
+    for (uint32_t oa = 0; oa < 24; ++oa) {  // stage 4: the widths, from the final low halves
+        const uint32_t o = oa / 3u, a = oa % 3u;
+        uint32_t* pl = dfw + oa * plane;
+        auto word = [&](uint32_t x, uint32_t y, uint32_t z) -> uint32_t { return pl[blk_index(x, y, z, nb2)] & 0xffffu; };
+        sweep(box_behind(D[oa], o, reach, nb1), o, [&](const uint32_t p[3]) {
+            uint32_t& w = pl[blk_index(p[0], p[1], p[2], nb2)];
+            const uint32_t k = w & 255u, L = (w >> 8) & 255u;
+            if (!k || !wid_dirty(p, o, a, k, L, (w >> 16) & 255u, w >> 24, D[oa])) return;
+            w = (w & 0xffffu) | axis_wids(p[0], p[1], p[2], o, a, k, L, nb1, word) << 16;
+            ++cnt.widths;
+        });
+    }
+    return cnt;
 }
 #endif
 

@@ -183,6 +183,34 @@ def generate_some_smoke(n, frequency=0.001, seed=0x12345678):
     return _generate(abi.GEN_SMOKE, n, frequency, seed)
 
 
+def sphere_brush(center, r2, value, match=(0, 255)):
+    """abi.Brush: the cells within squared distance r2 (integer) of `center` (x, y, z) get `value`
+    where their byte lies in match = (lo, hi); value 255 digs.  (0, 255) all cells, (255, 255)
+    only empty ones, (0, 254) only solid ones."""
+    i3 = C.c_int32 * 3
+    return abi.Brush(abi.BRUSH_SPHERE, i3(*[int(v) for v in center]), int(r2), i3(), i3(), int(value), int(match[0]),
+                     int(match[1]), 0)
+
+
+def box_brush(lo, hi, value, match=(0, 255)):
+    """abi.Brush: the cells lo <= (x, y, z) <= hi (inclusive, clipped to the grid) get `value`, filtered
+    as sphere_brush."""
+    i3 = C.c_int32 * 3
+    return abi.Brush(abi.BRUSH_BOX, i3(), 0, i3(*[int(v) for v in lo]), i3(*[int(v) for v in hi]), int(value),
+                     int(match[0]), int(match[1]), 0)
+
+
+def apply_brushes(cells, n, brushes):
+    """vpx_brush_apply_host: the brushes on a host grid of n^3 bytes, in place: abi.BrushResult."""
+    lib = abi.load_library()
+    assert cells.dtype == np.uint8 and cells.size == int(n) ** 3 and cells.flags.c_contiguous
+    arr = (abi.Brush * max(1, len(brushes)))(*brushes)
+    res = abi.BrushResult()
+    abi.check(lib, None, lib.vpx_brush_apply_host(cells.ctypes.data, int(n), arr, len(brushes), C.byref(res)),
+              "vpx_brush_apply_host")
+    return res
+
+
 def default_materials():
     lib = abi.load_library()
     mats = (abi.Material * 256)()
