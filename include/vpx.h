@@ -28,6 +28,8 @@
  *   vpx_find_nearest_filtered  Renderer::FindNearestPlayer  renderer.cpp:1020-1071 (Tick :2139-2152)
  *                              Scene::FindNearestExcept     template/scene.cpp:813-873
  *   vpx_is_occluded_filtered   Renderer::IsOccludedPlayerClimbable  renderer.cpp:245-273
+ *   vpx_find_nearest_cells / vpx_pick_pixel / vpx_render_ids   no reference counterpart; the cell of
+ *                              Scene::FindNearest's return, template/scene.cpp:751-811
  *   vpx_get_player_light  Renderer::inLight           renderer.h:231; set renderer.cpp:1228-1240,
  *                                                     1438-1450; read :2112-2118, cleared :2206
  *   vpx_trace_probe       Trace's smoke-branch probe  renderer.cpp:1228-1240 (per ray)
@@ -394,8 +396,9 @@ typedef struct vpx_brush_result {    /* 16 bytes */
    allocates nothing (its few hundred bytes of scratch come with the context's first brush call).
    VPX_E_INVALID: brushes == NULL, count outside 1..256, unknown shape, reserved != 0,
    match_lo > match_hi, unknown grid.  Like every world edit the call waits for the frames in
-   flight; a device set applies it to every member.  Picking the cell from a vpx_hit is the
-   host's business. */
+   flight; a device set applies it to every member.  Which cell a ray or a pixel points at comes
+   from vpx_find_nearest_cells / vpx_pick_pixel; which ray to cast and what to do with the cell
+   is the host's business. */
 int vpx_grid_brush(vpx_ctx* ctx, uint32_t grid_id, const vpx_brush* brushes, uint32_t count,
                    vpx_brush_result* out /* may be NULL */);
 /* The same brushes on a host grid of n^3 bytes (host only, the code the device runs);
@@ -660,6 +663,51 @@ typedef struct vpx_ray_filter {       /* 16 bytes */
 } vpx_ray_filter;
 int vpx_find_nearest_filtered(vpx_ctx* ctx, const vpx_ray* rays, uint32_t n, const vpx_ray_filter* f, vpx_hit* hits);
 int vpx_is_occluded_filtered(vpx_ctx* ctx, const vpx_ray* rays, uint32_t n, const vpx_ray_filter* f, uint8_t* occluded);
+/* Hit cells: the filtered FindNearest that also reports WHICH cell was hit and through which face
+   the walk entered it, so that "point at a voxel, dig it; point at a face, build on it" needs no
+   guess from O + t * D (a point that lies on a cell face by construction).  The record describes
+   the winning volume's walk as the reference's plain loop runs it (Scene::FindNearest /
+   FindNearestExcept, template/scene.cpp:751-873): `cell` is the (X, Y, Z) at which the loop
+   returned, axis and step are those of the last tmax advance before it, face_cell = cell -
+   step * e_axis, the cell the walk visited immediately before.  A hit in the walk's first cell
+   (Setup3DDDA's start cell: the ray starts inside a solid cell or enters the cube straight into
+   one) took no step: VPX_CELL_FACE is clear, face_cell is zero, and the host falls back on the
+   normal.  Cells that the material range lets the ray pass through count as visited, so face_cell
+   holds NONE or an excepted material, never another solid one; it is a visited cell, so
+   VPX_CELL_FACE_IN comes with every VPX_CELL_FACE.  Misses and shape wins (vox_index < 0) give an
+   all-zero record.  hits[i] is vpx_find_nearest_filtered's, bit for bit, in both arithmetic modes,
+   and the refusals are the same. */
+#define VPX_CELL_HIT     0x1u  /* a voxel volume won (vox_index >= 0): cell[], grid_id valid */
+#define VPX_CELL_FACE    0x2u  /* the walk stepped INTO the hit cell: axis, face_cell valid   */
+#define VPX_CELL_FACE_IN 0x4u  /* face_cell lies inside the grid [0, n)^3                      */
+typedef struct vpx_hit_cell {      /* 32 bytes */
+    int32_t  cell[3];              /* the hit cell in the winning volume's grid                */
+    uint32_t grid_id;              /* that volume's grid                                       */
+    int32_t  face_cell[3];         /* the cell the walk visited immediately before: cell - step on `axis` */
+    uint32_t flags;                /* VPX_CELL_* | axis << 8 (0..2) | (step < 0 ? 1 : 0) << 10 */
+} vpx_hit_cell;
+int vpx_find_nearest_cells(vpx_ctx* ctx, const vpx_ray* rays, uint32_t n, const vpx_ray_filter* f,
+                           vpx_hit* hits, vpx_hit_cell* cells);            /* host pointers */
+/* The same query for the ray of integer pixel (x, y): Camera::GetPrimaryRayNoDOF with the
+   context's camera (template/camera.h:103-110), the ray of the static-camera path
+   (vpx_render_reproject), built with exact arithmetic in both arithmetic modes as on that path.
+   f == NULL is the neutral filter {0, 1, 0, 0}; VPX_QUERY_RAW_DIRECTION is refused
+   (VPX_E_INVALID: the library builds these rays); VPX_E_STATE without a camera; VPX_E_INVALID
+   for a zero size, x >= width, y >= height or a null output. */
+int vpx_pick_pixel(vpx_ctx* ctx, uint32_t width, uint32_t height, uint32_t x, uint32_t y,
+                   const vpx_ray_filter* f /* NULL = {0,1,0,0} */, vpx_hit* hit, vpx_hit_cell* cell);
+/* vpx_pick_pixel for every pixel of params->width x height at once (AA and DOF flags ignored; of
+   params only the size is used), one uint4 per pixel, row-major, in DEVICE memory:
+     .x  the bits of t (tmax = 1e34 on a miss)
+     .y  (uint16)(vox_index + 2) | material << 16 | face << 24, face = 0 for none (VPX_CELL_FACE
+         clear), else 1 + 2 * axis + (step < 0)
+     .z  cell.x | cell.y << 16          .w  cell.z
+   Bit for bit vpx_pick_pixel's records.  Runs on the context's stream without synchronising,
+   ordered like vpx_render_reproject; adds nothing to the work counters or the player-light
+   record.  VPX_E_STATE with more than 65533 volumes.  On a device set all three entries run on
+   devices[0]. */
+int vpx_render_ids(vpx_ctx* ctx, const vpx_frame_params* params, const vpx_ray_filter* f /* NULL = neutral */,
+                   uint32_t* ids /* uint4[W*H], DEVICE */);
 /* Focus ray of Renderer::Tick (world-space ray against every Scene::FindNearest). */
 int vpx_focus_distance(vpx_ctx* ctx, uint32_t width, uint32_t height, float* focal_distance);
 

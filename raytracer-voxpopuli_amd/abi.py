@@ -111,6 +111,13 @@ QUERY_RAW_DIRECTION = 0x2  # VPX_QUERY_RAW_DIRECTION: direction used as given (t
 MAT_SMOKE_LOW_DENSITY, MAT_SMOKE_PLAYER = 9, 14  # VPX_MAT_SMOKE_*: the range FindNearestPlayer passes through
 
 
+class HitCell(C.Structure):  # vpx_hit_cell: the hit cell and the face the walk entered it through
+    _fields_ = [("cell", C.c_int32 * 3), ("grid_id", C.c_uint32), ("face_cell", C.c_int32 * 3), ("flags", C.c_uint32)]
+
+
+CELL_HIT, CELL_FACE, CELL_FACE_IN = 0x1, 0x2, 0x4  # VPX_CELL_*; flags also hold axis << 8 | (step < 0) << 10
+
+
 LOAD_FULL, LOAD_PARTIAL, LOAD_RANDOM = 0, 1, 2  # VPX_LOAD_*: Scene::LoadModel / LoadModelPartial / LoadModelRandomMaterials
 
 
@@ -186,7 +193,7 @@ STAGES = ("primary", "shade", "shadow", "resolve", "bounce", "finish", "frame", 
 
 STRUCT_SIZES = {PrevCamera: 64, Profile: 160, Volume: 160, Material: 32, PointLight: 24, SpotLight: 40, AreaLight: 32, DirLight: 24,
                 Sphere: 32, Triangle: 64, Camera: 80, FrameParams: 48, Ray: 32, Hit: 32, Stats: 40,
-                BvhTri: 36, BvhNode: 32, PlayerLight: 24, RayProbe: 16, RayFilter: 16, ModelLoad: 40, ModelResult: 16,
+                BvhTri: 36, BvhNode: 32, PlayerLight: 24, RayProbe: 16, RayFilter: 16, HitCell: 32, ModelLoad: 40, ModelResult: 16,
                 NoiseGen: 16, NoiseResult: 16, Brush: 48, BrushResult: 16}
 
 
@@ -263,6 +270,10 @@ SIGNATURES = {
     "vpx_get_player_light": (C.c_int, [C.c_void_p, C.POINTER(PlayerLight), C.c_int]),
     "vpx_find_nearest_filtered": (C.c_int, [C.c_void_p, C.POINTER(Ray), C.c_uint32, C.POINTER(RayFilter), C.POINTER(Hit)]),
     "vpx_is_occluded_filtered": (C.c_int, [C.c_void_p, C.POINTER(Ray), C.c_uint32, C.POINTER(RayFilter), C.c_void_p]),
+    "vpx_find_nearest_cells": (C.c_int, [C.c_void_p, C.POINTER(Ray), C.c_uint32, C.POINTER(RayFilter), C.POINTER(Hit),
+                                         C.POINTER(HitCell)]),
+    "vpx_pick_pixel": (C.c_int, [C.c_void_p] + [C.c_uint32] * 4 + [C.POINTER(RayFilter), C.POINTER(Hit), C.POINTER(HitCell)]),
+    "vpx_render_ids": (C.c_int, [C.c_void_p, C.POINTER(FrameParams), C.POINTER(RayFilter), C.c_void_p]),
     "vpx_focus_distance": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_float)]),
     "vpx_camera_look_at": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_uint32, C.c_uint32,
                                      C.POINTER(Camera)]),

@@ -350,6 +350,40 @@ class Context:
                   "vpx_is_occluded_filtered")
         return occ[:n]
 
+    def find_nearest_cells(self, rays, first_volume=0, except_materials=None, shapes=True, raw_direction=False,
+                           filter=None):
+        """vpx_find_nearest_cells: find_nearest_filtered's hits plus, per ray, the abi.HitCell with the
+        hit cell and the face the walk entered it through.  Returns (hits, cells), ctypes arrays
+        (hits_to_numpy / cells_to_numpy)."""
+        n = len(rays)
+        hits = (abi.Hit * max(1, n))()
+        cells = (abi.HitCell * max(1, n))()
+        f = filter if filter is not None else self.ray_filter(first_volume, except_materials, shapes, raw_direction)
+        self._chk(self.lib.vpx_find_nearest_cells(self.h, rays, n, C.byref(f), hits, cells), "vpx_find_nearest_cells")
+        return hits, cells
+
+    def pick_pixel(self, width, height, x, y, first_volume=0, except_materials=None, shapes=True, filter=None):
+        """vpx_pick_pixel: the same query for the ray of integer pixel (x, y) (GetPrimaryRayNoDOF with the
+        context's camera).  Returns (abi.Hit, abi.HitCell)."""
+        hit, cell = abi.Hit(), abi.HitCell()
+        f = filter if filter is not None else self.ray_filter(first_volume, except_materials, shapes, False)
+        self._chk(self.lib.vpx_pick_pixel(self.h, int(width), int(height), int(x), int(y), C.byref(f), C.byref(hit),
+                                          C.byref(cell)), "vpx_pick_pixel")
+        return hit, cell
+
+    def render_ids(self, params, filter=None):
+        """vpx_render_ids: pick_pixel for every pixel, a torch int32 [H, W, 4] tensor on the
+        context's device (unpack_ids reads it).  Runs on the context's stream, unsynchronised."""
+        import torch
+
+        out = torch.empty((int(params.height), int(params.width), 4), dtype=torch.int32,
+                          device=f"cuda:{self.device}")
+        self._chk(self.lib.vpx_render_ids(self.h, C.byref(params), C.byref(filter) if filter is not None else None,
+                                          C.c_void_p(out.data_ptr())), "vpx_render_ids")
+        return out
+
+    unpack_ids = staticmethod(lambda ids: unpack_ids(ids))
+
     def trace(self, rays, seeds, depth, sky=abi.SKY_DEFAULT, area_samples=3):
         """Renderer::Trace per ray; sky=None samples the sky texture (activateSky)."""
         n = len(rays)
@@ -395,3 +429,27 @@ def hits_to_numpy(hits, n):
     dt = np.dtype([("t", "<f4"), ("normal", "<f4", 3), ("vox_index", "<i4"), ("material", "<u4"), ("cells", "<u4"),
                    ("inside_glass", "<u4")])
     return np.frombuffer(hits, dtype=dt, count=n).copy()
+
+
+def cells_to_numpy(cells, n):
+    dt = np.dtype([("cell", "<i4", 3), ("grid_id", "<u4"), ("face_cell", "<i4", 3), ("flags", "<u4")])
+    return np.frombuffer(cells, dtype=dt, count=n).copy()
+
+
+def unpack_ids(ids):
+    """The fields of a vpx_render_ids buffer ([H, W, 4] int32 / uint32, torch or numpy) as numpy
+    arrays of shape [H, W]: t (float32), vox_index (-2 miss, -1 shape), material, face (0 none,
+    else 1 + 2 * axis + (step < 0)), axis and step (0 where face is 0), cell ([H, W, 3])."""
+    if hasattr(ids, "cpu"):
+        ids = ids.cpu().numpy()
+    w = np.ascontiguousarray(ids).view(np.uint32)
+    y = w[..., 1]
+    face = (y >> 24).astype(np.int32)
+    cell = np.stack([w[..., 2] & 0xFFFF, w[..., 2] >> 16, w[..., 3]], axis=-1).astype(np.int32)
+    return {"t": np.ascontiguousarray(w[..., 0]).view(np.float32),
+            "vox_index": (y & 0xFFFF).astype(np.int32) - 2,
+            "material": ((y >> 16) & 0xFF).astype(np.uint32),
+            "face": face,
+            "axis": np.where(face > 0, (face - 1) >> 1, 0).astype(np.int32),
+            "step": np.where(face > 0, 1 - 2 * ((face - 1) & 1), 0).astype(np.int32),
+            "cell": cell}

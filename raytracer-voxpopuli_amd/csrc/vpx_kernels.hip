@@ -205,6 +205,71 @@ __global__ void is_occluded_filtered_k(SceneView sv, const vpx_ray* rays, uint32
     occ[i] = is_occluded(sv, r, k, f.first_volume, !(f.flags & VPX_QUERY_NO_SHAPES)) ? 1 : 0;
 }
 
+// The hit-cell entries (vpx_find_nearest_cells / vpx_pick_pixel / vpx_render_ids): the filtered
+// FindNearest in its CELLS form, one walk for the hit record and the cell record.
+__device__ __forceinline__ vpx_hit cells_query(const SceneView& sv, Ray& r, const vpx_ray_filter& f, vpx_hit_cell& cell) {
+    Counters k{0u, 0u, 0u};
+    HitCell hc;
+    const int32_t vox = find_nearest_filtered<kSkipwNearest, kMincNearest, kRunNearest, true>(
+        sv, r, k, f.first_volume, f.mat_lo, f.mat_hi, !(f.flags & VPX_QUERY_NO_SHAPES), &hc);
+    cell = hit_cell_record(sv, vox, hc);
+    vpx_hit h;
+    h.t = r.t;
+    h.normal[0] = r.N.x, h.normal[1] = r.N.y, h.normal[2] = r.N.z;
+    h.vox_index = vox;
+    h.material = r.mat;
+    h.cells = k.cells;
+    h.inside_glass = r.inside ? 1u : 0u;
+    return h;
+}
+
+__global__ void find_nearest_cells_k(SceneView sv, const vpx_ray* rays, uint32_t n, vpx_ray_filter f, vpx_hit* hits,
+                                     vpx_hit_cell* cells) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    Ray r = ray_from(rays[i], f.flags);
+    vpx_hit_cell c;
+    hits[i] = cells_query(sv, r, f, c);
+    cells[i] = c;
+}
+
+// Pixel (x, y)'s ray: Camera::GetPrimaryRayNoDOF, exact in both arithmetic modes (f.flags holds
+// kFlagReproject and neither AA nor DOF, so the generator is never drawn from).
+__device__ __forceinline__ vpx_hit pixel_query(const SceneView& sv, const FrameArgs& f, const vpx_ray_filter& flt, uint32_t x,
+                                               uint32_t y, vpx_hit_cell& cell) {
+    Rng g{0u};
+    Ray r = primary_ray(f, x, y, g, sv.x86);
+    return cells_query(sv, r, flt, cell);
+}
+
+__global__ void pick_pixel_k(SceneView sv, FrameArgs f, vpx_ray_filter flt, uint32_t x, uint32_t y, vpx_hit* hit,
+                             vpx_hit_cell* cell) {
+    vpx_hit_cell c;
+    *hit = pixel_query(sv, f, flt, x, y, c);
+    *cell = c;
+}
+
+// The ID pass: one lane per pixel, a 16x16 tile per workgroup in the frame kernels' 8x8-quadrant
+// lane order (tile_lane_xy: a wave's rays leave from one 8x8 block, so its lanes stay in the same
+// bricks and its walk phases stay full); lanes outside the image leave before the walk, whose
+// ballots count active lanes only; one 16-byte store per pixel.
+__global__ __launch_bounds__(kThreads) void k_ids(SceneView sv, FrameArgs f, vpx_ray_filter flt, uint4* __restrict__ ids) {
+    uint32_t lx, ly;
+    tile_lane_xy(threadIdx.x, lx, ly);
+    const uint32_t x = (blockIdx.x % f.tiles_x) * kTile + lx;
+    const uint32_t y = (blockIdx.x / f.tiles_x) * kTile + ly;
+    if (x >= f.width || y >= f.height) return;
+    vpx_hit_cell c;
+    const vpx_hit h = pixel_query(sv, f, flt, x, y, c);
+    const uint32_t face = (c.flags & VPX_CELL_FACE) ? 1u + 2u * ((c.flags >> 8) & 3u) + ((c.flags >> 10) & 1u) : 0u;
+    uint4 o;
+    o.x = __float_as_uint(h.t);
+    o.y = ((uint32_t)(h.vox_index + 2) & 0xffffu) | (h.material & 255u) << 16 | face << 24;
+    o.z = (uint32_t)c.cell[0] | (uint32_t)c.cell[1] << 16;
+    o.w = (uint32_t)c.cell[2];
+    ids[(uint64_t)y * f.width + x] = o;
+}
+
 // BasicBVH::IntersectBVH (src/BVH/BasicBVH.cpp:19-70), one ray per lane.  The workgroup
 // stages the whole BVH in LDS (nodes, then the triangles already permuted into tri_idx
 // order, so a leaf's triangles are contiguous); the recursion (node test, then left
@@ -3214,6 +3279,89 @@ int vpx_is_occluded_filtered(vpx_ctx* c, const vpx_ray* rays, uint32_t n, const 
     VPX_HIP(c, hipGetLastError());
     VPX_HIP(c, hipMemcpyAsync(occ, doc, n, hipMemcpyDeviceToHost, c->stream));
     VPX_HIP(c, sync_all(c));
+    return VPX_OK;
+}
+
+int vpx_find_nearest_cells(vpx_ctx* c, const vpx_ray* rays, uint32_t n, const vpx_ray_filter* f, vpx_hit* hits,
+                           vpx_hit_cell* cells) {
+    VPX_GROUP_FIRST(c, vpx_find_nearest_cells(m_, rays, n, f, hits, cells));
+    if (!c || (n && (!rays || !hits || !cells))) return fail(c, VPX_E_INVALID, "null argument");
+    int rc = check_filter(c, f, false);
+    if (rc) return rc;
+    if ((rc = check_ready(c))) return rc;
+    if (n == 0) return VPX_OK;
+    const size_t rb = sizeof(vpx_ray) * n, hb = sizeof(vpx_hit) * n, cb = sizeof(vpx_hit_cell) * n;
+    if ((rc = ensure_scratch(c, rb + hb + cb))) return rc;
+    vpx_ray* dr = (vpx_ray*)c->d_scratch;
+    vpx_hit* dh = (vpx_hit*)((char*)c->d_scratch + rb);
+    vpx_hit_cell* dc = (vpx_hit_cell*)((char*)c->d_scratch + rb + hb);
+    VPX_HIP(c, hipMemcpyAsync(dr, rays, rb, hipMemcpyHostToDevice, c->stream));
+    const float sky[3] = {0.392f, 0.584f, 0.829f};
+    hipLaunchKernelGGL(find_nearest_cells_k, dim3((n + 255) / 256), dim3(256), 0, c->stream, view_of(c, sky, 3), dr, n,
+                       *f, dh, dc);
+    VPX_HIP(c, hipGetLastError());
+    VPX_HIP(c, hipMemcpyAsync(hits, dh, hb, hipMemcpyDeviceToHost, c->stream));
+    VPX_HIP(c, hipMemcpyAsync(cells, dc, cb, hipMemcpyDeviceToHost, c->stream));
+    VPX_HIP(c, sync_all(c));
+    return VPX_OK;
+}
+
+// The pixel entries' shared checks and frame: the filter (NULL = neutral, no raw directions: the
+// library builds these rays), the size, the camera; the frame of the static-camera path's
+// GetPrimaryRayNoDOF (kFlagReproject keeps the ray's arithmetic exact in both modes).
+static int pixel_frame(vpx_ctx* c, uint32_t width, uint32_t height, const vpx_ray_filter* f, vpx_ray_filter& flt,
+                       FrameArgs& fa) {
+    flt = f ? *f : vpx_ray_filter{0u, 1u, 0u, 0u};
+    int rc = check_filter(c, &flt, false);
+    if (rc) return rc;
+    if (flt.flags & VPX_QUERY_RAW_DIRECTION)
+        return fail(c, VPX_E_INVALID, "VPX_QUERY_RAW_DIRECTION on a pixel query (the library builds the ray)");
+    if (width == 0 || height == 0 || width > 32768 || height > 32768)
+        return fail(c, VPX_E_INVALID, "frame size out of range");
+    if (!c->have_camera) return fail(c, VPX_E_STATE, "no camera set (vpx_set_camera)");
+    if ((rc = check_ready(c))) return rc;
+    if (c->volumes.size() > 65533u) return fail(c, VPX_E_STATE, "more than 65533 volumes: vox_index does not fit the ID word");
+    vpx_frame_params p = {};
+    p.width = width, p.height = height;
+    fa = frame_of(c, &p, 0, 1);
+    fa.flags = kFlagReproject;
+    return VPX_OK;
+}
+
+int vpx_pick_pixel(vpx_ctx* c, uint32_t width, uint32_t height, uint32_t x, uint32_t y, const vpx_ray_filter* f,
+                   vpx_hit* hit, vpx_hit_cell* cell) {
+    VPX_GROUP_FIRST(c, vpx_pick_pixel(m_, width, height, x, y, f, hit, cell));
+    if (!c || !hit || !cell) return fail(c, VPX_E_INVALID, "null argument");
+    vpx_ray_filter flt;
+    FrameArgs fa;
+    int rc = pixel_frame(c, width, height, f, flt, fa);
+    if (rc) return rc;
+    if (x >= width || y >= height) return fail(c, VPX_E_INVALID, "pixel outside the frame");
+    VPX_HIP(c, hipSetDevice(c->device));
+    if ((rc = ensure_scratch(c, sizeof(vpx_hit) + sizeof(vpx_hit_cell)))) return rc;
+    vpx_hit* dh = (vpx_hit*)c->d_scratch;
+    vpx_hit_cell* dc = (vpx_hit_cell*)((char*)c->d_scratch + sizeof(vpx_hit));
+    const float sky[3] = {0.392f, 0.584f, 0.829f};
+    hipLaunchKernelGGL(pick_pixel_k, dim3(1), dim3(1), 0, c->stream, view_of(c, sky, 3), fa, flt, x, y, dh, dc);
+    VPX_HIP(c, hipGetLastError());
+    VPX_HIP(c, hipMemcpyAsync(hit, dh, sizeof(vpx_hit), hipMemcpyDeviceToHost, c->stream));
+    VPX_HIP(c, hipMemcpyAsync(cell, dc, sizeof(vpx_hit_cell), hipMemcpyDeviceToHost, c->stream));
+    VPX_HIP(c, sync_all(c));
+    return VPX_OK;
+}
+
+int vpx_render_ids(vpx_ctx* c, const vpx_frame_params* p, const vpx_ray_filter* f, uint32_t* ids) {
+    VPX_GROUP_FIRST(c, vpx_render_ids(m_, p, f, ids));
+    if (!c || !p || !ids) return fail(c, VPX_E_INVALID, "null argument");
+    vpx_ray_filter flt;
+    FrameArgs fa;
+    const int rc = pixel_frame(c, p->width, p->height, f, flt, fa);
+    if (rc) return rc;
+    VPX_HIP(c, hipSetDevice(c->device));
+    const float sky[3] = {0.392f, 0.584f, 0.829f};
+    hipLaunchKernelGGL(k_ids, dim3(fa.num_tiles), dim3(kThreads), 0, c->stream, view_of(c, sky, 3), fa, flt,
+                       reinterpret_cast<uint4*>(ids));
+    VPX_HIP(c, hipGetLastError());
     return VPX_OK;
 }
 

@@ -704,10 +704,19 @@ __device__ __forceinline__ void frame_phase(int k) {
 // POOL (the bounce pool, k_nearest_pool): the lanes' modes come in and go out through *pmode
 // (lanes without a ray are kWalkMiss), and the walk also returns, with its lanes' state intact,
 // once `leave` or more lanes of the wave have finished, so that their rays can be replaced.
+// REC (the hit-cell queries, find_nearest_filtered<.., true>): *plast is the axis of the lane's
+// last cell advance, -1 while it stands in its first cell.  Every advance that can end in a
+// visited cell is one skip::step1 — a run's steps, and the leaving event after a skip's landing
+// cell (the closed forms move a lane only inside an empty box) — and step1 moves exactly one of
+// X / Y / Z by one, so the axis is read off the coordinates around each call: the plain loop's
+// axis by construction, ties, NaN and infinite tdeltas included.  Without REC nothing is added.
 constexpr int kWalkStep = 0, kWalkSkip = 1, kWalkMiss = 2, kWalkHit = 3;
-template <int PHK, uint32_t SKIPW, uint32_t MINC, uint32_t RUN, bool POOL = false>
+__device__ __forceinline__ int stepped_axis(const skip::Walk& w, uint32_t ox, uint32_t oy) {
+    return w.X != ox ? 0 : (w.Y != oy ? 1 : 2);
+}
+template <int PHK, uint32_t SKIPW, uint32_t MINC, uint32_t RUN, bool POOL = false, bool REC = false>
 __device__ __forceinline__ bool walk_wave(const skip::GridView& g, skip::Walk& w, float bound, uint32_t& cells,
-                                          int* pmode = nullptr, uint32_t leave = 65u) {
+                                          int* pmode = nullptr, uint32_t leave = 65u, int* plast = nullptr) {
     enum : int { kStep = kWalkStep, kSkip = kWalkSkip, kMiss = kWalkMiss, kHit = kWalkHit };
     constexpr int kRun = (int)(RUN & 255u);
     constexpr int kPasses = (int)((RUN >> 8) & 255u);
@@ -727,6 +736,7 @@ __device__ __forceinline__ bool walk_wave(const skip::GridView& g, skip::Walk& w
     // the ray's plane: its octant's, or its (octant, dominant axis)'s
     const uint32_t opar = skip::plane_parent(g, kAxis ? (w.osh >> 3) * 3u + skip::dom_axis(w) : w.osh >> 3);
     int mode = POOL ? *pmode : kStep;
+    int last = REC ? *plast : -1;
     VPX_PH(uint64_t cs = 0, ck = 0, ns = 0, nk = 0, ls = 0, lk = 0, fb = 0, cf = 0;)
     for (;;) {
         VPX_PH(uint64_t t0 = __builtin_amdgcn_s_memtime();)
@@ -772,6 +782,7 @@ __device__ __forceinline__ bool walk_wave(const skip::GridView& g, skip::Walk& w
                                 // cap) -> the next pass loads; bound reached -> miss; else the
                                 // cell is visited, a solid one ends the walk
                                 const bool ing = skip::step1<kMin2>(w, g.n);
+                                if (REC) last = stepped_axis(w, ox, oy);
                                 const bool inb = r + 1 < kRun && ((w.X ^ ox) | (w.Y ^ oy) | (w.Z ^ oz)) <= 3u;
                                 const bool inbound = w.t < bound;
                                 const bool sol =
@@ -812,7 +823,9 @@ __device__ __forceinline__ bool walk_wave(const skip::GridView& g, skip::Walk& w
                 mode = kMiss;
             } else {
                 ++cells;  // visit the landing cell, then take the leaving event
+                const uint32_t ox = w.X, oy = w.Y;
                 mode = skip::step1<kMin2>(w, g.n) ? kStep : kMiss;
+                if (REC) last = stepped_axis(w, ox, oy);
             }
         }
         VPX_PH(ck += __builtin_amdgcn_s_memtime() - t1;)
@@ -821,6 +834,7 @@ __device__ __forceinline__ bool walk_wave(const skip::GridView& g, skip::Walk& w
     pool_out:
         *pmode = mode;
     }
+    if (REC) *plast = last;
 #ifdef VPX_PHASE_PROF
     if ((threadIdx.x & 63) == __builtin_amdgcn_readfirstlane(threadIdx.x & 63)) {
         atomicAdd(&g_phase[PHK + 0], cs);
@@ -1205,12 +1219,21 @@ __device__ __forceinline__ int32_t find_nearest(const SceneView& sv, Ray& r, Cou
 __device__ __forceinline__ bool rcp_nan(float x) {  // zero (denormals flush), infinite or NaN
     return !(fabsf(x) > 0.0f && fabsf(x) < __builtin_inff());
 }
-template <uint32_t SKIPW = kSkipwNearest, uint32_t MINC = kMincNearest, uint32_t RUN = kRunNearest>
+// CELLS (vpx_find_nearest_cells, vpx_pick_pixel, vpx_render_ids): the same walk also reports the
+// winner's cell and the step that entered it in *hc (walk_wave's REC; an excepted cell's leaving
+// event is a step like any other).  A volume or shape that wins later replaces or clears it.
+struct HitCell {
+    uint32_t x, y, z, grid;
+    int32_t axis;  // of the last advance before the hit; -1: the hit cell is the walk's first cell
+    int32_t step;  // that axis' step, +1 / -1
+};
+template <uint32_t SKIPW = kSkipwNearest, uint32_t MINC = kMincNearest, uint32_t RUN = kRunNearest, bool CELLS = false>
 __device__ __forceinline__ int32_t find_nearest_filtered(const SceneView& sv, Ray& r, Counters& k, uint32_t first,
-                                                         uint32_t mlo, uint32_t mhi, bool shapes) {
+                                                         uint32_t mlo, uint32_t mhi, bool shapes, HitCell* hc = nullptr) {
     int32_t vox = -2;
     ++k.nearest;
     uint32_t hmat = kNone;  // the byte of the hit cell in volume `vox`
+    if (CELLS) *hc = HitCell{0u, 0u, 0u, 0u, -1, 0};
     const f3 inv = world_inv(r.D);
     auto visit = [&](uint32_t i) {
         if (i < first) return true;  // not visited: no cell read or counted
@@ -1232,14 +1255,17 @@ __device__ __forceinline__ int32_t find_nearest_filtered(const SceneView& sv, Ra
         }
         const skip::GridView gv = grid_view(g);
         int mode = kWalkStep;
+        int last = -1;
         uint32_t cell = kNone;
         for (;;) {
-            walk_wave<0, SKIPW, MINC, RUN, true>(gv, w, r.t, k.cells, &mode);
+            walk_wave<0, SKIPW, MINC, RUN, true, CELLS>(gv, w, r.t, k.cells, &mode, 65u, &last);
             bool on = false;
             if (mode == kWalkHit) {
                 cell = gv.cells[(uint64_t)w.X + (uint64_t)w.Y * gv.n + (uint64_t)w.Z * ((uint64_t)gv.n * gv.n)];
                 if (cell >= mlo && cell <= mhi) {  // scene.cpp:826: passed through
+                    const uint32_t ox = w.X, oy = w.Y;
                     on = skip::step1<((RUN >> 18) & 1u) != 0u>(w, gv.n);
+                    if (CELLS) last = stepped_axis(w, ox, oy);
                     mode = on ? kWalkStep : kWalkMiss;
                 }
             }
@@ -1249,6 +1275,7 @@ __device__ __forceinline__ int32_t find_nearest_filtered(const SceneView& sv, Ra
             r.t = w.t;
             hmat = cell;
             vox = (int32_t)i;
+            if (CELLS) *hc = HitCell{w.X, w.Y, w.Z, vol.grid_id, last, last == 0 ? w.sx : (last == 1 ? w.sy : w.sz)};
         }
         return true;
     };
@@ -1275,9 +1302,29 @@ __device__ __forceinline__ int32_t find_nearest_filtered(const SceneView& sv, Ra
             r.N = sh.N;
             r.inside = sh.inside;
             vox = -1;
+            if (CELLS) *hc = HitCell{0u, 0u, 0u, 0u, -1, 0};
         }
     }
     return vox;
+}
+
+// The vpx_hit_cell of a find_nearest_filtered<.., true> result (vox: its return value).
+__device__ __forceinline__ vpx_hit_cell hit_cell_record(const SceneView& sv, int32_t vox, const HitCell& h) {
+    vpx_hit_cell o = {};
+    if (vox < 0) return o;
+    o.cell[0] = (int32_t)h.x, o.cell[1] = (int32_t)h.y, o.cell[2] = (int32_t)h.z;
+    o.grid_id = h.grid;
+    o.flags = VPX_CELL_HIT;
+    if (h.axis >= 0) {
+        const int32_t n = (int32_t)sv.grids[h.grid].n;
+        o.face_cell[0] = o.cell[0] - (h.axis == 0 ? h.step : 0);
+        o.face_cell[1] = o.cell[1] - (h.axis == 1 ? h.step : 0);
+        o.face_cell[2] = o.cell[2] - (h.axis == 2 ? h.step : 0);
+        const int32_t f = h.axis == 0 ? o.face_cell[0] : (h.axis == 1 ? o.face_cell[1] : o.face_cell[2]);  // (no dynamic index)
+        o.flags |= VPX_CELL_FACE | (uint32_t)h.axis << 8 | (h.step < 0 ? 1u : 0u) << 10 |
+                   (f >= 0 && f < n ? VPX_CELL_FACE_IN : 0u);
+    }
+    return o;
 }
 
 #ifndef VPX_LANE_VOLUMES

@@ -23,6 +23,9 @@
 //   nothing: GenerateSomeNoise(0.03f) and GenerateSomeSmoke(0.167f) through the mirror on an n^3
 //   grid (n: the first argument), the checksum, the draws and the seed after each as one JSON
 //   line; '-' none.
+// usage: vpx_demo pick [n] [width] [height] [x] [y]
+//   renders nothing: the same world and camera, then Renderer::PickPixel(x, y) (vpx_pick_pixel,
+//   everything visible) and the hit and its cell record as one JSON line.
 //   devices: comma-separated HIP devices, e.g. 0,1,2,3 — a device set (vpx_create_multi:
 //   tiles over the devices, RCCL gather to the first); default: device 0 alone.
 #include <chrono>
@@ -207,6 +210,8 @@ static int generators(vpxhost::Renderer& r, uint32_t n) {
 }
 
 int main(int argc, char** argv) {
+    const bool pick = argc > 1 && std::strcmp(argv[1], "pick") == 0;
+    if (pick) --argc, ++argv;  // the pixel takes the places of frames and max_bounces
     const uint32_t n = argc > 1 ? (uint32_t)atoi(argv[1]) : 256;
     const uint32_t W = argc > 2 ? (uint32_t)atoi(argv[2]) : 640;
     const uint32_t H = argc > 3 ? (uint32_t)atoi(argv[3]) : 360;
@@ -254,6 +259,18 @@ int main(int argc, char** argv) {
     CHECK(r.SetShapes({}, {}));
     const float pos[3] = {1.25f, 0.9f, -0.35f}, target[3] = {0.45f, 0.15f, 0.55f};
     CHECK(r.LookAt(pos, target));
+    if (pick) {
+        vpx_hit h{};
+        vpx_hit_cell c{};
+        CHECK(r.PickPixel((uint32_t)frames, (uint32_t)bounces, nullptr, &h, &c));
+        uint32_t tb;
+        std::memcpy(&tb, &h.t, 4);
+        std::printf("{\"pick\": {\"x\": %d, \"y\": %d, \"t_bits\": %u, \"vox\": %d, \"material\": %u, \"cells\": %u, "
+                    "\"cell\": [%d, %d, %d], \"grid_id\": %u, \"face_cell\": [%d, %d, %d], \"flags\": %u}}\n",
+                    frames, bounces, tb, h.vox_index, h.material, h.cells, c.cell[0], c.cell[1], c.cell[2], c.grid_id,
+                    c.face_cell[0], c.face_cell[1], c.face_cell[2], c.flags);
+        return 0;
+    }
     r.maxBounces = bounces;
     if (sky) {
         const std::vector<float> tex = demo_sky(64, 32);

@@ -296,6 +296,28 @@ int Renderer::FindNearestPlayer(PlayerRay& ray, int32_t* vox_index) {
     return VPX_OK;
 }
 
+int Renderer::FindNearestCells(PlayerRay& ray, int32_t* vox_index, vpx_hit_cell* cell) {
+    if (status_) return status_;
+    if (!vox_index || !cell) return VPX_E_INVALID;
+    const vpx_ray r = player_ray(ray);
+    const vpx_ray_filter f{1u, VPX_MAT_SMOKE_LOW_DENSITY, VPX_MAT_SMOKE_PLAYER, VPX_QUERY_NO_SHAPES | VPX_QUERY_RAW_DIRECTION};
+    vpx_hit h{};
+    const int rc = vpx_find_nearest_cells(ctx_, &r, 1, &f, &h, cell);
+    if (rc) return rc;
+    if (h.vox_index >= 0) {
+        ray.t = h.t;
+        for (int i = 0; i < 3; ++i) ray.rayNormal[i] = h.normal[i];
+        ray.indexMaterial = h.material;
+    }
+    *vox_index = player_vox_index(h.vox_index, numVolumes_, currentChunk);
+    return VPX_OK;
+}
+
+int Renderer::PickPixel(uint32_t x, uint32_t y, const vpx_ray_filter* filter, vpx_hit* hit, vpx_hit_cell* cell) {
+    if (status_) return status_;
+    return vpx_pick_pixel(ctx_, width_, height_, x, y, filter, hit, cell);
+}
+
 int Renderer::IsOccludedPlayerClimbable(const PlayerRay& ray, bool* occluded) {
     if (status_) return status_;
     if (!occluded) return VPX_E_INVALID;

@@ -112,6 +112,12 @@ public:
     // smoke passed through (Scene::FindNearestExcept), no spheres / triangles.  *vox_index = the
     // volume index after player_vox_index; on a hit t, rayNormal and indexMaterial are updated.
     int FindNearestPlayer(PlayerRay& ray, int32_t* vox_index);
+    // The same cast with the hit cell (vpx_find_nearest_cells): *cell names the cell the player
+    // points at and, with VPX_CELL_FACE, the empty neighbour a new voxel would go into.
+    int FindNearestCells(PlayerRay& ray, int32_t* vox_index, vpx_hit_cell* cell);
+    // The hit and the hit cell under pixel (x, y) of the frame (vpx_pick_pixel; filter NULL =
+    // everything).  Which pixel to pick and what to do with the cell is the game's business.
+    int PickPixel(uint32_t x, uint32_t y, const vpx_ray_filter* filter, vpx_hit* hit, vpx_hit_cell* cell);
     // Renderer::IsOccludedPlayerClimbable (renderer.cpp:245-273).
     int IsOccludedPlayerClimbable(const PlayerRay& ray, bool* occluded);
 

@@ -165,6 +165,25 @@ class Renderer:
             ray.t, ray.rayNormal, ray.indexMaterial = h.t, tuple(h.normal), h.material
         return player_vox_index(h.vox_index, len(self.scene.volumes), self.currentChunk)
 
+    def FindNearestCells(self, ray):
+        """FindNearestPlayer's query with the hit cell (vpx_find_nearest_cells): the same filter and
+        the same update of `ray`.  Returns (volume index as FindNearestPlayer, abi.HitCell): the
+        cell the player points at and the neighbour a new voxel would go into."""
+        hits, cells = self.ctx.find_nearest_cells(make_rays([ray.O], [ray.D], ray.t), 1,
+                                                  (abi.MAT_SMOKE_LOW_DENSITY, abi.MAT_SMOKE_PLAYER), shapes=False,
+                                                  raw_direction=True)
+        h = hits[0]
+        if h.vox_index >= 0:
+            ray.t, ray.rayNormal, ray.indexMaterial = h.t, tuple(h.normal), h.material
+        return player_vox_index(h.vox_index, len(self.scene.volumes), self.currentChunk), cells[0]
+
+    def PickPixel(self, x, y, filter=None):
+        """The hit and the hit cell under pixel (x, y) of the frame (vpx_pick_pixel): (abi.Hit,
+        abi.HitCell).  Which pixel to pick and what to do with the cell is the game's business."""
+        return self.ctx.pick_pixel(self.scene.width, self.scene.height, x, y, filter=filter)
+
+    pick_pixel = PickPixel
+
     def IsOccludedPlayerClimbable(self, ray):
         """Renderer::IsOccludedPlayerClimbable (renderer.cpp:245-273): IsOccluded from volume 1 on,
         without the spheres / triangles, ray.D as given."""
