@@ -210,7 +210,7 @@ __global__ void is_occluded_filtered_k(SceneView sv, const vpx_ray* rays, uint32
 __device__ __forceinline__ vpx_hit cells_query(const SceneView& sv, Ray& r, const vpx_ray_filter& f, vpx_hit_cell& cell) {
     Counters k{0u, 0u, 0u};
     HitCell hc;
-    const int32_t vox = find_nearest_filtered<kSkipwNearest, kMincNearest, kRunNearest, true>(
+    const int32_t vox = find_nearest_filtered<NearestWalk, true>(
         sv, r, k, f.first_volume, f.mat_lo, f.mat_hi, !(f.flags & VPX_QUERY_NO_SHAPES), &hc);
     cell = hit_cell_record(sv, vox, hc);
     vpx_hit h;

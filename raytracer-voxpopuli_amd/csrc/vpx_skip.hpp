@@ -361,27 +361,10 @@ template <uint32_t MINC = kMinCube>
 VPX_HD int classify_dfp(Walk& w, const GridView& g, const uint8_t* pl) {
     return classify_dfp_byte<MINC>(w, g, load_u8(pl, blk_index(w.X >> 2, w.Y >> 2, w.Z >> 2, g.nb2)));
 }
-// classify_dfp with the plane named by its first parent, opar = octant * nb2^3: the planes
-// are consecutive and parent-major, so octant and parent fold into one 32-bit parent index
-// (< 2^27 up to 4096^3 grids) and only the byte offset is formed in 64 bits — a walk keeps
-// one 32-bit value live for its plane instead of a 64-bit pointer.
-template <uint32_t MINC = kMinCube>
-VPX_HD int classify_dfp_o(Walk& w, const GridView& g, uint32_t opar) {
-    const uint32_t bx = w.X >> 2, by = w.Y >> 2, bz = w.Z >> 2, np = g.nb2;
-#if defined(__HIP_DEVICE_COMPILE__)
-    const uint32_t parent = opar + __umul24(bz >> 2, __umul24(np, np)) + __umul24(by >> 2, np) + (bx >> 2);
-#else
-    const uint32_t parent = opar + (bz >> 2) * np * np + (by >> 2) * np + (bx >> 2);
-#endif
-    const uint64_t i = (uint64_t)parent << 6 | ((bx & 3u) | ((by & 3u) << 2) | ((bz & 3u) << 4));
-#if defined(__HIP_DEVICE_COMPILE__)
-    const uint32_t k = ((const __attribute__((address_space(1))) uint8_t*)g.dfp)[i];
-#else
-    const uint32_t k = g.dfp[i];
-#endif
-    return classify_dfp_byte<MINC>(w, g, k);
-}
-// The first parent of octant o's plane (classify_dfp_o).
+// The first parent of plane o, o * nb2^3: the planes are consecutive and parent-major, so plane
+// and parent fold into one 32-bit parent index (< 2^27 up to 4096^3 grids) and only the word's
+// offset is formed in 64 bits — a walk keeps one 32-bit value live for its plane instead of a
+// 64-bit pointer (classify_axis_o).
 VPX_HD uint32_t plane_parent(const GridView& g, uint32_t o) { return o * (g.nb2 * g.nb2 * g.nb2); }
 // The axis a walk takes its boxes along: the one with the smallest tdelta (the ray advances
 // fastest along it).  Fixed per ray; ties, infinities and NaNs take whatever the compares
@@ -394,7 +377,7 @@ VPX_HD uint32_t sec_axis(uint32_t a, float dx, float dy, float dz) {
     return a == 0u ? (dy <= dz ? 1u : 2u) : (a == 1u ? (dx <= dz ? 0u : 2u) : (dx <= dy ? 0u : 1u));
 }
 VPX_HD uint32_t sec_axis(const Walk& w) { return sec_axis(dom_axis(w), w.dx, w.dy, w.dz); }
-// classify_dfp_o on the axis planes: apar = (octant * 3 + axis) * nb2^3 (plane_parent of the
+// classify_dfp on the axis planes: apar = (octant * 3 + axis) * nb2^3 (plane_parent of the
 // plane's index), one load per step: the 32-bit word of dfw, or on the host dfa's 16 bits.  An empty brick skips (class 2) when its cube
 // reaches MINC or its box's length MINL; m1 gets the word (cube_dfp / len_dfa read it back).
 template <uint32_t MINC = kMinCube, uint32_t MINL = 2>
@@ -475,7 +458,7 @@ VPX_HD bool step1_commit(Walk& w, uint32_t n, bool ax, bool ay, bool az) {
 // "a = x<y ? x : y; a<z ? (the axis of a) : z" — the same axis for every input, NaN and ties
 // included (x<y false -> a = y, then y<z; x<y true -> x<z), with two compares and one select
 // instead of three compares and a select chain.
-// The walkers choose per walk kind (bit 18 of their RUN word, vpx_trace.hpp): with the
+// The walkers choose per walk kind (its `min2` field, vpx_walk_kinds.hpp): with the
 // shadow walkers' 72-VGPR budget this form spilled more and measured slower on C3.
 template <bool MIN2 = true>
 VPX_HD bool step1(Walk& w, uint32_t n) {
@@ -918,7 +901,7 @@ VPX_HD bool gate_open(float tx, float ty, float tz, float dx, float dy, float dz
     return !((ix & (tx < lim)) | (iy & (ty < lim)) | (iz & (tz < lim)));
 }
 // The gate as walk_skip takes it: 0 = none, else 1 | G << 1 | f << 3 with G <= 3 and N = 4 << f,
-// f <= 3 (the walkers' RUN word holds the same five bits from bit 26, vpx_trace.hpp).
+// f <= 3 (the walk kinds' gate_g and gate_n have the same ranges, vpx_walk_kinds.hpp).
 VPX_HD uint32_t gate_word(uint32_t G, uint32_t f) { return 1u | G << 1 | f << 3; }
 VPX_HD bool gate_open(const Walk& w, uint32_t gate) {
     return !(gate & 1u) || gate_open(w.tx, w.ty, w.tz, w.dx, w.dy, w.dz, (gate >> 1) & 3u, 4u << ((gate >> 3) & 3u));
@@ -929,7 +912,7 @@ VPX_HD bool gate_open(const Walk& w, uint32_t gate) {
 // walker (walk_wave, vpx_trace.hpp) runs the same per-lane sequence.
 // With the axis planes (g.dfa / g.dfw) the boxes are theirs, along the ray's dominant axis, and
 // with g.dfw widened along its second.  `gate` (gate_word, 0: none): a class-2 brick is stepped
-// through while the maturity gate is shut, as the walkers do for the kinds that have the bit;
+// through while the maturity gate is shut, as the walkers do for the kinds with `gate`;
 // bits 5-7 of it: the further segments its skips may take (skip_box_lean's MORE, up to 4); bit 8
 // (kGatePre): its skips take the plain-step prefix (skip_box_lean's PRE).
 constexpr uint32_t kGatePre = 1u << 8;

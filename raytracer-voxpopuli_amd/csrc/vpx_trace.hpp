@@ -21,6 +21,11 @@
 #include "../../include/vpx.h"
 #include "vpx_skip.hpp"
 #include "vpx_x86.hpp"
+// The walk kinds (walk_wave's KIND); an A/B build names an edited copy here.
+#ifndef VPX_WALK_KINDS
+#define VPX_WALK_KINDS "vpx_walk_kinds.hpp"
+#endif
+#include VPX_WALK_KINDS
 
 namespace vpx {
 
@@ -448,207 +453,9 @@ __device__ __forceinline__ skip::Walk to_walk(const Dda& s) {
 // skip::walk_skip with wave-aware scheduling: each lane runs exactly the same sequence of
 // classify / skip_box / step1 as skip::walk_skip (so results are identical), but the long
 // skip_box is executed in batches — only when few lanes of the wave still want to take
-// plain cell steps — instead of inside every step iteration of the wave.
-// Skip-phase weights SKIPW per walk kind: keep stepping while steppers x SKIPW >= waiting
-// skippers (measured on C1 / C3 / C2: FindNearest 2, IsOccluded 4, bounces 2; with the
-// two-compare step FindNearest 1: C1 0.666 vs 0.671 ms over two three-run A/Bs).
-constexpr uint32_t kSkipwNearest = 1, kSkipwBounce = 2, kSkipwShadow = 4;
-// Smallest distance-field cube worth a skip per walk kind (C1, ms: FindNearest 0.430 with
-// 2 / 0.435 with 1; IsOccluded 0.383 with 2 / 0.354 with 1).
-#ifndef VPX_MINC_NEAREST
-#define VPX_MINC_NEAREST 2
-#endif
-#ifndef VPX_MINC_SHADOW
-#define VPX_MINC_SHADOW 1
-#endif
-constexpr uint32_t kMincNearest = VPX_MINC_NEAREST, kMincBounce = 2, kMincShadow = VPX_MINC_SHADOW;
-// Brick runs per walk kind, the RUN word: cap | passes << 8 | pre << 16 | seg2 << 17 | min2 << 18 |
-// axis << 19 | minlen << 20 | wide << 24 | local << 25 | gate << 26 | G << 27 | N << 29 | seg3 << 31.
-// After its octant-plane byte (and, in an occupied brick, its cell mask) loads, a lane
-// steps up to `cap` cells inside its 4^3 brick on the register copy; `passes` brick loads
-// per step-phase iteration.  Measured (ms, one box): primary C1 0.432 -> 0.402 with 3|2<<8;
-// shadow C3 4.01 -> 3.82 with 3|1<<8; bounce C2 0.654 -> 0.569 with 4|1<<8.  Caps above 4
-// spill (the runs are unrolled); caps 6 / 10 for runs through all-empty bricks: C1 0.751 /
-// 0.765 vs 0.703 ms.
-// seg2 (bit 17): the skip's second closed-form segment only when a lane of the wave needs it
-// (skip_box_lean<true>).  Measured (ms, one box): C1 0.713 -> 0.693, C3 5.57 -> 5.34, rank
-// 0's C1 share at 8 ranks 0.234 -> 0.222; bounce walks (rays leaving surfaces, whose boxes
-// cross binades in most waves) C2 4.27 -> 4.34 with it, so off there.
-// min2 (bit 18): step1's two-compare axis choice (vpx_skip.hpp).  Measured (ms, three
-// interleaved runs, vs the three-compare form): C1 0.678 vs 0.687; the shadow walkers (72
-// VGPRs, 7 waves/SIMD) spilled two more VGPRs with it and C3 went 5.26 -> 5.53, so they keep
-// the three-compare form.
-// axis (bit 19): the walk's boxes come from the axis planes (skip::GridView::dfw): the brick's
-// cube extended along the ray's dominant axis, one 32-bit load per step instead of the octant
-// plane's byte.  minlen (bits 20-23): an empty brick whose cube is below the skip minimum
-// still skips when its box is at least this many bricks long.  VPX_AXIS_BOXES sets the bit for
-// every walk kind that has no word of its own on the command line.  Measured (ms per step, one
-// box, three interleaved runs each of the build before the planes and this one, every kind on):
-// C1 0.5424-0.5484 -> 0.4737-0.4789, C2 2.292-2.323 -> 2.051-2.058, C3 3.594-3.599 ->
-// 3.363-3.377, C4 26.39-26.63 -> 25.40-25.56, Z1 (tiny grids, little to extend) 1.491-1.514 ->
-// 1.470-1.510; k_frame0 spills 27 VGPRs with it instead of 19 (DESIGN.md §4 has the table).
-// Rejected walk variants (DESIGN.md §4 keeps the measurements): classifying from the l1 + l2
-// words instead of the octant plane, a branch-free select-committed step, loading two
-// cells' words per round trip, prefetching the exit brick's byte, speculative cell-mask
-// loads after an occupied brick, walk continuations with a step budget.
-#ifndef VPX_AXIS_BOXES
-#define VPX_AXIS_BOXES 1
-#endif
-#ifndef VPX_AXIS_MINLEN
-#define VPX_AXIS_MINLEN 2u
-#endif
-// wide (bit 24, with axis): the box is also widened along the ray's second axis (skip::sec_axis)
-// to the word's Mb or Mc, from the same load.  VPX_WIDE_BOXES sets it like VPX_AXIS_BOXES.
-// Measured (ms per step, three interleaved runs each of the build on the 16-bit planes and this
-// one): C1 0.4644-0.4729 -> 0.4436-0.4457, C3 3.352-3.376 -> 3.212-3.227, C4 25.41-25.57 ->
-// 24.84-25.22; C2 2.043-2.076 -> 2.005-2.057 and Z1 1.480-1.498 -> 1.496-1.522 count as unchanged.
-// local (bit 25, with axis): the skip phase works its axes out from the tdeltas each time, behind
-// a barrier.  The compares are the same all walk long, and the compiler hoists them out of the
-// loop: in the 72- and 80-VGPR kernels (k_frame0, the shadow walkers, k_primary) their results then
-// sat in scratch and were reloaded in every skip phase.  The bounce walks (k_tail, k_nearest_tile,
-// k_nearest_pool) have the registers to keep them and Z1 lost 2 % with the bit in every kind, so
-// every kind but the bounce one has it.  VPX_LOCAL_AXES=1 sets it
-// for every kind, 0 for none.
-#ifndef VPX_WIDE_BOXES
-#define VPX_WIDE_BOXES 1
-#endif
-#ifdef VPX_LOCAL_AXES
-#define VPX_RUN_LOCAL(on) ((VPX_LOCAL_AXES ? 1u : 0u) << 25)
-#else
-#define VPX_RUN_LOCAL(on) ((on) << 25)
-#endif
-#define VPX_RUN_AXIS ((VPX_AXIS_BOXES ? 1u : 0u) << 19 | VPX_AXIS_MINLEN << 20 | (VPX_AXIS_BOXES && VPX_WIDE_BOXES ? 1u : 0u) << 24)
-// gate (bit 26), G (bits 27-28), N (bits 29-30: N = 4 << field): the maturity gate (skip::gate_open,
-// vpx_skip.hpp).  A class-2 lane whose skip would be clipped at an immature axis's next event
-// (exponent of tmax below exponent of tdelta + G, that event within N events of the dominant
-// axis) takes its brick as class 3 and steps.  Walks that start at t = 0 (shadow and bounce rays)
-// begin with every axis immature, and in a compacted shadow wave all lanes at once.  Measured (ms
-// per step, one box, interleaved runs of the parent's library and this one, DESIGN.md section 4,
-// round 10): with the bit in k_frame0's shadow walks C1 0.4760-0.4795 -> 0.4503-0.4592; in the
-// other tile shadow walkers (kRunShadow) on top C4 24.90-25.42 -> 24.38-24.87; in the shadow pool
-// C3 3.307-3.351 -> 3.355-3.389 and in the bounce walks C2 / Z1 2.166-2.191 / 1.609-1.611 ->
-// 2.187-2.209 / 1.618-1.620 (their lanes start at different times, so a stepping lane holds its
-// wave in the step phase while the others wait to skip): off there.  G 2 or N 8 instead of 1 and 4
-// measured the same on C1.  VPX_SKIP_GATE=1 sets the bit for every kind, 0 for none; VPX_GATE_G /
-// VPX_GATE_NF set the fields.
-#ifndef VPX_GATE_G
-#define VPX_GATE_G 1u
-#endif
-#ifndef VPX_GATE_NF
-#define VPX_GATE_NF 0u
-#endif
-#ifdef VPX_SKIP_GATE
-#define VPX_RUN_GATE(on) ((VPX_SKIP_GATE ? 1u : 0u) << 26 | VPX_GATE_G << 27 | VPX_GATE_NF << 29)
-#else
-#define VPX_RUN_GATE(on) ((on) << 26 | VPX_GATE_G << 27 | VPX_GATE_NF << 29)
-#endif
-// seg3 (bit 31, with seg2): a skip whose box outruns its two closed-form segments rebases its
-// clipped axes onto the next binade, up to VPX_SEG_MORE times, behind a ballot like seg2's
-// (skip::skip_box_lean's MORE).  Off in every kind: the CPU model gives the shadow walks 13 % to
-// 18 % fewer wave-cost units with one or two further segments (none to the primary walks, whose
-// clipped axes are not the ones their boxes are left through), but k_frame0 spills 34 / 58 VGPRs
-// with them instead of 20 and C1 measured 0.518-0.526 / 0.581-0.588 ms against 0.476-0.480 (with
-// the gate on top 0.482-0.485 against 0.462-0.464).  VPX_SEG3=1 sets the bit for every kind that
-// has seg2.
-#ifndef VPX_SEG_MORE
-#define VPX_SEG_MORE 1
-#endif
-#ifdef VPX_SEG3
-#define VPX_RUN_SEG3(on) ((VPX_SEG3 ? 1u : 0u) << 31)
-#else
-#define VPX_RUN_SEG3(on) ((on) << 31)
-#endif
-// pre (bit 16): the skip takes the plain-step prefix (skip::skip_box_lean's PRE, vpx_skip.hpp): an
-// axis whose tmax is at or below its tdelta (every axis of a walk that starts at t = 0) is not
-// clipped to zero events but to "the plain IEEE step, then the closed form from the value it lands
-// on", and the step's value is reached even where no closed form follows it.  Same Axis words,
-// nothing new live across the walk.  Measured per kind (ms per step, one box, interleaved runs of
-// the parent's library and each variant, DESIGN.md section 4, round 12, profiles/r12_prefix_ab.txt):
-// in the bounce walks (kRunBounce) Z1 1.560-1.572 against 1.604-1.612, C2 and C4 unchanged: on.  In
-// k_frame0's FindNearest (kRunFrameNearest) C1 0.4458-0.4524 in thirteen runs against 0.4524-0.4593
-// in eight: on, although the walk's iterations per wave are unchanged (the CPU model moves no
-// primary walk) and the counters show 16 % fewer vector memory reads at the same brick loads, that
-// is fewer scratch reloads: the gain is the register allocation around the changed skip.  In k_frame0's shadow walks on top of their
-// gate C1 0.4526-0.4622 against 0.4524-0.4593, without the gate 0.4612-0.4624 in two passes and
-// 0.4580-0.4653 in three (19 spilled VGPRs instead of 17): off.  In the other FindNearest kernels
-// (kRunNearest) C2 2.164-2.180 against 2.127-2.168, in the tile shadow walkers (kRunShadow) with or
-// without their gate and in the shadow pool nothing outside the parent's ranges on C2, C3, C4 and
-// Z1: off.  As shipped against the parent: C1 0.4399-0.4443 / 0.4489-0.4577, C2 2.143-2.170 /
-// 2.194-2.199, C3 3.296-3.310 / 3.324-3.335, Z1 1.571-1.599 / 1.601-1.627 (eight runs), C4
-// unchanged.  VPX_SKIP_PRE=1 sets the bit for every kind, 0 for none; VPX_PRE_<KIND> one kind's.
-#ifdef VPX_SKIP_PRE
-#define VPX_RUN_PRE(on) ((VPX_SKIP_PRE ? 1u : 0u) << 16)
-#else
-#define VPX_RUN_PRE(on) ((on) << 16)
-#endif
-#ifndef VPX_PRE_NEAREST
-#define VPX_PRE_NEAREST 0u
-#endif
-#ifndef VPX_PRE_BOUNCE
-#define VPX_PRE_BOUNCE 1u
-#endif
-#ifndef VPX_PRE_SHADOW
-#define VPX_PRE_SHADOW 0u
-#endif
-#ifndef VPX_PRE_FRAME_NEAREST
-#define VPX_PRE_FRAME_NEAREST 1u
-#endif
-#ifndef VPX_PRE_FRAME_SHADOW
-#define VPX_PRE_FRAME_SHADOW 0u
-#endif
-#ifndef VPX_PRE_SHADOW_POOL
-#define VPX_PRE_SHADOW_POOL 0u
-#endif
-#ifndef VPX_RUN_NEAREST
-#define VPX_RUN_NEAREST (3u | 3u << 8 | 1u << 17 | 1u << 18 | VPX_RUN_AXIS | VPX_RUN_LOCAL(1u) | VPX_RUN_GATE(0u) | VPX_RUN_SEG3(0u) | VPX_RUN_PRE(VPX_PRE_NEAREST))
-#endif
-constexpr uint32_t kRunNearest = VPX_RUN_NEAREST;
-#ifndef VPX_RUN_BOUNCE
-#define VPX_RUN_BOUNCE (4u | 1u << 8 | 0u << 17 | 1u << 18 | VPX_RUN_AXIS | VPX_RUN_LOCAL(0u) | VPX_RUN_GATE(0u) | VPX_RUN_PRE(VPX_PRE_BOUNCE))
-#endif
-constexpr uint32_t kRunBounce = VPX_RUN_BOUNCE;
-#ifndef VPX_RUN_SHADOW
-#define VPX_RUN_SHADOW (3u | 1u << 8 | 1u << 17 | 0u << 18 | VPX_RUN_AXIS | VPX_RUN_LOCAL(1u) | VPX_RUN_GATE(1u) | VPX_RUN_SEG3(0u) | VPX_RUN_PRE(VPX_PRE_SHADOW))
-#endif
-constexpr uint32_t kRunShadow = VPX_RUN_SHADOW;
-// Round 5 (ms per step, three interleaved runs, tools/gpu_ab.sh): FindNearest runs of 3 cells in
-// three passes instead of two, C1 0.5419-0.5446 vs 0.5491-0.5496, C3 3.57 either way (four
-// passes 0.5424-0.5459; runs of 4 in three passes 0.5462-0.5497); k_frame0's shadow walks in two
-// passes on top, C1 0.5413-0.5431 (its own word: the other shadow walkers with two passes, C2
-// 2.466-2.480 vs 2.427-2.452).
-// k_frame0's FindNearest (7 waves/SIMD, round 5): runs of 3 cells in four passes, C1
-// 0.5433-0.5444 vs 0.5456-0.5482 ms in three, then 0.5427-0.5457 vs 0.5447-0.5484 (two boxes,
-// three interleaved runs each); five passes 0.5464-0.5474, runs of 2 in four 0.5428-0.5472.
-#ifndef VPX_RUN_FRAME_NEAREST
-#define VPX_RUN_FRAME_NEAREST (3u | 4u << 8 | 1u << 17 | 1u << 18 | VPX_RUN_AXIS | VPX_RUN_LOCAL(1u) | VPX_RUN_GATE(0u) | VPX_RUN_SEG3(0u) | VPX_RUN_PRE(VPX_PRE_FRAME_NEAREST))
-#endif
-constexpr uint32_t kRunFrameNearest = VPX_RUN_FRAME_NEAREST;
-// At 7 waves/SIMD the frame's shadow walks take the two-compare step too: C1 0.5418-0.5489 vs
-// 0.5456-0.5539 ms (seven interleaved runs, all won; three passes 0.5479-0.5591).  Round 10: with
-// the gate a stepping lane needs several brick loads before its first skip, and three passes
-// win: C1 0.4514-0.4522 vs 0.4560-0.4626 ms in two (three interleaved runs each).
-#ifndef VPX_RUN_FRAME_SHADOW
-#define VPX_RUN_FRAME_SHADOW (3u | 3u << 8 | 1u << 17 | 1u << 18 | VPX_RUN_AXIS | VPX_RUN_LOCAL(1u) | VPX_RUN_GATE(1u) | VPX_RUN_SEG3(0u) | VPX_RUN_PRE(VPX_PRE_FRAME_SHADOW))
-#endif
-constexpr uint32_t kRunFrameShadow = VPX_RUN_FRAME_SHADOW;
-// The pools' walks (k_nearest_pool, k_shadow_pool: 96 VGPRs at 5 waves/SIMD) have their own
-// words (A/B overrides: VPX_*_POOL).  With the pool's registers the shadow walks take the
-// two-compare step without spilling: C3 3.684-3.719 vs 3.724-3.756 ms (three interleaved runs,
-// round 3; skip weight 2 / 8 or skip minimum 2 on top: 3.70-3.73 / 3.70-3.72 / 3.77-3.78).
-// The bounce pool takes the bounce words (kRunBounce, kSkipwBounce, kMincBounce): seg2, skip
-// weight 1 / 4, runs of 3 cells in two passes measured C2 2.63-2.66 / 2.60-2.64 / 2.66-2.75 /
-// 2.65-2.71 vs 2.59-2.65 ms, and re-checked at three lanes in round 5 (within noise).
-#ifndef VPX_RUN_SHADOW_POOL
-#define VPX_RUN_SHADOW_POOL (3u | 1u << 8 | 1u << 17 | 1u << 18 | VPX_RUN_AXIS | VPX_RUN_LOCAL(1u) | VPX_RUN_GATE(0u) | VPX_RUN_SEG3(0u) | VPX_RUN_PRE(VPX_PRE_SHADOW_POOL))
-#endif
-#ifndef VPX_SKIPW_SHADOW_POOL
-#define VPX_SKIPW_SHADOW_POOL 4u
-#endif
-#ifndef VPX_MINC_SHADOW_POOL
-#define VPX_MINC_SHADOW_POOL 1u
-#endif
-constexpr uint32_t kRunShadowPool = VPX_RUN_SHADOW_POOL, kSkipwShadowPool = VPX_SKIPW_SHADOW_POOL,
-                   kMincShadowPool = VPX_MINC_SHADOW_POOL;
+// plain cell steps — instead of inside every step iteration of the wave.  When the wave
+// skips, how far a lane runs on one brick load and which form of the skip it takes are the walk
+// kind's fields (vpx_walk_kinds.hpp).
 #ifdef VPX_ASM_MARKS  // analysis builds only: label the walk phases in the ISA listing
 #define VPX_MARK(s) asm volatile("; MARK " s)
 #else
@@ -696,9 +503,9 @@ __device__ __forceinline__ void frame_phase(int k) {
 #define VPX_FRAME_PHASE(k) VPX_MARK("frame " #k)
 #endif
 
-// Lane modes: kStep wants a cell step, kSkip an empty-box skip (the distance-field cube
-// of its brick, skip::df_box, through skip::skip_box_lean), kMiss / kHit are done.
-// Phases are wave-uniform: cell steps while enough lanes want one (see SKIPW), then the
+// Lane modes: kStep wants a cell step, kSkip an empty-box skip (its brick's box from the axis
+// planes, skip::df_box_axis, through skip::skip_box_lean), kMiss / kHit are done.
+// Phases are wave-uniform: cell steps while enough lanes want one (KIND::skipw), then the
 // waiting lanes skip together.  Each lane runs exactly skip::walk_skip's sequence (the
 // reference's cells with the reference's floats).
 // POOL (the bounce pool, k_nearest_pool): the lanes' modes come in and go out through *pmode
@@ -714,27 +521,17 @@ constexpr int kWalkStep = 0, kWalkSkip = 1, kWalkMiss = 2, kWalkHit = 3;
 __device__ __forceinline__ int stepped_axis(const skip::Walk& w, uint32_t ox, uint32_t oy) {
     return w.X != ox ? 0 : (w.Y != oy ? 1 : 2);
 }
-template <int PHK, uint32_t SKIPW, uint32_t MINC, uint32_t RUN, bool POOL = false, bool REC = false>
+template <class KIND, bool POOL = false, bool REC = false>
 __device__ __forceinline__ bool walk_wave(const skip::GridView& g, skip::Walk& w, float bound, uint32_t& cells,
                                           int* pmode = nullptr, uint32_t leave = 65u, int* plast = nullptr) {
     enum : int { kStep = kWalkStep, kSkip = kWalkSkip, kMiss = kWalkMiss, kHit = kWalkHit };
-    constexpr int kRun = (int)(RUN & 255u);
-    constexpr int kPasses = (int)((RUN >> 8) & 255u);
-    constexpr bool kPre = (RUN >> 16) & 1u;  // the skip's plain-step prefix (skip::skip_box_lean's PRE)
-    constexpr bool kSeg2Branch = (RUN >> 17) & 1u;
-    constexpr bool kMin2 = (RUN >> 18) & 1u;  // step1's two-compare axis choice (vpx_skip.hpp)
-    constexpr bool kAxis = (RUN >> 19) & 1u;  // boxes from the axis planes (skip::classify_axis_o)
-    constexpr uint32_t kMinLen = (RUN >> 20) & 15u;
-    constexpr bool kWide = (RUN >> 24) & 1u;  // ... widened along the second axis (skip::wid_dfw)
-    constexpr bool kLocal = (RUN >> 25) & 1u;  // the skip phase's axes behind a barrier
-    constexpr bool kGate = (RUN >> 26) & 1u;   // the maturity gate on class 2 (skip::gate_open)
-    constexpr uint32_t kGateG = (RUN >> 27) & 3u, kGateN = 4u << ((RUN >> 29) & 3u);
-    constexpr int kMore = ((RUN >> 31) & 1u) && kSeg2Branch ? VPX_SEG_MORE : 0;  // further lean segments
-    static_assert(!kWide || kAxis, "walk_wave: wide boxes are axis boxes");
-    static_assert(SKIPW > 0 && kRun > 0 && kPasses > 0, "walk_wave: skip weight, run cap and passes");
-    static_assert(!kAxis || kMinLen > 0, "walk_wave: the axis boxes' minimum length");
-    // the ray's plane: its octant's, or its (octant, dominant axis)'s
-    const uint32_t opar = skip::plane_parent(g, kAxis ? (w.osh >> 3) * 3u + skip::dom_axis(w) : w.osh >> 3);
+    constexpr int kRun = (int)KIND::run, kPasses = (int)KIND::passes;
+    static_assert(KIND::skipw > 0 && kRun > 0 && kPasses > 0, "walk_wave: skip weight, run cap and passes");
+    static_assert(KIND::minlen > 0, "walk_wave: the axis boxes' minimum length");
+    static_assert(KIND::gate_g <= 3 && KIND::gate_n >= 4 && KIND::gate_n <= 32 && !(KIND::gate_n & (KIND::gate_n - 1)),
+                  "walk_wave: the gate's exponent margin and event count (skip::gate_word's ranges)");
+    // the ray's plane: its (octant, dominant axis)'s
+    const uint32_t opar = skip::plane_parent(g, (w.osh >> 3) * 3u + skip::dom_axis(w));
     int mode = POOL ? *pmode : kStep;
     int last = REC ? *plast : -1;
     VPX_PH(uint64_t cs = 0, ck = 0, ns = 0, nk = 0, ls = 0, lk = 0, fb = 0, cf = 0;)
@@ -744,13 +541,13 @@ __device__ __forceinline__ bool walk_wave(const skip::GridView& g, skip::Walk& w
             const uint64_t stepping = __ballot(mode == kStep);
             if (!stepping) break;
             // cost-weighted: a skip phase costs several step phases, so keep stepping while
-            // steppers x SKIPW >= waiting skippers
+            // steppers x skipw >= waiting skippers
             const uint32_t nskip = (uint32_t)__popcll(__ballot(mode == kSkip));
-            if ((uint32_t)__popcll(stepping) * SKIPW < nskip) break;
+            if ((uint32_t)__popcll(stepping) * KIND::skipw < nskip) break;
             if (POOL && 64u - (uint32_t)__popcll(stepping) - nskip >= leave) goto pool_out;
             VPX_PH(++ns; ls += __popcll(stepping); cf += __popcll(__ballot(mode >= kMiss));)  // cf: finished lanes per step iteration
             VPX_MARK("step body");
-            // Brick runs: the class of a cell is a function of its brick's plane byte and cell
+            // Brick runs: the class of a cell is a function of its brick's plane word and cell
             // mask only, so once they are loaded a lane keeps stepping on the register copy
             // while it stays in that brick — the cell mask (class 1) or "all empty" (class 3)
             // decides each cell exactly as classify would — and reloads only when it crosses
@@ -761,12 +558,11 @@ __device__ __forceinline__ bool walk_wave(const skip::GridView& g, skip::Walk& w
                     if (!(w.t < bound)) {
                         mode = kMiss;
                     } else {
-                        int cls = kAxis ? skip::classify_axis_o<MINC, kAxis ? kMinLen : 1u>(w, g, opar)
-                                        : skip::classify_dfp_o<MINC>(w, g, opar);
-                        if (kGate) {  // an immature lane steps through its empty brick (the RUN word's gate)
+                        int cls = skip::classify_axis_o<KIND::minc, KIND::minlen>(w, g, opar);
+                        if (KIND::gate) {  // an immature lane steps through its empty brick
                             float dx = w.dx, dy = w.dy, dz = w.dz;
                             asm volatile("" : "+v"(dx), "+v"(dy), "+v"(dz));  // the tdeltas' compares stay here
-                            cls = (cls == 2 && !skip::gate_open(w.tx, w.ty, w.tz, dx, dy, dz, kGateG, kGateN)) ? 3 : cls;
+                            cls = (cls == 2 && !skip::gate_open(w.tx, w.ty, w.tz, dx, dy, dz, KIND::gate_g, KIND::gate_n)) ? 3 : cls;
                         }
                         // the class's outcome by selects: 0 = the solid cell (visited, hit), 2 =
                         // skip; 1 / 3 visit the cell and run on in the brick
@@ -781,7 +577,7 @@ __device__ __forceinline__ bool walk_wave(const skip::GridView& g, skip::Walk& w
                                 // merges): left the grid -> miss; left the brick (or the run's
                                 // cap) -> the next pass loads; bound reached -> miss; else the
                                 // cell is visited, a solid one ends the walk
-                                const bool ing = skip::step1<kMin2>(w, g.n);
+                                const bool ing = skip::step1<KIND::min2>(w, g.n);
                                 if (REC) last = stepped_axis(w, ox, oy);
                                 const bool inb = r + 1 < kRun && ((w.X ^ ox) | (w.Y ^ oy) | (w.Z ^ oz)) <= 3u;
                                 const bool inbound = w.t < bound;
@@ -808,15 +604,11 @@ __device__ __forceinline__ bool walk_wave(const skip::GridView& g, skip::Walk& w
         VPX_MARK("skip phase");
         if (mode == kSkip) {
             uint32_t lo[3], hi[3];
-            if (kAxis) {
-                float dx = w.dx, dy = w.dy, dz = w.dz;
-                if (kLocal) asm volatile("" : "+v"(dx), "+v"(dy), "+v"(dz));  // not hoisted (the RUN word's local)
-                const uint32_t axis = skip::dom_axis(dx, dy, dz), sec = kWide ? skip::sec_axis(axis, dx, dy, dz) : 3u;
-                skip::df_box_axis(w, g.n, skip::cube_dfp(w), skip::len_dfa(w), axis, lo, hi, sec, kWide ? skip::wid_dfw(w, axis, sec) : 0u);
-            } else {
-                skip::df_box(w, g.n, skip::cube_dfp(w), lo, hi);
-            }
-            const int sr = skip::skip_box_lean<kSeg2Branch, kMore, kPre>(w, lo, hi, bound, cells);  // 2 (refused): a plain step
+            float dx = w.dx, dy = w.dy, dz = w.dz;
+            if (KIND::local) asm volatile("" : "+v"(dx), "+v"(dy), "+v"(dz));  // the axes' compares are not hoisted
+            const uint32_t axis = skip::dom_axis(dx, dy, dz), sec = skip::sec_axis(axis, dx, dy, dz);
+            skip::df_box_axis(w, g.n, skip::cube_dfp(w), skip::len_dfa(w), axis, lo, hi, sec, skip::wid_dfw(w, axis, sec));
+            const int sr = skip::skip_box_lean<KIND::seg2, 0, KIND::pre>(w, lo, hi, bound, cells);  // 2 (refused): a plain step
             VPX_MARK("skip end");
             VPX_PH(fb += __popcll(__ballot(sr == 2));)
             if (sr == 1) {
@@ -824,7 +616,7 @@ __device__ __forceinline__ bool walk_wave(const skip::GridView& g, skip::Walk& w
             } else {
                 ++cells;  // visit the landing cell, then take the leaving event
                 const uint32_t ox = w.X, oy = w.Y;
-                mode = skip::step1<kMin2>(w, g.n) ? kStep : kMiss;
+                mode = skip::step1<KIND::min2>(w, g.n) ? kStep : kMiss;
                 if (REC) last = stepped_axis(w, ox, oy);
             }
         }
@@ -837,15 +629,15 @@ __device__ __forceinline__ bool walk_wave(const skip::GridView& g, skip::Walk& w
     if (REC) *plast = last;
 #ifdef VPX_PHASE_PROF
     if ((threadIdx.x & 63) == __builtin_amdgcn_readfirstlane(threadIdx.x & 63)) {
-        atomicAdd(&g_phase[PHK + 0], cs);
-        atomicAdd(&g_phase[PHK + 1], ck);
-        atomicAdd(&g_phase[PHK + 2], ns);
-        atomicAdd(&g_phase[PHK + 3], nk);
-        atomicAdd(&g_phase[PHK + 4], ls);
-        atomicAdd(&g_phase[PHK + 5], lk);
-        atomicAdd(&g_phase[PHK + 6], 1ull);
-        atomicAdd(&g_phase[PHK + 7], fb);
-        atomicAdd(&g_phase[PHK + 8], cf);
+        atomicAdd(&g_phase[KIND::phase_slot + 0], cs);
+        atomicAdd(&g_phase[KIND::phase_slot + 1], ck);
+        atomicAdd(&g_phase[KIND::phase_slot + 2], ns);
+        atomicAdd(&g_phase[KIND::phase_slot + 3], nk);
+        atomicAdd(&g_phase[KIND::phase_slot + 4], ls);
+        atomicAdd(&g_phase[KIND::phase_slot + 5], lk);
+        atomicAdd(&g_phase[KIND::phase_slot + 6], 1ull);
+        atomicAdd(&g_phase[KIND::phase_slot + 7], fb);
+        atomicAdd(&g_phase[KIND::phase_slot + 8], cf);
     }
 #endif
     return mode == kHit;
@@ -1138,7 +930,7 @@ __device__ __forceinline__ void prof_visit(int what, bool pass) {
 #else
 #define VPX_PROF_VISIT(what, pass)
 #endif
-template <uint32_t SKIPW = kSkipwNearest, uint32_t MINC = kMincNearest, uint32_t RUN = kRunNearest>
+template <class KIND = NearestWalk>
 __device__ __forceinline__ int32_t find_nearest(const SceneView& sv, Ray& r, Counters& k) {
     int32_t vox = -2;
     ++k.nearest;
@@ -1163,7 +955,7 @@ __device__ __forceinline__ int32_t find_nearest(const SceneView& sv, Ray& r, Cou
             if (!ok) return true;
             w = to_walk(s);
         }
-        if (walk_wave<0, SKIPW, MINC, RUN>(grid_view(g), w, r.t, k.cells)) {
+        if (walk_wave<KIND>(grid_view(g), w, r.t, k.cells)) {
             r.t = w.t;
             hx = w.X, hy = w.Y, hz = w.Z;
             vox = (int32_t)i;
@@ -1227,7 +1019,7 @@ struct HitCell {
     int32_t axis;  // of the last advance before the hit; -1: the hit cell is the walk's first cell
     int32_t step;  // that axis' step, +1 / -1
 };
-template <uint32_t SKIPW = kSkipwNearest, uint32_t MINC = kMincNearest, uint32_t RUN = kRunNearest, bool CELLS = false>
+template <class KIND = NearestWalk, bool CELLS = false>
 __device__ __forceinline__ int32_t find_nearest_filtered(const SceneView& sv, Ray& r, Counters& k, uint32_t first,
                                                          uint32_t mlo, uint32_t mhi, bool shapes, HitCell* hc = nullptr) {
     int32_t vox = -2;
@@ -1258,13 +1050,13 @@ __device__ __forceinline__ int32_t find_nearest_filtered(const SceneView& sv, Ra
         int last = -1;
         uint32_t cell = kNone;
         for (;;) {
-            walk_wave<0, SKIPW, MINC, RUN, true, CELLS>(gv, w, r.t, k.cells, &mode, 65u, &last);
+            walk_wave<KIND, true, CELLS>(gv, w, r.t, k.cells, &mode, 65u, &last);
             bool on = false;
             if (mode == kWalkHit) {
                 cell = gv.cells[(uint64_t)w.X + (uint64_t)w.Y * gv.n + (uint64_t)w.Z * ((uint64_t)gv.n * gv.n)];
                 if (cell >= mlo && cell <= mhi) {  // scene.cpp:826: passed through
                     const uint32_t ox = w.X, oy = w.Y;
-                    on = skip::step1<((RUN >> 18) & 1u) != 0u>(w, gv.n);
+                    on = skip::step1<KIND::min2>(w, gv.n);
                     if (CELLS) last = stepped_axis(w, ox, oy);
                     mode = on ? kWalkStep : kWalkMiss;
                 }
@@ -1337,7 +1129,7 @@ __device__ __forceinline__ vpx_hit_cell hit_cell_record(const SceneView& sv, int
 // later volumes through the TLAS (or linearly), then the shapes — so the same winner, t and
 // counts as find_nearest; the FindNearest call itself was counted by the world pass.
 // Returns whether the record changed (a later volume or a shape won: r.t, r.N, r.mat, *vox).
-template <uint32_t SKIPW = kSkipwNearest, uint32_t MINC = kMincNearest, uint32_t RUN = kRunNearest>
+template <class KIND = NearestWalk>
 __device__ __forceinline__ bool find_nearest_rest(const SceneView& sv, Ray& r, Counters& k, int32_t* vox_io) {
     int32_t vox = *vox_io;
     const int32_t vox0 = vox;
@@ -1362,7 +1154,7 @@ __device__ __forceinline__ bool find_nearest_rest(const SceneView& sv, Ray& r, C
             if (!ok) return true;
             w = to_walk(s);
         }
-        if (walk_wave<0, SKIPW, MINC, RUN>(grid_view(g), w, r.t, k.cells)) {
+        if (walk_wave<KIND>(grid_view(g), w, r.t, k.cells)) {
             r.t = w.t;
             hx = w.X, hy = w.Y, hz = w.Z;
             vox = (int32_t)i;
@@ -1391,7 +1183,7 @@ __device__ __forceinline__ bool find_nearest_rest(const SceneView& sv, Ray& r, C
             return false;
         };
         auto done = [&](skip::Walk& w, uint32_t vi) {
-            if (walk_wave<0, SKIPW, MINC, RUN>(grid_view(g), w, r.t, k.cells)) {
+            if (walk_wave<KIND>(grid_view(g), w, r.t, k.cells)) {
                 r.t = w.t;
                 hx = w.X, hy = w.Y, hz = w.Z;
                 vox = (int32_t)vi;
@@ -1454,7 +1246,7 @@ __device__ __forceinline__ bool is_occluded(const SceneView& sv, const Ray& r, C
         if (!dda_setup(vol, g.n, o, s)) return true;
         skip::Walk w = to_walk(s);
         // first solid cell with t < bound: occluded, the reference returns (no later volume)
-        occ = walk_wave<16, kSkipwShadow, kMincShadow, kRunShadow>(grid_view(g), w, r.t, k.cells);
+        occ = walk_wave<ShadowWalk>(grid_view(g), w, r.t, k.cells);
         return !occ;
     };
     for (uint32_t i = first; i < sv.num_volumes && !occ; ++i) visit(i);

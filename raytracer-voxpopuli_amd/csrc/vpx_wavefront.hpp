@@ -847,12 +847,12 @@ __device__ __forceinline__ uint32_t block_scan(uint32_t cnt, uint32_t& total, ui
     return base + off;
 }
 
-template <uint32_t SKIPW = kSkipwNearest, uint32_t MINC = kMincNearest, uint32_t RUN = kRunNearest>
+template <class KIND = NearestWalk>
 __device__ __forceinline__ void nearest_record(SceneView sv, const PathRay& pr, uint32_t p, Ray& r, Counters& k) {
     r.t = kBig;
     r.mat = kNone;
     r.N = mk(0.f, 0.f, 0.f);
-    const int32_t vox = find_nearest<SKIPW, MINC, RUN>(sv, r, k);
+    const int32_t vox = find_nearest<KIND>(sv, r, k);
     pr.H[pr.at(p)] = make_float4(r.t, r.N.x, r.N.y, r.N.z);
     pr.HM[pr.at(p)] = r.mat | ((uint32_t)(vox + 2) << 8) | (r.inside ? 0x80000000u : 0u);
 }
@@ -897,12 +897,12 @@ __device__ __forceinline__ void nearest_end_1v(const SceneView& sv, const PathRa
     nearest_end_v(*vol, g.cells, g.n, w, p, wk, hit);
 }
 
-template <uint32_t SKIPW = kSkipwNearest, uint32_t MINC = kMincNearest, uint32_t RUN = kRunNearest>
+template <class KIND = NearestWalk>
 __device__ __forceinline__ void nearest_record_1v(const SceneView& sv, const PathRay& w, uint32_t p, Counters& k) {
     bool hit = false;
     skip::Walk wk;
     if (nearest_begin_1v(sv, w, p, k, wk))
-        hit = walk_wave<0, SKIPW, MINC, RUN>(grid_view(sv.grids[uni_ptr(&sv.volumes[0])->grid_id]), wk, kBig, k.cells);
+        hit = walk_wave<KIND>(grid_view(sv.grids[uni_ptr(&sv.volumes[0])->grid_id]), wk, kBig, k.cells);
     nearest_end_1v(sv, w, p, wk, hit);
 }
 
@@ -955,7 +955,7 @@ __device__ __forceinline__ bool meets_later_volume(const SceneView& sv, f3 o, f3
 // written to HBM and flagged in amask (one ballot word per wave, unused at depth 0) for the
 // instance pass, which continues FindNearest and shades only them.  C4: ~15 % of the primary
 // rays reach the instance lattice's box.
-template <bool ONE, bool SHADE, uint32_t RUN = kRunNearest, bool DEFER = false>
+template <bool ONE, bool SHADE, class KIND = NearestWalk, bool DEFER = false>
 __device__ __forceinline__ void primary_tile(const SceneView& sv, const FrameArgs& f, const WaveBufs& w,
                                              HeadLds<SHADE>& L, unsigned long long* __restrict__ ctr) {
     uint32_t* sh = L.sh;
@@ -1017,7 +1017,7 @@ __device__ __forceinline__ void primary_tile(const SceneView& sv, const FrameArg
     if (threadIdx.x < total) {
         const uint32_t q = lst[threadIdx.x];
         if (ONE) {
-            nearest_record_1v<kSkipwNearest, kMincNearest, RUN>(sv, pr, q, k);
+            nearest_record_1v<KIND>(sv, pr, q, k);
         } else {
             const float4 o = pr.O[pr.at(q)], d = pr.D[pr.at(q)];
             Ray r;
@@ -1058,7 +1058,7 @@ template <bool ONE, bool SHADE = false, bool X86 = false, bool DEFER = false>
 __global__ __launch_bounds__(256) VPX_WPE(ONE ? VPX_WPE_NEAREST : VPX_WPE_MULTI_NEAREST) void k_primary(SceneView sv, FrameArgs f, WaveBufs w,
                                                  unsigned long long* __restrict__ ctr) {
     __shared__ HeadLds<SHADE> L;
-    primary_tile<ONE, SHADE, kRunNearest, DEFER>(arith_view<X86>(sv), f, w, L, ctr);
+    primary_tile<ONE, SHADE, NearestWalk, DEFER>(arith_view<X86>(sv), f, w, L, ctr);
 }
 
 // Level l + 1's live list from level l's shade bits: 256 mask words (16 k list positions) per
@@ -1243,7 +1243,7 @@ __global__ __launch_bounds__(256) VPX_WPE(VPX_WPE_MULTI_NEAREST) void k_nearest_
             r.O = mk(o.x, o.y, o.z);
             r.D = mk(d.x, d.y, d.z);
             r.inside = (__float_as_uint(d.w) & kInside) != 0u;
-            nearest_record<kSkipwBounce, kMincBounce, kRunBounce>(sv, PathRay{w.O, w.D, w.H, w.HM, 0u}, q, r, k);
+            nearest_record<BounceWalk>(sv, PathRay{w.O, w.D, w.H, w.HM, 0u}, q, r, k);
         }
     }
     flush_counters(k, 0u, ctr, VPX_STAGE_BOUNCE);
@@ -1319,7 +1319,7 @@ __global__ __launch_bounds__(kPoolWg) VPX_WPE(VPX_WPE_BOUNCE) void k_nearest_poo
             avail -= take;
         }
         if (!__ballot(q != ~0u)) break;  // the list is done and every lane is done
-        walk_wave<0, kSkipwBounce, kMincBounce, kRunBounce, true>(gv, wk, kBig, k.cells, &mode,
+        walk_wave<BounceWalk, true>(gv, wk, kBig, k.cells, &mode,
                                                                    more ? kPoolLeave : 65u);
     }
     flush_counters(k, 0u, ctr, VPX_STAGE_BOUNCE);
@@ -1341,14 +1341,11 @@ __device__ __forceinline__ void mark_occluded(const WaveBufs& w, uint64_t slot, 
 }
 
 // occ: the fused tails' LDS bitmap of occluded slots (one tile per workgroup), else nullptr.
-// RUN: the shadow walks' RUN word (vpx_trace.hpp kRun*).  k_frame0's shadow walks (80 VGPRs)
-// keep kRunShadow: the two-compare step (5 spilled VGPRs instead of 3) measured C1
-// 0.5824-0.5839 vs 0.5833-0.5859 ms and runs of 4 cells 0.5843-0.5873 (round 3, three
-// interleaved runs each: noise / slower).
+// KIND: the shadow walks' kind (vpx_walk_kinds.hpp): ShadowWalk, or k_frame0's FrameShadowWalk.
 // p: this thread's path (the tile's, or a live-list entry; >= w.P: none).
 // l16 (k_frame0: one slot per path, the tile's own paths): the list as 16-bit offsets into the
 // tile in the caller's LDS instead of 32-bit entries in the dynamic LDS.
-template <bool ONE, uint32_t RUN = kRunShadow>
+template <bool ONE, class KIND = ShadowWalk>
 __device__ __forceinline__ void shadow_tile(const SceneView& sv, const WaveBufs& w, unsigned long long* __restrict__ ctr,
                                             uint32_t* occ, uint32_t p, uint16_t* l16 = nullptr) {
     __shared__ uint32_t sh[4];
@@ -1406,7 +1403,7 @@ __device__ __forceinline__ void shadow_tile(const SceneView& sv, const WaveBufs&
                 Dda s;
                 if (dda_setup(*vol, g.n, o, s)) {
                     skip::Walk wk = to_walk(s);
-                    hit = walk_wave<16, kSkipwShadow, kMincShadow, RUN>(grid_view(g), wk, so.w, k.cells);
+                    hit = walk_wave<KIND>(grid_view(g), wk, so.w, k.cells);
                 }
             }
             asm volatile("" ::: "memory");
@@ -1572,7 +1569,7 @@ __global__ __launch_bounds__(kPoolWg) VPX_WPE(VPX_WPE_SPOOL) void k_shadow_pool(
             walked += take;  // IsOccluded calls (a scalar: no register across the walks)
         }
         if (!__ballot(e != ~0u)) break;
-        walk_wave<16, kSkipwShadowPool, kMincShadowPool, kRunShadowPool, true>(gv, wk, bound, k.cells, &mode,
+        walk_wave<ShadowPoolWalk, true>(gv, wk, bound, k.cells, &mode,
                                                                    more ? kPoolLeave : 65u);
     }
     k.shadow = lane == 0u ? walked : 0u;
@@ -1597,10 +1594,6 @@ __global__ __launch_bounds__(kPoolWg) VPX_WPE(VPX_WPE_SPOOL) void k_shadow_pool(
 #ifndef VPX_INST_CULL
 #define VPX_INST_CULL 1
 #endif
-// The instance grids' shadow walks take the shadow words with skip minimum 2 (cubes of one
-// brick stepped through): C4 42.43-42.51 vs 42.71-42.96 ms (five interleaved runs, all won; 3:
-// 42.82-42.90, 4: 43.05-43.26; two passes per iteration 43.1-43.3, the two-compare step 42.7-42.8).
-constexpr uint32_t kMincInstShadow = 2u;
 __device__ __forceinline__ bool occluded_instances(const SceneView& sv, const float4* vb, const Ray& r, Counters& k) {
     const uint32_t nv = sv.num_volumes;
     uint64_t cand = 0ull;
@@ -1632,7 +1625,7 @@ __device__ __forceinline__ bool occluded_instances(const SceneView& sv, const fl
             return false;
         };
         auto done = [&](skip::Walk& wk, uint32_t) {
-            if (walk_wave<16, kSkipwShadow, kMincInstShadow, kRunShadow>(grid_view(g), wk, r.t, k.cells)) {
+            if (walk_wave<InstShadowWalk>(grid_view(g), wk, r.t, k.cells)) {
                 occ = true;
                 rest = 0ull;  // the reference returns at the first occluder
             }
@@ -1669,7 +1662,7 @@ __device__ __forceinline__ bool occluded_instances(const SceneView& sv, const fl
         Dda s;
         if (!dda_setup(vol, g.n, o, s)) continue;
         skip::Walk wk = to_walk(s);
-        occ = walk_wave<16, kSkipwShadow, kMincInstShadow, kRunShadow>(grid_view(g), wk, r.t, k.cells);
+        occ = walk_wave<InstShadowWalk>(grid_view(g), wk, r.t, k.cells);
     }
     if (occ) return true;
     for (uint32_t i = 0; i < sv.num_spheres; ++i)
@@ -1904,7 +1897,7 @@ __global__ __launch_bounds__(256) VPX_WPE(VPX_WPE_TAIL) void k_tail(SceneView sv
             r.O = mk(o.x, o.y, o.z);
             r.D = mk(d.x, d.y, d.z);
             r.inside = (__float_as_uint(d.w) & kInside) != 0u;
-            nearest_record<kSkipwBounce, kMincBounce, kRunBounce>(sv, pr, p, r, kn);
+            nearest_record<BounceWalk>(sv, pr, p, r, kn);
         }
         const bool cont = shade_path(sv, f, w, pr, p, l, kh);
         const uint32_t slots = w.smask[p] & kSlotBits;
@@ -2066,15 +2059,15 @@ __global__ __launch_bounds__(256) VPX_WPE(ONE ? VPX_WPE_FRAME : VPX_WPE_MULTI_NE
     wl.SD = L.ray + 256 - tb;
     wl.SL = L.ray + 512 - tb;
     if (VIEW >= kFrameGuaranteed) wl.S = 1u;  // frame0_fits: one slot per path
-    primary_tile<ONE, true, kRunFrameNearest>(sv, f, wl, L, ctr);
+    primary_tile<ONE, true, FrameNearestWalk>(sv, f, wl, L, ctr);
     __syncthreads();
     VPX_FRAME_PHASE(4);
 #ifdef VPX_FRAME_P_TILE
-    shadow_tile<ONE, kRunFrameShadow>(sv, wl, ctr, occ, tile_block() * 256u + threadIdx.x, l16);
+    shadow_tile<ONE, FrameShadowWalk>(sv, wl, ctr, occ, tile_block() * 256u + threadIdx.x, l16);
 #else
     uint32_t ps = p;  // re-derived, not kept live across the head (as pt below)
     asm volatile("" : "+v"(ps));
-    shadow_tile<ONE, kRunFrameShadow>(sv, wl, ctr, occ, ps, l16);
+    shadow_tile<ONE, FrameShadowWalk>(sv, wl, ctr, occ, ps, l16);
 #endif
     __syncthreads();
     VPX_FRAME_PHASE(7);

@@ -1,5 +1,5 @@
-"""The walkers' maturity gate and further lean segments (csrc/vpx_trace.hpp, the RUN word's gate and
-seg3 bits), on the GPU.
+"""The walkers' maturity gate and lean skips (csrc/vpx_trace.hpp walk_wave, the walk kinds' gate
+fields in csrc/vpx_walk_kinds.hpp), on the GPU.
 
 A 128^3 town (ground, blocks of different heights between streets, thin walls) under a point and a
 directional light, seen from outside the grid in 64x64 and 128x96 pixels at depth 0, once at depth 2

@@ -1,4 +1,4 @@
-"""The walkers' plain-step prefix (csrc/vpx_trace.hpp, the RUN word's pre bit; csrc/vpx_skip.hpp
+"""The walkers' plain-step prefix (csrc/vpx_walk_kinds.hpp, the walk kinds' pre; csrc/vpx_skip.hpp
 skip_box_lean's PRE), on the GPU, with the library as shipped.
 
 The 128^3 town of test_skip_gate_gpu.py under a point and a directional light: 64x64 and 128x96 at
