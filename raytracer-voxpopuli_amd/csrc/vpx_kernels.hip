@@ -1567,7 +1567,7 @@ int launch_render(vpx_ctx* c, hipStream_t s, vpx_ctx::WaveStore& ws, const Scene
         c->last_frame_kernel = lean ? 2 : 1;
         hipLaunchKernelGGL((lean ? (x86 ? k_frame0<true, MODE, true, kLean> : k_frame0<true, MODE, false, kLean>)
                                  : (x86 ? k_frame0<true, MODE, true, kBase> : k_frame0<true, MODE, false, kBase>)),
-                           grid, block, slds + VPX_FRAME_EXTRA_LDS, s, sv, f, w, c->d_ctr, accum, rgb8, packed);
+                           grid, block, VPX_FRAME_EXTRA_LDS, s, sv, f, w, c->d_ctr, accum, rgb8, packed);
         prof_mark(c, s, -1);
         VPX_HIP(c, hipGetLastError());
         return VPX_OK;

@@ -941,6 +941,51 @@ struct HeadLds {
     uint32_t hm[SHADE ? 256 : 1];
 };
 
+// The head's walk state handed to the walkers (k_frame0): a pixel thread whose Setup3DDDA
+// succeeds has the walk's whole start state in registers, and the walker lane that takes the
+// path after the compaction would derive it again from the LDS ray (the two transforms, the
+// reciprocals with their table loads, Setup3DDDA: 367 VALU instructions and 7 divisions per
+// walker lane in the bench's instance).  The 11 words go through three float4 records of the
+// path that are idle between the head and the walkers' barrier: a, b, c are indexed by the
+// path's place in the tile.  The step signs travel as the bits Setup3DDDA computed (never
+// re-derived from the tdeltas: an infinite or NaN tdelta and a -0 direction keep theirs).
+struct WalkStash {
+    float4 *a, *b, *c;  // (X, Y, Z, sign bits), (t, tmax), (tdelta, -)
+};
+__device__ __forceinline__ void stash_put(const WalkStash& st, uint32_t i, const Dda& s) {
+    const uint32_t sg = (s.sx < 0 ? 1u : 0u) | (s.sy < 0 ? 2u : 0u) | (s.sz < 0 ? 4u : 0u);  // each is 1 or -1
+    st.a[i] = make_float4(__uint_as_float(s.X), __uint_as_float(s.Y), __uint_as_float(s.Z), __uint_as_float(sg));
+    st.b[i] = make_float4(s.t, s.tmax.x, s.tmax.y, s.tmax.z);
+    st.c[i] = make_float4(s.tdelta.x, s.tdelta.y, s.tdelta.z, 0.f);
+}
+__device__ __forceinline__ skip::Walk stash_get(const WalkStash& st, uint32_t i) {
+    const float4 a = st.a[i], b = st.b[i], c = st.c[i];
+    const uint32_t sg = __float_as_uint(a.w);
+    skip::Walk w;
+    w.X = __float_as_uint(a.x), w.Y = __float_as_uint(a.y), w.Z = __float_as_uint(a.z);
+    w.t = b.x;
+    w.tx = b.y, w.ty = b.z, w.tz = b.w;
+    w.dx = c.x, w.dy = c.y, w.dz = c.z;
+    w.sx = sg & 1u ? -1 : 1, w.sy = sg & 2u ? -1 : 1, w.sz = sg & 4u ? -1 : 1;
+    skip::walk_begin(w);
+    return w;
+}
+// nearest_record_1v for a path whose walk state the head stashed: the same walk from the same
+// state, the same count and the same hit record (nearest_end_1v re-reads the ray for the normal).
+// The path is the lane's entry of the walker list: read again after the walk (through an
+// index the compiler takes for a new one), so that neither the path nor the list and stash
+// addresses stay live (spilled) across the walk loops.
+template <class KIND>
+__device__ __forceinline__ void nearest_record_stashed(const SceneView& sv, const PathRay& w, const uint32_t* lst,
+                                                       Counters& k, const WalkStash& st) {
+    ++k.nearest;
+    skip::Walk wk = stash_get(st, w.at(lst[threadIdx.x]));
+    const bool hit = walk_wave<KIND>(grid_view(sv.grids[uni_ptr(&sv.volumes[0])->grid_id]), wk, kBig, k.cells);
+    uint32_t i = threadIdx.x;
+    asm volatile("" : "+v"(i) : : "memory");
+    nearest_end_1v(sv, w, lst[i], wk, hit);
+}
+
 // Whether FindNearest may still find something after volume 0 for a ray whose world walk
 // ended at t: the TLAS root box within its segment [0, t] (conservative, tlas_box), or always
 // when there are shapes, volumes outside the tree or no TLAS (the instance pass's candidates).
@@ -955,9 +1000,13 @@ __device__ __forceinline__ bool meets_later_volume(const SceneView& sv, f3 o, f3
 // written to HBM and flagged in amask (one ballot word per wave, unused at depth 0) for the
 // instance pass, which continues FindNearest and shades only them.  C4: ~15 % of the primary
 // rays reach the instance lattice's box.
-template <bool ONE, bool SHADE, class KIND = NearestWalk, bool DEFER = false>
+// STASH (k_frame0; ONE && SHADE): the pixel threads hand their walk state to the walkers
+// through *st (WalkStash) instead of the walkers setting the walk up again.
+template <bool ONE, bool SHADE, class KIND = NearestWalk, bool DEFER = false, bool STASH = false>
 __device__ __forceinline__ void primary_tile(const SceneView& sv, const FrameArgs& f, const WaveBufs& w,
-                                             HeadLds<SHADE>& L, unsigned long long* __restrict__ ctr) {
+                                             HeadLds<SHADE>& L, unsigned long long* __restrict__ ctr,
+                                             const WalkStash* st = nullptr) {
+    static_assert(!STASH || (ONE && SHADE), "the walk stash is the fused single-volume head's");
     uint32_t* sh = L.sh;
     uint32_t* lst = L.lst;
     const uint32_t tb = tile_block() * 256u;
@@ -1005,9 +1054,19 @@ __device__ __forceinline__ void primary_tile(const SceneView& sv, const FrameArg
                     ++k.nearest;
                     pr.H[pr.at(p)] = make_float4(kBig, 0.f, 0.f, 0.f);
                     pr.HM[pr.at(p)] = kNone;  // vox -2, not inside glass
+                } else if (STASH) {
+                    stash_put(*st, pr.at(p), s);
                 }
             }
         }
+    }
+    // STASH: what the pixel thread carries across the walks in one register (its two one-bit
+    // counts) or not at all (its path, re-derived below): the walk loops have no register to spare
+    uint32_t carried = 0u;
+    if (STASH) {
+        carried = prim | k.nearest << 1;
+        asm volatile("" : "+v"(carried));
+        prim = k.nearest = 0u;
     }
     uint32_t total;
     const uint32_t at = block_scan(walk ? 1u : 0u, total, sh);  // (its barrier orders the LDS writes)
@@ -1016,7 +1075,9 @@ __device__ __forceinline__ void primary_tile(const SceneView& sv, const FrameArg
     VPX_FRAME_PHASE(1);
     if (threadIdx.x < total) {
         const uint32_t q = lst[threadIdx.x];
-        if (ONE) {
+        if (ONE && STASH) {
+            nearest_record_stashed<KIND>(sv, pr, lst, k, *st);
+        } else if (ONE) {
             nearest_record_1v<KIND>(sv, pr, q, k);
         } else {
             const float4 o = pr.O[pr.at(q)], d = pr.D[pr.at(q)];
@@ -1028,28 +1089,37 @@ __device__ __forceinline__ void primary_tile(const SceneView& sv, const FrameArg
         }
     }
     VPX_FRAME_PHASE(2);
+    uint32_t ps = p;  // the thread's own path for the shade
+    if (STASH) {
+        prim = carried & 1u;
+        k.nearest += carried >> 1;
+        ps = tb + threadIdx.x;
+        asm volatile("" : "+v"(ps));
+    }
     flush_counters(k, prim, ctr, VPX_STAGE_PRIMARY);
     if (SHADE) {  // level 0's material switch for this thread's own path (k_primary_shade)
-        __syncthreads();  // the tile's hit records, written by the compacted walkers
+        // the tile's hit records, written by the compacted walkers; with STASH it also orders
+        // the walkers' reads of the stash before the shade's writes to the records that held it
+        __syncthreads();
         VPX_FRAME_PHASE(3);
         Counters ks{0u, 0u, 0u};
         bool defer = false;
-        if (DEFER && p < w.P) {
-            const float4 d = pr.D[pr.at(p)];
+        if (DEFER && ps < w.P) {
+            const float4 d = pr.D[pr.at(ps)];
             if (__float_as_uint(d.w) & kActive) {
-                const float4 o = pr.O[pr.at(p)], h = pr.H[pr.at(p)];
+                const float4 o = pr.O[pr.at(ps)], h = pr.H[pr.at(ps)];
                 defer = meets_later_volume(sv, mk(o.x, o.y, o.z), mk(d.x, d.y, d.z), h.x);
                 if (defer) {  // the instance pass reads the ray and the world's hit record
-                    w.O[p] = o;
-                    w.D[p] = d;
-                    w.H[p] = h;
-                    w.HM[p] = pr.HM[pr.at(p)];
+                    w.O[ps] = o;
+                    w.D[ps] = d;
+                    w.H[ps] = h;
+                    w.HM[ps] = pr.HM[pr.at(ps)];
                 }
             }
         }
-        if (DEFER) put_amask(w, p, defer);
-        const bool cont = defer ? false : shade_path<true>(sv, f, w, pr, p, 0, ks);
-        if (!DEFER && f.max_bounces > 0) put_amask(w, p, cont);
+        if (DEFER) put_amask(w, ps, defer);
+        const bool cont = defer ? false : shade_path<true>(sv, f, w, pr, ps, 0, ks);
+        if (!DEFER && f.max_bounces > 0) put_amask(w, ps, cont);
         flush_counters(ks, 0u, ctr, VPX_STAGE_SHADE);
     }
 }
@@ -1343,11 +1413,14 @@ __device__ __forceinline__ void mark_occluded(const WaveBufs& w, uint64_t slot, 
 // occ: the fused tails' LDS bitmap of occluded slots (one tile per workgroup), else nullptr.
 // KIND: the shadow walks' kind (vpx_walk_kinds.hpp): ShadowWalk, or k_frame0's FrameShadowWalk.
 // p: this thread's path (the tile's, or a live-list entry; >= w.P: none).
-// l16 (k_frame0: one slot per path, the tile's own paths): the list as 16-bit offsets into the
-// tile in the caller's LDS instead of 32-bit entries in the dynamic LDS.
+// lw (k_frame0: one slot per path, the tile's own paths): the list as offsets into the tile,
+// entry i in the .w word of lw[i], instead of 32-bit entries in the dynamic LDS.  k_frame0
+// passes the tile's SL records: put_slot writes 0 there and nobody reads it (resolve_path takes
+// x, y, z), so the list costs no LDS of its own.
+constexpr uint32_t kShadowTileLds = sizeof(uint32_t) * (4u + kLightKeys);  // shadow_tile's own statics: sh, hist
 template <bool ONE, class KIND = ShadowWalk>
 __device__ __forceinline__ void shadow_tile(const SceneView& sv, const WaveBufs& w, unsigned long long* __restrict__ ctr,
-                                            uint32_t* occ, uint32_t p, uint16_t* l16 = nullptr) {
+                                            uint32_t* occ, uint32_t p, float4* lw = nullptr) {
     __shared__ uint32_t sh[4];
     if (occ)
         for (uint32_t i = threadIdx.x; i < w.S * 8u; i += 256u) occ[i] = 0u;  // published by the barriers below
@@ -1376,8 +1449,8 @@ __device__ __forceinline__ void shadow_tile(const SceneView& sv, const WaveBufs&
     const uint32_t tb = tile_block() * 256u;
     {
         uint32_t at = m ? hist[key] + pos : 0u;
-        if (l16) {
-            if (m) l16[at] = (uint16_t)(p - tb);  // slot 0
+        if (lw) {
+            if (m) lw[at].w = __uint_as_float(p - tb);  // slot 0
         } else {
             for (uint32_t b = m; b; b &= b - 1u) lst_dyn[at++] = ((uint32_t)__ffs(b) - 1u) << 27 | p;
         }
@@ -1385,7 +1458,7 @@ __device__ __forceinline__ void shadow_tile(const SceneView& sv, const WaveBufs&
     __syncthreads();
     VPX_FRAME_PHASE(5);
     for (uint32_t i = threadIdx.x; i < total; i += 256u) {
-        const uint32_t e = l16 ? tb + l16[i] : lst_dyn[i];
+        const uint32_t e = lw ? tb + __float_as_uint(lw[i].w) : lst_dyn[i];
         const uint64_t slot = (uint64_t)(e >> 27) * w.P + (e & 0x07ffffffu);
         if (ONE) {
             // Renderer::IsOccluded in the single volume with only the walk state live
@@ -1963,11 +2036,21 @@ constexpr uint32_t kFuseFrameTiles = VPX_FUSE_FRAME_TILES;
 // (round 2: 272) and measured 1.5 % faster than 5 (no spills) with frames in flight
 // (profiles/r03_frame_occupancy_ab.txt).  Round 5: the occluded bitmap sized for its one slot
 // per path and the shadow list as 16-bit tile offsets in static LDS (23168 instead of
-// 24128 bytes per workgroup) let 7 workgroups share a CU's 160 KiB; at 7 (72 VGPRs, 14-19
-// spilled) C1 measured 0.5440-0.5509 vs 0.5478-0.5580 ms at 6 (seven interleaved runs, five
-// won).
+// 24128 bytes per workgroup), meant to let 7 workgroups share a CU's 160 KiB; at 7 (72 VGPRs,
+// 14-19 spilled) C1 measured 0.5440-0.5509 vs 0.5478-0.5580 ms at 6 (seven interleaved runs,
+// five won).  Those runs never had the seventh workgroup: the launch still added the dynamic
+// list's 1024 bytes (24192 per workgroup, 7 x 24192 = 169344 > 163840), and 23168 alone fits
+// seven times only under a 256-byte allocation granule.  Round 14 (kFrame0LdsBudget below)
+// drops the dynamic bytes and moves the list into the SL records: with the seventh workgroup
+// resident C1 measured 0.3981-0.4047 vs the parent's 0.4034-0.4102 ms (eight interleaved runs),
+// and at 6 (80 VGPRs, 5 spilled) with the same LDS 0.4070-0.4107 vs 0.4040-0.4107.
 #ifndef VPX_WPE_FRAME
 #define VPX_WPE_FRAME 7
+#endif
+// The head hands its walk state to the walkers (WalkStash); 0: the walkers set the walk up
+// again (the A/B baseline).
+#ifndef VPX_FRAME_HANDOFF
+#define VPX_FRAME_HANDOFF 1
 #endif
 // The depth-0 frame's path state never leaves the workgroup: a path is shaded, its light
 // resolved and its pixel finished by the same thread, and its shadow slots are walked by the
@@ -2035,6 +2118,21 @@ __device__ __forceinline__ FrameArgs frame0_args(const FrameArgs& f) {
     return v;
 }
 
+// k_frame0's LDS, all of it: this record plus shadow_tile's own statics (kShadowTileLds); its
+// launch passes no dynamic bytes (shadow_tile's lst_dyn is unused with the list in SL.w).
+// Seven workgroups must share a CU's 163840 bytes whatever the allocation granule: a workgroup
+// may take 23040 bytes = 18 x 1280 = 45 x 512 = 90 x 256 (7 x 23040 = 161280); 23168, the
+// round-5 size, rounds to 23552 at 512 (7 x = 164864) and to 24320 at 1280 (7 x = 170240).
+struct Frame0Lds {
+    HeadLds<true> L;     // 14352: sh, the walker list (then forms), O / D / H (then SO / SD / SL), HM (then smask)
+    float4 s_val[256];   // 4096: the walk stash, then LA (a) or leaf of the path's one level
+    float4 s_sm[256];    // 4096: the walk stash, then SM: the pending light
+    uint32_t occ[8];     // 32: one slot per path (S == 1, checked at launch)
+};
+constexpr uint32_t kFrame0LdsBudget = 23040;
+static_assert(sizeof(Frame0Lds) + kShadowTileLds <= kFrame0LdsBudget,
+              "k_frame0: seven workgroups no longer fit a CU's LDS (22576 + 80 = 22656 today)");
+
 template <bool ONE, int MODE, bool X86 = false, int VIEW = kFrameAsGiven>
 __global__ __launch_bounds__(256) VPX_WPE(ONE ? VPX_WPE_FRAME : VPX_WPE_MULTI_NEAREST) void k_frame0(
     SceneView sv_, FrameArgs f_, WaveBufs w, unsigned long long* __restrict__ ctr, float4* __restrict__ accum,
@@ -2042,11 +2140,11 @@ __global__ __launch_bounds__(256) VPX_WPE(ONE ? VPX_WPE_FRAME : VPX_WPE_MULTI_NE
     VPX_FRAME_PHASE(0);
     const SceneView sv = frame0_scene<X86, VIEW>(sv_);
     const FrameArgs f = frame0_args<VIEW>(f_);
-    __shared__ HeadLds<true> L;
-    __shared__ float4 s_val[256];  // LA (a) or leaf of the path's one level
-    __shared__ float4 s_sm[256];   // SM: the pending light
-    __shared__ uint32_t occ[8];      // one slot per path (S == 1, checked at launch)
-    __shared__ uint16_t l16[256];    // the shadow walks' list (shadow_tile)
+    __shared__ Frame0Lds F;
+    HeadLds<true>& L = F.L;
+    float4* const s_val = F.s_val;
+    float4* const s_sm = F.s_sm;
+    uint32_t* const occ = F.occ;
     const uint32_t tb = tile_block() * 256u;
     const uint32_t p = tb + threadIdx.x;
     WaveBufs wl = w;
@@ -2059,15 +2157,20 @@ __global__ __launch_bounds__(256) VPX_WPE(ONE ? VPX_WPE_FRAME : VPX_WPE_MULTI_NE
     wl.SD = L.ray + 256 - tb;
     wl.SL = L.ray + 512 - tb;
     if (VIEW >= kFrameGuaranteed) wl.S = 1u;  // frame0_fits: one slot per path
-    primary_tile<ONE, true, FrameNearestWalk>(sv, f, wl, L, ctr);
+    // the walk stash: the path's own LA / SM records (first written by the level-0 shade, after
+    // the walkers' barrier) and its H record (written by its walker, after the walk)
+    constexpr bool kStash = ONE && VPX_FRAME_HANDOFF;
+    const WalkStash st{L.ray + 512, s_val, s_sm};
+    primary_tile<ONE, true, FrameNearestWalk, false, kStash>(sv, f, wl, L, ctr, &st);
     __syncthreads();
     VPX_FRAME_PHASE(4);
+    float4* const lw = L.ray + 512;  // the shadow list in the SL records' .w (shadow_tile)
 #ifdef VPX_FRAME_P_TILE
-    shadow_tile<ONE, FrameShadowWalk>(sv, wl, ctr, occ, tile_block() * 256u + threadIdx.x, l16);
+    shadow_tile<ONE, FrameShadowWalk>(sv, wl, ctr, occ, tile_block() * 256u + threadIdx.x, lw);
 #else
     uint32_t ps = p;  // re-derived, not kept live across the head (as pt below)
     asm volatile("" : "+v"(ps));
-    shadow_tile<ONE, FrameShadowWalk>(sv, wl, ctr, occ, ps, l16);
+    shadow_tile<ONE, FrameShadowWalk>(sv, wl, ctr, occ, ps, lw);
 #endif
     __syncthreads();
     VPX_FRAME_PHASE(7);
