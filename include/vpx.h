@@ -708,6 +708,54 @@ int vpx_pick_pixel(vpx_ctx* ctx, uint32_t width, uint32_t height, uint32_t x, ui
    devices[0]. */
 int vpx_render_ids(vpx_ctx* ctx, const vpx_frame_params* params, const vpx_ray_filter* f /* NULL = neutral */,
                    uint32_t* ids /* uint4[W*H], DEVICE */);
+/* Plane-keyed denoise: an a-trous filter over a float4 image (a vpx_render accumulator) whose edge
+   test is an integer equality on the vpx_render_ids record (no reference counterpart; the
+   reference's only filter is the static-camera history, renderer.cpp:1996-2101).  A pixel's key:
+   with v = .y & 0xffff and face = .y >> 24, valid iff v >= 2 (a voxel volume won) and
+   1 <= face <= 6; then axis = (face - 1) >> 1, coord = .z & 0xffff / .z >> 16 / .w for axis
+   0 / 1 / 2, and the key is the pair (.y, 0x80000000 | coord): same volume, material, face and
+   plane.  Every other pixel (miss, shape win, first-cell hit, a malformed face) has the invalid
+   key (0, 0); the key is only compared, never used as an index.
+   Pass p (0-based, step s = 1 << p) reads image S and writes D.  A pixel q with an invalid key
+   keeps S(q), all four channels.  Otherwise, over the taps r = (x + i*s, y + j*s), j = -2..2 outer,
+   i = -2..2 inner, that lie inside the image and have q's key:
+     h = H[|j|] * H[|i|], H = {0.375, 0.25, 0.0625}
+     w = h                                           (sigma_l == 0)
+     w = h / (1 + d*d), d = (lum(S(r)) - lum(S(q))) * (1.0f / sigma_l), lum(c) = (c.x*0.2126f +
+         c.y*0.7152f) + c.z*0.0722f                  (sigma_l > 0)
+     acc = acc + w * S(r) per colour channel (the product rounded, then the sum), wsum = wsum + w
+   and D(q) = (acc / wsum, S(q).w).  A tap that does not match is not read into the arithmetic, so
+   a NaN on another surface stays there; the centre always matches, so wsum >= 9/64.  Every
+   operation rounds once to float32; the result is defined bit for bit (NaN payloads apart).  The
+   call runs d->passes passes, the first reading `in`, the last writing `out`; when rgb8 is not
+   NULL it receives the frame's tonemap (Reinhard-Jodie + RGB8 pack, as vpx_render's) of `out`.
+   vpx_denoise_ids runs on the context's stream without synchronising, ordered like
+   vpx_render_ids (it follows a vpx_render on that stream, frames in flight included); adds
+   nothing to the work counters or the player-light record; needs no camera and no world; on a
+   device set it runs on devices[0].  Its scratch (the keys, and two images when passes > 1)
+   belongs to the context, comes with the first call and grows with the size: VPX_E_NOMEM when
+   that fails.  VPX_E_INVALID: a null p, ids, in, out or d; a zero size or one beyond
+   vpx_frame_params' limits; passes outside 1..5; a negative, NaN or infinite sigma_l; nonzero
+   flags or reserved; out == in or out == ids.  Any other overlap of the buffers is the caller's
+   error and gives undefined pixels.
+   Limits: the ids come from the un-jittered pixel-centre ray, so with VPX_FLAG_AA / VPX_FLAG_DOF
+   they guide a slightly different ray; a path through glass, smoke or a mirror is keyed by its
+   first hit only; shadows on one surface are softened unless sigma_l is set, and sigma_l
+   protects little at one sample per pixel. */
+typedef struct vpx_denoise {      /* 16 bytes */
+    uint32_t passes;              /* 1..5: steps 1, 2, 4, 8, 16 */
+    float    sigma_l;             /* 0 = plane key only; else finite and > 0 */
+    uint32_t flags;               /* 0 */
+    uint32_t reserved;            /* 0 */
+} vpx_denoise;
+int vpx_denoise_ids(vpx_ctx* ctx, const vpx_frame_params* p /* only width, height */,
+                    const uint32_t* ids /* uint4[W*H], DEVICE */, const float* in /* float4[W*H], DEVICE */,
+                    float* out /* float4[W*H], DEVICE */, uint32_t* rgb8 /* uint32[W*H], DEVICE, may be NULL */,
+                    const vpx_denoise* d);
+/* The same filter on host memory (no device, no context): the CPU path of the same code
+   (csrc/vpx_denoise.hpp).  VPX_E_NOMEM when its scratch cannot be allocated. */
+int vpx_denoise_host(uint32_t width, uint32_t height, const uint32_t* ids, const float* in, float* out,
+                     uint32_t* rgb8 /* may be NULL */, const vpx_denoise* d);
 /* Focus ray of Renderer::Tick (world-space ray against every Scene::FindNearest). */
 int vpx_focus_distance(vpx_ctx* ctx, uint32_t width, uint32_t height, float* focal_distance);
 

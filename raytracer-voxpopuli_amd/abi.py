@@ -118,6 +118,10 @@ class HitCell(C.Structure):  # vpx_hit_cell: the hit cell and the face the walk 
 CELL_HIT, CELL_FACE, CELL_FACE_IN = 0x1, 0x2, 0x4  # VPX_CELL_*; flags also hold axis << 8 | (step < 0) << 10
 
 
+class Denoise(C.Structure):  # vpx_denoise: passes 1..5 (steps 1..16), sigma_l (0: plane key only), flags, reserved
+    _fields_ = [("passes", C.c_uint32), ("sigma_l", C.c_float), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 LOAD_FULL, LOAD_PARTIAL, LOAD_RANDOM = 0, 1, 2  # VPX_LOAD_*: Scene::LoadModel / LoadModelPartial / LoadModelRandomMaterials
 
 
@@ -194,7 +198,7 @@ STAGES = ("primary", "shade", "shadow", "resolve", "bounce", "finish", "frame", 
 STRUCT_SIZES = {PrevCamera: 64, Profile: 160, Volume: 160, Material: 32, PointLight: 24, SpotLight: 40, AreaLight: 32, DirLight: 24,
                 Sphere: 32, Triangle: 64, Camera: 80, FrameParams: 48, Ray: 32, Hit: 32, Stats: 40,
                 BvhTri: 36, BvhNode: 32, PlayerLight: 24, RayProbe: 16, RayFilter: 16, HitCell: 32, ModelLoad: 40, ModelResult: 16,
-                NoiseGen: 16, NoiseResult: 16, Brush: 48, BrushResult: 16}
+                NoiseGen: 16, NoiseResult: 16, Brush: 48, BrushResult: 16, Denoise: 16}
 
 
 def np_dtype(struct):
@@ -274,6 +278,10 @@ SIGNATURES = {
                                          C.POINTER(HitCell)]),
     "vpx_pick_pixel": (C.c_int, [C.c_void_p] + [C.c_uint32] * 4 + [C.POINTER(RayFilter), C.POINTER(Hit), C.POINTER(HitCell)]),
     "vpx_render_ids": (C.c_int, [C.c_void_p, C.POINTER(FrameParams), C.POINTER(RayFilter), C.c_void_p]),
+    "vpx_denoise_ids": (C.c_int, [C.c_void_p, C.POINTER(FrameParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.POINTER(Denoise)]),
+    "vpx_denoise_host": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.POINTER(Denoise)]),
     "vpx_focus_distance": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_float)]),
     "vpx_camera_look_at": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_uint32, C.c_uint32,
                                      C.POINTER(Camera)]),

@@ -384,6 +384,25 @@ class Context:
 
     unpack_ids = staticmethod(lambda ids: unpack_ids(ids))
 
+    def denoise(self, params, ids, src, out=None, passes=5, sigma_l=0.0, rgb_ptr=None):
+        """vpx_denoise_ids: the plane-keyed a-trous filter of `src` (a float32 torch tensor of
+        4 * W * H elements on the context's device, e.g. a render accumulator) guided by `ids`
+        (render_ids' tensor), `passes` passes (steps 1, 2, 4, ...), sigma_l 0 = plane key only.
+        Returns `out` (allocated like src when None; never src itself); rgb_ptr: a device uint32[W*H]
+        pointer that receives the tonemapped result.  Runs on the context's stream, unsynchronised."""
+        import torch
+
+        if out is None:
+            out = torch.empty_like(src)
+        d = abi.Denoise(int(passes), float(sigma_l), 0, 0)
+        self._chk(self.lib.vpx_denoise_ids(self.h, C.byref(params), C.c_void_p(ids.data_ptr()),
+                                           C.c_void_p(src.data_ptr()), C.c_void_p(out.data_ptr()),
+                                           C.c_void_p(rgb_ptr or 0), C.byref(d)), "vpx_denoise_ids")
+        return out
+
+    def denoise_host(self, width, height, ids, src, passes=5, sigma_l=0.0, rgb=False):
+        return denoise_host(width, height, ids, src, passes, sigma_l, rgb, lib=self.lib)
+
     def trace(self, rays, seeds, depth, sky=abi.SKY_DEFAULT, area_samples=3):
         """Renderer::Trace per ray; sky=None samples the sky texture (activateSky)."""
         n = len(rays)
@@ -453,3 +472,19 @@ def unpack_ids(ids):
             "axis": np.where(face > 0, (face - 1) >> 1, 0).astype(np.int32),
             "step": np.where(face > 0, 1 - 2 * ((face - 1) & 1), 0).astype(np.int32),
             "cell": cell}
+
+
+def denoise_host(width, height, ids, src, passes=5, sigma_l=0.0, rgb=False, lib=None):
+    """vpx_denoise_host: the same filter on numpy arrays, no device.  ids: uint32 [H, W, 4] (or
+    anything of that size), src: float32 [H, W, 4].  Returns out [H, W, 4], or (out, rgb8 [H, W])
+    with rgb=True."""
+    lib = lib or abi.load_library()
+    w, h = int(width), int(height)
+    i = np.ascontiguousarray(ids).view(np.uint32).reshape(h, w, 4)
+    s = np.ascontiguousarray(src, np.float32).reshape(h, w, 4)
+    out = np.empty_like(s)
+    rgb8 = np.empty((h, w), np.uint32) if rgb else None
+    d = abi.Denoise(int(passes), float(sigma_l), 0, 0)
+    abi.check(lib, None, lib.vpx_denoise_host(w, h, abi.as_ptr(i), abi.as_ptr(s), abi.as_ptr(out), abi.as_ptr(rgb8),
+                                              C.byref(d)), "vpx_denoise_host")
+    return (out, rgb8) if rgb else out

@@ -7,6 +7,7 @@
 // sinf/cosf are the correctly rounded values (f64 evaluation), as on the device.
 #include <cmath>
 #include <cstring>
+#include <new>
 #include <utility>
 #include <vector>
 
@@ -14,6 +15,7 @@
 #include "vpx_model.hpp"
 #include "vpx_noise.hpp"
 #include "vpx_brush.hpp"
+#include "vpx_denoise.hpp"
 #include "vpx_skip.hpp"
 
 namespace {
@@ -599,5 +601,23 @@ int vpx_brush_apply_host(uint8_t* cells, uint32_t n, const vpx_brush* brushes, u
 #endif
     return VPX_OK;
 }
+
+// vpx_denoise_ids on host memory: vpx_denoise.hpp's host loops, the code the kernels share.
+int vpx_denoise_host(uint32_t width, uint32_t height, const uint32_t* ids, const float* in, float* out, uint32_t* rgb8,
+                     const vpx_denoise* d) {
+    if (vpx::denoise::check_call(width, height, ids, in, out, d)) return VPX_E_INVALID;
+    const size_t pixels = (size_t)width * height;
+    try {
+        std::vector<vpx::denoise::Key> keys(pixels);
+        std::vector<float> scratch(d->passes > 1 ? 8 * pixels : 0);
+        vpx::denoise::run_host(width, height, ids, in, out, rgb8, *d, keys.data(), scratch.data(),
+                               scratch.data() + (d->passes > 1 ? 4 * pixels : 0));
+    } catch (const std::bad_alloc&) {
+        return VPX_E_NOMEM;
+    }
+    return VPX_OK;
+}
+
+static_assert(sizeof(vpx_denoise) == 16 && sizeof(vpx::denoise::Key) == 8, "denoise layout");
 
 }  // extern "C"

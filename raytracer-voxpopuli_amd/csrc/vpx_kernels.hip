@@ -11,6 +11,7 @@
 //   model_gather_k / model_random_k   the model loaders' placement (vpx_model.hpp).
 //   smoke_gen_k / noise_mark_k / noise_scan_k / noise_draw_k   the noise generators (vpx_noise.hpp).
 //   brush_k                       one brush edit (vpx_brush.hpp).
+//   k_plane_key / k_atrous_lds / k_atrous_gather   the plane-keyed denoise (vpx_denoise.hpp).
 //   refresh_l1_k / df_mark_k / df_diag_k / df_planes_box_k / axis_box_k / wide_box_k   the
 //                                 region-local level refresh after an edit (refresh_levels).
 #include <hip/hip_runtime.h>
@@ -31,6 +32,7 @@
 #include "vpx_model.hpp"
 #include "vpx_noise.hpp"
 #include "vpx_brush.hpp"
+#include "vpx_denoise.hpp"
 
 using namespace vpx;
 
@@ -61,6 +63,9 @@ constexpr int kTile = 16;  // 16x16 pixels per tile / 256-thread workgroup
 #define VPX_TAIL_MIN_DEPTH 8
 #endif
 constexpr int kThreads = 256;
+#ifndef VPX_DENOISE_LDS
+#define VPX_DENOISE_LDS 1  // denoise steps 1 and 2 stage tile + halo in LDS (0: every step gathers from global memory)
+#endif
 
 // One tile per workgroup.  Several tiles per workgroup with their loads issued together
 // measured within noise (round 3, four interleaved runs, ms per step: C1 0.5829-0.5888 with 1,
@@ -268,6 +273,141 @@ __global__ __launch_bounds__(kThreads) void k_ids(SceneView sv, FrameArgs f, vpx
     o.z = (uint32_t)c.cell[0] | (uint32_t)c.cell[1] << 16;
     o.w = (uint32_t)c.cell[2];
     ids[(uint64_t)y * f.width + x] = o;
+}
+
+// ------------------------------------------------------------------ plane-keyed denoise
+// vpx_denoise_ids (vpx_denoise.hpp holds the definition and the arithmetic).  Images are
+// row-major float4[W*H]; a workgroup filters one 16x16 tile, lane t at (t & 15, t >> 4): a wave's
+// loads are four runs of 256 contiguous bytes (the frame kernels' 8x8-quadrant lane order measured
+// the same: DESIGN.md §4).
+struct DenoiseArgs {
+    uint32_t width, height, tiles_x;
+    int32_t step;
+    float inv_sigma;
+};
+
+// ids -> keys: one 8-byte store per pixel.
+__global__ __launch_bounds__(kThreads) void k_plane_key(uint32_t pixels, const uint4* __restrict__ ids,
+                                                        uint2* __restrict__ keys) {
+    const uint32_t p = blockIdx.x * kThreads + threadIdx.x;
+    if (p >= pixels) return;
+    const uint4 r = ids[p];
+    const denoise::Key k = denoise::plane_key(r.y, r.z, r.w);
+    keys[p] = make_uint2(k.a, k.b);
+}
+
+__device__ __forceinline__ void denoise_store(uint64_t q, float4 o, float4* __restrict__ D,
+                                              uint32_t* __restrict__ rgb8) {
+    D[q] = o;
+    if (rgb8) rgb8[q] = tonemap_pack(o);  // the last pass only
+}
+
+// Steps 1 and 2: the tile and its halo of 2 * STEP pixels (20x20, 24x24) staged in LDS, keys and
+// colours (9.6 / 13.8 KiB).  A pixel outside the image is staged with the invalid key, which
+// matches no valid one, so the tap loop needs no bounds test; a colour is loaded only under a
+// valid key.
+template <bool LUM, int STEP>
+__global__ __launch_bounds__(kThreads) void k_atrous_lds(DenoiseArgs a, const uint2* __restrict__ keys,
+                                                         const float4* __restrict__ S, float4* __restrict__ D,
+                                                         uint32_t* __restrict__ rgb8) {
+    constexpr int R = 2 * STEP, DIM = kTile + 2 * R;
+    __shared__ uint2 lk[DIM * DIM];
+    __shared__ float4 lc[DIM * DIM];
+    const int tx0 = (int)(blockIdx.x % a.tiles_x) * kTile, ty0 = (int)(blockIdx.x / a.tiles_x) * kTile;
+    for (int e = threadIdx.x; e < DIM * DIM; e += kThreads) {
+        const int gx = tx0 - R + e % DIM, gy = ty0 - R + e / DIM;
+        uint2 k = make_uint2(0u, 0u);
+        if (gx >= 0 && gy >= 0 && gx < (int)a.width && gy < (int)a.height) {
+            const uint64_t p = (uint64_t)gy * a.width + (uint32_t)gx;
+            k = keys[p];
+            if (k.y) lc[e] = S[p];
+        }
+        lk[e] = k;
+    }
+    __syncthreads();
+    const int lx = threadIdx.x & 15, ly = threadIdx.x >> 4;
+    const uint32_t x = tx0 + lx, y = ty0 + ly;
+    if (x >= a.width || y >= a.height) return;
+    const uint64_t q = (uint64_t)y * a.width + x;
+    const int eq = (ly + R) * DIM + lx + R;
+    const uint2 kq = lk[eq];
+    if (!kq.y) {
+        denoise_store(q, S[q], D, rgb8);
+        return;
+    }
+    const float4 cq = lc[eq];
+    const float lq = LUM ? denoise::lum(cq.x, cq.y, cq.z) : 0.f;
+    denoise::Sum s;
+#pragma unroll
+    for (int j = -2; j <= 2; ++j)
+#pragma unroll
+        for (int i = -2; i <= 2; ++i) {
+            const int e = eq + j * STEP * DIM + i * STEP;
+            const uint2 k = lk[e];
+            if (k.x == kq.x && k.y == kq.y) {
+                const float4 c = lc[e];
+                denoise::tap<LUM>(s, denoise::base_weight(j, i), c.x, c.y, c.z, lq, a.inv_sigma);
+            }
+        }
+    denoise_store(q, make_float4(s.r / s.w, s.g / s.w, s.b / s.w, cq.w), D, rgb8);
+}
+
+// Steps 4 and up (the halo outgrows the tile): 25 taps gathered from global memory through L2.
+// First the 25 keys, from clamped addresses so that the loads need no branch and go out together,
+// folded into a match mask; then the colours of the matching taps only.
+template <bool LUM>
+__global__ __launch_bounds__(kThreads) void k_atrous_gather(DenoiseArgs a, const uint2* __restrict__ keys,
+                                                            const float4* __restrict__ S, float4* __restrict__ D,
+                                                            uint32_t* __restrict__ rgb8) {
+    const int x = (int)(blockIdx.x % a.tiles_x) * kTile + (int)(threadIdx.x & 15);
+    const int y = (int)(blockIdx.x / a.tiles_x) * kTile + (int)(threadIdx.x >> 4);
+    const int W = (int)a.width, H = (int)a.height;
+    if (x >= W || y >= H) return;
+    const uint64_t q = (uint64_t)y * a.width + (uint32_t)x;
+    const uint2 kq = keys[q];
+    const float4 cq = S[q];
+    if (!kq.y) {
+        denoise_store(q, cq, D, rgb8);
+        return;
+    }
+    uint32_t match = 0u;
+#pragma unroll
+    for (int j = -2; j <= 2; ++j)
+#pragma unroll
+        for (int i = -2; i <= 2; ++i) {
+            const int rx = x + i * a.step, ry = y + j * a.step;
+            const bool in = rx >= 0 && ry >= 0 && rx < W && ry < H;
+            const int cx = min(max(rx, 0), W - 1), cy = min(max(ry, 0), H - 1);
+            const uint2 k = keys[(uint64_t)cy * a.width + (uint32_t)cx];
+            match |= (uint32_t)(in && k.x == kq.x && k.y == kq.y) << ((j + 2) * 5 + i + 2);
+        }
+    const float lq = LUM ? denoise::lum(cq.x, cq.y, cq.z) : 0.f;
+    denoise::Sum s;
+#pragma unroll
+    for (int j = -2; j <= 2; ++j)
+#pragma unroll
+        for (int i = -2; i <= 2; ++i)
+            if (match >> ((j + 2) * 5 + i + 2) & 1u) {  // in the image: the mask says so
+                const float4 c = S[(uint64_t)(y + j * a.step) * a.width + (uint32_t)(x + i * a.step)];
+                denoise::tap<LUM>(s, denoise::base_weight(j, i), c.x, c.y, c.z, lq, a.inv_sigma);
+            }
+    denoise_store(q, make_float4(s.r / s.w, s.g / s.w, s.b / s.w, cq.w), D, rgb8);
+}
+
+template <bool LUM>
+void launch_atrous(hipStream_t st, uint32_t tiles, const DenoiseArgs& a, const uint2* keys, const float4* src,
+                          float4* dst, uint32_t* rgb8) {
+#if VPX_DENOISE_LDS
+    if (a.step == 1) {
+        hipLaunchKernelGGL((k_atrous_lds<LUM, 1>), dim3(tiles), dim3(kThreads), 0, st, a, keys, src, dst, rgb8);
+        return;
+    }
+    if (a.step == 2) {
+        hipLaunchKernelGGL((k_atrous_lds<LUM, 2>), dim3(tiles), dim3(kThreads), 0, st, a, keys, src, dst, rgb8);
+        return;
+    }
+#endif
+    hipLaunchKernelGGL((k_atrous_gather<LUM>), dim3(tiles), dim3(kThreads), 0, st, a, keys, src, dst, rgb8);
 }
 
 // BasicBVH::IntersectBVH (src/BVH/BasicBVH.cpp:19-70), one ray per lane.  The workgroup
@@ -1167,6 +1307,10 @@ struct vpx_ctx {
     // a window chain's samples when no lanes run (vpx_render_window)
     float4* win_buf = nullptr;
     size_t win_len = 0;
+    // vpx_denoise_ids' scratch: the keys (uint2 per pixel), then two float4 images when a call
+    // ran more than one pass; carved per call for the call's size
+    void* dn_buf = nullptr;
+    size_t dn_bytes = 0;
     // device set (vpx_create_multi): one member context per device; this context only
     // forwards (VPX_GROUP_*) and runs the tile-sharded vpx_render (group_render)
     std::vector<vpx_ctx*> members;
@@ -1918,6 +2062,7 @@ int vpx_destroy(vpx_ctx* c) {
     for (hipEvent_t e : c->prof_ev) (void)hipEventDestroy(e);
     if (c->rp_buf) (void)hipFree(c->rp_buf);
     if (c->win_buf) (void)hipFree(c->win_buf);
+    if (c->dn_buf) (void)hipFree(c->dn_buf);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     if (c->ev2) (void)hipEventDestroy(c->ev2);
@@ -3361,6 +3506,47 @@ int vpx_render_ids(vpx_ctx* c, const vpx_frame_params* p, const vpx_ray_filter* 
     const float sky[3] = {0.392f, 0.584f, 0.829f};
     hipLaunchKernelGGL(k_ids, dim3(fa.num_tiles), dim3(kThreads), 0, c->stream, view_of(c, sky, 3), fa, flt,
                        reinterpret_cast<uint4*>(ids));
+    VPX_HIP(c, hipGetLastError());
+    return VPX_OK;
+}
+
+int vpx_denoise_ids(vpx_ctx* c, const vpx_frame_params* p, const uint32_t* ids, const float* in, float* out,
+                    uint32_t* rgb8, const vpx_denoise* d) {
+    VPX_GROUP_FIRST(c, vpx_denoise_ids(m_, p, ids, in, out, rgb8, d));
+    if (!c || !p) return fail(c, VPX_E_INVALID, "null argument");
+    if (const char* why = denoise::check_call(p->width, p->height, ids, in, out, d)) return fail(c, VPX_E_INVALID, why);
+    VPX_HIP(c, hipSetDevice(c->device));
+    const size_t pixels = (size_t)p->width * p->height;
+    const size_t key_bytes = (pixels * sizeof(uint2) + 255) & ~(size_t)255;
+    const size_t bytes = key_bytes + (d->passes > 1 ? 2 * pixels * sizeof(float4) : 0);
+    if (bytes > c->dn_bytes) {
+        VPX_HIP(c, sync_all(c));  // an earlier call may still read the old scratch
+        if (c->dn_buf) (void)hipFree(c->dn_buf);
+        c->dn_buf = nullptr;
+        c->dn_bytes = 0;
+        VPX_HIP(c, hipMalloc(&c->dn_buf, bytes));
+        c->dn_bytes = bytes;
+    }
+    uint2* keys = reinterpret_cast<uint2*>(c->dn_buf);
+    float4* img[2] = {reinterpret_cast<float4*>((char*)c->dn_buf + key_bytes),
+                      reinterpret_cast<float4*>((char*)c->dn_buf + key_bytes) + pixels};
+    hipLaunchKernelGGL(k_plane_key, dim3((uint32_t)((pixels + kThreads - 1) / kThreads)), dim3(kThreads), 0, c->stream,
+                       (uint32_t)pixels, reinterpret_cast<const uint4*>(ids), keys);
+    DenoiseArgs a;
+    a.width = p->width, a.height = p->height, a.tiles_x = (p->width + kTile - 1) / kTile;
+    a.inv_sigma = d->sigma_l > 0.0f ? 1.0f / d->sigma_l : 0.0f;
+    const uint32_t tiles = a.tiles_x * ((p->height + kTile - 1) / kTile);
+    const float4* src = reinterpret_cast<const float4*>(in);
+    for (uint32_t k = 0; k < d->passes; ++k) {
+        const bool last = k + 1 == d->passes;
+        float4* dst = last ? reinterpret_cast<float4*>(out) : img[k & 1u];
+        a.step = 1 << k;
+        if (d->sigma_l > 0.0f)
+            launch_atrous<true>(c->stream, tiles, a, keys, src, dst, last ? rgb8 : nullptr);
+        else
+            launch_atrous<false>(c->stream, tiles, a, keys, src, dst, last ? rgb8 : nullptr);
+        src = dst;
+    }
     VPX_HIP(c, hipGetLastError());
     return VPX_OK;
 }

@@ -15,6 +15,8 @@ Renderer::~Renderer() {
     if (accumulator_) (void)hipFree(accumulator_);
     if (screen_) (void)hipFree(screen_);
     if (history_) (void)hipFree(history_);
+    if (denoised_) (void)hipFree(denoised_);
+    if (ids_) (void)hipFree(ids_);
     if (ctx_) vpx_destroy(ctx_);
 }
 
@@ -316,6 +318,35 @@ int Renderer::FindNearestCells(PlayerRay& ray, int32_t* vox_index, vpx_hit_cell*
 int Renderer::PickPixel(uint32_t x, uint32_t y, const vpx_ray_filter* filter, vpx_hit* hit, vpx_hit_cell* cell) {
     if (status_) return status_;
     return vpx_pick_pixel(ctx_, width_, height_, x, y, filter, hit, cell);
+}
+
+int Renderer::Denoise(uint32_t passes, float sigma_l) {
+    if (status_) return status_;
+    if (!accumulator_) return VPX_E_STATE;
+    const size_t pixels = (size_t)width_ * height_;
+    if (!denoised_ && (hipSetDevice(device_) != hipSuccess || hipMalloc(&denoised_, sizeof(float) * 4 * pixels) != hipSuccess ||
+                       hipMalloc(&ids_, sizeof(uint32_t) * 4 * pixels) != hipSuccess)) {
+        err_ = "denoise buffer allocation failed";
+        return VPX_E_NOMEM;
+    }
+    vpx_frame_params p{};
+    p.width = width_, p.height = height_;
+    int rc = vpx_render_ids(ctx_, &p, nullptr, ids_);
+    if (rc) return rc;
+    const vpx_denoise d{passes, sigma_l, 0u, 0u};
+    uint32_t* target = nullptr;
+    if ((rc = MapScreen(&target))) return rc;
+    return UnmapScreen(vpx_denoise_ids(ctx_, &p, ids_, accumulator_, denoised_, target, &d));
+}
+
+int Renderer::CopyDenoised(float* host_rgba) const {
+    if (status_) return status_;
+    if (!denoised_) return VPX_E_STATE;
+    const int rc = vpx_synchronize(ctx_);
+    if (rc) return rc;
+    return hipMemcpy(host_rgba, denoised_, sizeof(float) * 4 * width_ * height_, hipMemcpyDeviceToHost) == hipSuccess
+               ? VPX_OK
+               : VPX_E_DEVICE;
 }
 
 int Renderer::IsOccludedPlayerClimbable(const PlayerRay& ray, bool* occluded) {

@@ -118,6 +118,12 @@ public:
     // The hit and the hit cell under pixel (x, y) of the frame (vpx_pick_pixel; filter NULL =
     // everything).  Which pixel to pick and what to do with the cell is the game's business.
     int PickPixel(uint32_t x, uint32_t y, const vpx_ray_filter* filter, vpx_hit* hit, vpx_hit_cell* cell);
+    // The plane-keyed a-trous filter of the current accumulator (vpx_render_ids, then
+    // vpx_denoise_ids; no reference counterpart: the reference shows a moving camera's frame as
+    // it is): `passes` passes (1..5), sigma_l 0 = plane key only, the result in the denoised
+    // image (CopyDenoised) and tonemapped into the screen.  Queued on the context's stream.
+    int Denoise(uint32_t passes = 5, float sigma_l = 0.0f);
+    int CopyDenoised(float* host_rgba) const;
     // Renderer::IsOccludedPlayerClimbable (renderer.cpp:245-273).
     int IsOccludedPlayerClimbable(const PlayerRay& ray, bool* occluded);
 
@@ -170,6 +176,8 @@ private:
     uint32_t width_ = 0, height_ = 0;
     float* accumulator_ = nullptr;  // float4[W*H] in HBM
     uint32_t* screen_ = nullptr;    // uint32[W*H] in HBM
+    float* denoised_ = nullptr;     // Denoise(): float4[W*H] in HBM
+    uint32_t* ids_ = nullptr;       // ... and its ID buffer, uint4[W*H]
     std::string err_;
 };
 

@@ -66,6 +66,8 @@ class Renderer:
         self.illuminationHistory = None    # renderer.h:242, float4[W*H] in HBM
         self.accumulator = None
         self.screen = None
+        self.denoised = None   # Denoise()'s image, float4[W*H] in HBM
+        self.ids = None        # ... and the ID buffer that guided it (vpx_render_ids)
         self.last_stats = None
         # Renderer::inLight (renderer.h:231): a path reached the player's smoke and found more
         # light there than VPX_PLAYER_LIGHT_SQR.  Kept up to date by Tick only while
@@ -183,6 +185,25 @@ class Renderer:
         return self.ctx.pick_pixel(self.scene.width, self.scene.height, x, y, filter=filter)
 
     pick_pixel = PickPixel
+
+    def Denoise(self, passes=5, sigma_l=0.0):
+        """The plane-keyed a-trous filter of the current accumulator (no reference counterpart: the
+        reference shows a moving camera's frame as it is): the ids of the current camera
+        (vpx_render_ids), then vpx_denoise_ids from self.accumulator into self.denoised, tonemapped
+        into self.screen.  Three launches or more on the renderer's stream, no synchronisation.
+        The ids are those of the un-jittered pixel-centre ray; paths through glass, smoke or a
+        mirror are keyed by their first hit."""
+        p = self._frame_params()
+        with torch.cuda.stream(self.stream):  # the tensors belong to the stream their kernels run on
+            self.ids = self.ctx.render_ids(p)
+            if self.denoised is None:
+                self.denoised = torch.empty_like(self.accumulator)
+        self.ctx.denoise(p, self.ids, self.accumulator, self.denoised, passes, sigma_l, self.screen.data_ptr())
+        return self.denoised
+
+    def denoised_host(self):
+        self.synchronize()
+        return self.denoised.cpu().numpy().reshape(self.scene.height, self.scene.width, 4)
 
     def IsOccludedPlayerClimbable(self, ray):
         """Renderer::IsOccludedPlayerClimbable (renderer.cpp:245-273): IsOccluded from volume 1 on,
