@@ -30,6 +30,8 @@
  *   vpx_is_occluded_filtered   Renderer::IsOccludedPlayerClimbable  renderer.cpp:245-273
  *   vpx_find_nearest_cells / vpx_pick_pixel / vpx_render_ids   no reference counterpart; the cell of
  *                              Scene::FindNearest's return, template/scene.cpp:751-811
+ *   vpx_cast_nearest / vpx_cast_occluded / vpx_debug_last_cast_kernel   no reference counterpart; the
+ *                              records of Renderer::FindNearest / IsOccluded per ray, on device memory
  *   vpx_get_player_light  Renderer::inLight           renderer.h:231; set renderer.cpp:1228-1240,
  *                                                     1438-1450; read :2112-2118, cleared :2206
  *   vpx_trace_probe       Trace's smoke-branch probe  renderer.cpp:1228-1240 (per ray)
@@ -708,6 +710,42 @@ int vpx_pick_pixel(vpx_ctx* ctx, uint32_t width, uint32_t height, uint32_t x, ui
    devices[0]. */
 int vpx_render_ids(vpx_ctx* ctx, const vpx_frame_params* params, const vpx_ray_filter* f /* NULL = neutral */,
                    uint32_t* ids /* uint4[W*H], DEVICE */);
+/* Ray batches that already live on the device: vpx_find_nearest_cells / vpx_is_occluded_filtered on
+   DEVICE pointers (no reference counterpart; the records of Renderer::FindNearest / IsOccluded per
+   ray).  hits[i] and cells[i] are vpx_find_nearest_cells' records for rays[i] and occluded[i] is
+   vpx_is_occluded_filtered's byte, bit for bit, in both arithmetic modes, with the same filter
+   semantics and refusals (f == NULL is the neutral filter {0, 1, 0, 0}; VPX_QUERY_RAW_DIRECTION is
+   allowed; vpx_cast_occluded refuses a material range).  The results do not depend on the order of
+   the rays, the form, max_waves or which lane walked a ray; vpx_hit.cells is per ray.
+   The calls are queued on the context's stream, ordered like vpx_render_ids (frames in flight and
+   world edits included), and do not synchronise; they add nothing to the work counters or the
+   player-light record; on a device set they run on devices[0].
+   Two forms.  Per lane: one thread per ray, every scene and filter.  Pool: persistent waves that
+   take the batch's rays in grabs and hand a new ray to each lane as its walk ends, so a wave is
+   not held by its longest walk; it serves the batches that visit exactly one volume
+   (first_volume == count - 1), with or without a material range or the shapes and with any tmax.
+   VPX_CAST_POOL on any other batch takes the per-lane form; flags == 0 is the library's choice
+   (DESIGN.md section 4); vpx_debug_last_cast_kernel tells which form the last call launched.
+   The pool's grab counter (a few cache lines) belongs to the context: allocated with the first
+   pool call, zeroed on the stream per call; later calls allocate nothing.
+   VPX_E_INVALID: a null context; null rays, hits or occluded with n > 0; n > 2^30; unknown flags
+   bits, both form bits, nonzero reserved; the filter refusals.  VPX_E_STATE as the host entries.
+   n == 0 is VPX_OK and launches nothing.  Overlapping buffers are the caller's error. */
+#define VPX_CAST_PER_LANE 0x1u   /* one thread per ray, no refill (the unit entries' form) */
+#define VPX_CAST_POOL     0x2u   /* the pool form wherever it can serve the batch (above)  */
+typedef struct vpx_cast {        /* 16 bytes */
+    uint32_t flags;              /* 0 = the library's choice; both bits: VPX_E_INVALID     */
+    uint32_t max_waves;          /* pool form: at most this many persistent waves, rounded up to whole
+                                    workgroups; 0 = the library's choice.  Leaves CUs to frames in
+                                    flight, and lets a small batch exercise many refills per wave */
+    uint32_t reserved[2];        /* 0 */
+} vpx_cast;
+int vpx_cast_nearest(vpx_ctx* ctx, const vpx_ray* rays /* DEVICE, n */, uint32_t n,
+                     const vpx_ray_filter* f /* NULL = {0,1,0,0} */, const vpx_cast* opt /* NULL = zeros */,
+                     vpx_hit* hits /* DEVICE, n */, vpx_hit_cell* cells /* DEVICE, n; may be NULL */);
+int vpx_cast_occluded(vpx_ctx* ctx, const vpx_ray* rays /* DEVICE */, uint32_t n, const vpx_ray_filter* f,
+                      const vpx_cast* opt, uint8_t* occluded /* DEVICE, n */);
+int vpx_debug_last_cast_kernel(vpx_ctx* ctx);  /* 0 none launched, 1 per-lane, 2 pool; host state only */
 /* Plane-keyed denoise: an a-trous filter over a float4 image (a vpx_render accumulator) whose edge
    test is an integer equality on the vpx_render_ids record (no reference counterpart; the
    reference's only filter is the static-camera history, renderer.cpp:1996-2101).  A pixel's key:

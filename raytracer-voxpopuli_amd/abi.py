@@ -118,6 +118,13 @@ class HitCell(C.Structure):  # vpx_hit_cell: the hit cell and the face the walk 
 CELL_HIT, CELL_FACE, CELL_FACE_IN = 0x1, 0x2, 0x4  # VPX_CELL_*; flags also hold axis << 8 | (step < 0) << 10
 
 
+class Cast(C.Structure):  # vpx_cast: the form of a device ray batch (vpx_cast_nearest / vpx_cast_occluded) and its wave cap
+    _fields_ = [("flags", C.c_uint32), ("max_waves", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+CAST_PER_LANE, CAST_POOL = 0x1, 0x2  # VPX_CAST_*: one thread per ray / persistent waves that refill (one visited volume)
+
+
 class Denoise(C.Structure):  # vpx_denoise: passes 1..5 (steps 1..16), sigma_l (0: plane key only), flags, reserved
     _fields_ = [("passes", C.c_uint32), ("sigma_l", C.c_float), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
 
@@ -198,7 +205,7 @@ STAGES = ("primary", "shade", "shadow", "resolve", "bounce", "finish", "frame", 
 STRUCT_SIZES = {PrevCamera: 64, Profile: 160, Volume: 160, Material: 32, PointLight: 24, SpotLight: 40, AreaLight: 32, DirLight: 24,
                 Sphere: 32, Triangle: 64, Camera: 80, FrameParams: 48, Ray: 32, Hit: 32, Stats: 40,
                 BvhTri: 36, BvhNode: 32, PlayerLight: 24, RayProbe: 16, RayFilter: 16, HitCell: 32, ModelLoad: 40, ModelResult: 16,
-                NoiseGen: 16, NoiseResult: 16, Brush: 48, BrushResult: 16, Denoise: 16}
+                NoiseGen: 16, NoiseResult: 16, Brush: 48, BrushResult: 16, Denoise: 16, Cast: 16}
 
 
 def np_dtype(struct):
@@ -278,6 +285,10 @@ SIGNATURES = {
                                          C.POINTER(HitCell)]),
     "vpx_pick_pixel": (C.c_int, [C.c_void_p] + [C.c_uint32] * 4 + [C.POINTER(RayFilter), C.POINTER(Hit), C.POINTER(HitCell)]),
     "vpx_render_ids": (C.c_int, [C.c_void_p, C.POINTER(FrameParams), C.POINTER(RayFilter), C.c_void_p]),
+    "vpx_cast_nearest": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(RayFilter), C.POINTER(Cast), C.c_void_p,
+                                   C.c_void_p]),
+    "vpx_cast_occluded": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(RayFilter), C.POINTER(Cast), C.c_void_p]),
+    "vpx_debug_last_cast_kernel": (C.c_int, [C.c_void_p]),
     "vpx_denoise_ids": (C.c_int, [C.c_void_p, C.POINTER(FrameParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.POINTER(Denoise)]),
     "vpx_denoise_host": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -363,6 +374,16 @@ def check(lib, ctx, rc, what):
 
 def vec3(v):
     return f3(*[float(x) for x in v])
+
+
+def rays_tensor(rays, device):
+    """A ctypes array of abi.Ray as the float32 torch tensor [n, 8] that cast_nearest / cast_occluded
+    take (vpx_ray's layout; inside_glass carried as bits) on `device`: for tests and small callers."""
+    import torch
+
+    n = len(rays)
+    host = np.frombuffer(rays, dtype=np.float32, count=8 * n).reshape(n, 8).copy() if n else np.zeros((0, 8), np.float32)
+    return torch.from_numpy(host).to(device)
 
 
 def sky_arg(sky):

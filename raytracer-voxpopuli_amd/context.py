@@ -384,6 +384,52 @@ class Context:
 
     unpack_ids = staticmethod(lambda ids: unpack_ids(ids))
 
+    def _cast_args(self, rays, form, max_waves):
+        import torch
+
+        if not (isinstance(rays, torch.Tensor) and rays.dtype == torch.float32 and rays.dim() == 2
+                and rays.shape[1] == 8 and rays.is_contiguous() and rays.is_cuda
+                and rays.device.index == self.device):
+            raise ValueError(f"rays: a contiguous float32 torch tensor [n, 8] on cuda:{self.device} (abi.rays_tensor)")
+        return torch, int(rays.shape[0]), abi.Cast(int(form or 0), int(max_waves), (C.c_uint32 * 2)(0, 0))
+
+    def cast_nearest(self, rays, first_volume=0, except_materials=None, shapes=True, raw_direction=False, filter=None,
+                     cells=True, form=None, max_waves=0):
+        """vpx_cast_nearest: find_nearest_cells for rays that already live on the device.  rays: a
+        contiguous float32 torch tensor [n, 8] on the context's device with vpx_ray's layout
+        (inside_glass as bits; abi.rays_tensor converts).  Returns (hits, cells): int32 tensors
+        [n, 8] (unpack_hits / unpack_cells read them), cells None with cells=False.  form:
+        abi.CAST_PER_LANE, abi.CAST_POOL or None (the library's choice); max_waves caps the pool's
+        persistent waves.  Runs on the context's stream, unsynchronised; last_cast_kernel() tells
+        which form ran.  torch orders and recycles tensors by ITS current stream: produce the rays,
+        cast and read the results under torch.cuda.stream() of the stream given to set_stream, or
+        keep the tensors alive and synchronize() before reading."""
+        torch, n, opt = self._cast_args(rays, form, max_waves)
+        f = filter if filter is not None else self.ray_filter(first_volume, except_materials, shapes, raw_direction)
+        hits = torch.empty((n, 8), dtype=torch.int32, device=rays.device)
+        cell = torch.empty((n, 8), dtype=torch.int32, device=rays.device) if cells else None
+        self._chk(self.lib.vpx_cast_nearest(self.h, C.c_void_p(rays.data_ptr()), n, C.byref(f), C.byref(opt),
+                                            C.c_void_p(hits.data_ptr()), C.c_void_p(cell.data_ptr()) if cells else None),
+                  "vpx_cast_nearest")
+        return hits, cell
+
+    def cast_occluded(self, rays, first_volume=0, shapes=True, raw_direction=False, filter=None, form=None, max_waves=0):
+        """vpx_cast_occluded: is_occluded_filtered for rays on the device (cast_nearest's tensor).
+        Returns a uint8 tensor [n].  Runs on the context's stream, unsynchronised."""
+        torch, n, opt = self._cast_args(rays, form, max_waves)
+        f = filter if filter is not None else self.ray_filter(first_volume, None, shapes, raw_direction)
+        occ = torch.empty((n,), dtype=torch.uint8, device=rays.device)
+        self._chk(self.lib.vpx_cast_occluded(self.h, C.c_void_p(rays.data_ptr()), n, C.byref(f), C.byref(opt),
+                                             C.c_void_p(occ.data_ptr())), "vpx_cast_occluded")
+        return occ
+
+    def last_cast_kernel(self):
+        """vpx_debug_last_cast_kernel: 0 nothing launched, 1 the per-lane form, 2 the pool."""
+        return int(self.lib.vpx_debug_last_cast_kernel(self.h))
+
+    unpack_hits = staticmethod(lambda hits: unpack_hits(hits))
+    unpack_cells = staticmethod(lambda cells: unpack_cells(cells))
+
     def denoise(self, params, ids, src, out=None, passes=5, sigma_l=0.0, rgb_ptr=None):
         """vpx_denoise_ids: the plane-keyed a-trous filter of `src` (a float32 torch tensor of
         4 * W * H elements on the context's device, e.g. a render accumulator) guided by `ids`
@@ -472,6 +518,28 @@ def unpack_ids(ids):
             "axis": np.where(face > 0, (face - 1) >> 1, 0).astype(np.int32),
             "step": np.where(face > 0, 1 - 2 * ((face - 1) & 1), 0).astype(np.int32),
             "cell": cell}
+
+
+_HIT_DT = np.dtype([("t", "<f4"), ("normal", "<f4", 3), ("vox_index", "<i4"), ("material", "<u4"), ("cells", "<u4"),
+                    ("inside_glass", "<u4")])
+_CELL_DT = np.dtype([("cell", "<i4", 3), ("grid_id", "<u4"), ("face_cell", "<i4", 3), ("flags", "<u4")])
+
+
+def _records(buf, dt):
+    if hasattr(buf, "cpu"):
+        buf = buf.cpu().numpy()
+    return np.ascontiguousarray(buf).view(np.uint8).reshape(-1).view(dt)
+
+
+def unpack_hits(hits):
+    """cast_nearest's hits ([n, 8] int32, torch or numpy) as hits_to_numpy's record array (a view
+    of the host copy)."""
+    return _records(hits, _HIT_DT)
+
+
+def unpack_cells(cells):
+    """cast_nearest's cells ([n, 8] int32, torch or numpy) as cells_to_numpy's record array."""
+    return _records(cells, _CELL_DT)
 
 
 def denoise_host(width, height, ids, src, passes=5, sigma_l=0.0, rgb=False, lib=None):

@@ -260,6 +260,7 @@ static_assert(sizeof(vpx_prev_camera) == 64, "vpx_prev_camera layout");
 static_assert(sizeof(vpx_player_light) == 24 && sizeof(vpx_ray_probe) == 16, "player light layout");
 static_assert(sizeof(vpx_ray_filter) == 16, "ray filter layout");
 static_assert(sizeof(vpx_hit_cell) == 32, "hit cell layout");
+static_assert(sizeof(vpx_cast) == 16 && offsetof(vpx_cast, max_waves) == 4 && offsetof(vpx_cast, reserved) == 8, "cast options layout");
 static_assert(sizeof(vpx_model_load) == 40 && sizeof(vpx_model_result) == 16, "model load layout");
 static_assert(sizeof(vpx_noise_gen) == 16 && sizeof(vpx_noise_result) == 16, "noise generator layout");
 static_assert(sizeof(vpx_brush) == 48 && sizeof(vpx_brush_result) == 16, "brush layout");

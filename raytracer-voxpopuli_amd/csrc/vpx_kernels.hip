@@ -7,6 +7,8 @@
 //   composite_tiles               rank-0 unpack + accumulate + tonemap of gathered tiles.
 //   composite_rgb8                rank-0 unpack of gathered RGB8 tiles (sharded accumulator).
 //   find_nearest_k / is_occluded_k / trace_k   per-ray unit entries.
+//   k_cast_lane / k_cast_occluded_lane / k_cast_pool / k_cast_occluded_pool   ray batches in device
+//                                 memory (vpx_cast_*): one thread per ray, or persistent waves that refill.
 //   tiled_world_k / checksum_k    world generator and grid checksum.
 //   model_gather_k / model_random_k   the model loaders' placement (vpx_model.hpp).
 //   smoke_gen_k / noise_mark_k / noise_scan_k / noise_draw_k   the noise generators (vpx_noise.hpp).
@@ -273,6 +275,300 @@ __global__ __launch_bounds__(kThreads) void k_ids(SceneView sv, FrameArgs f, vpx
     o.z = (uint32_t)c.cell[0] | (uint32_t)c.cell[1] << 16;
     o.w = (uint32_t)c.cell[2];
     ids[(uint64_t)y * f.width + x] = o;
+}
+
+// ------------------------------------------------------------------ ray batches in device memory
+// vpx_cast_nearest / vpx_cast_occluded: the filtered queries on rays and records that already
+// live on the device, queued on the context's stream like k_ids.
+// Per-lane form: the unit kernels' bodies (find_nearest_filtered_k / find_nearest_cells_k /
+// is_occluded_filtered_k) on device pointers, one thread per ray, every scene and filter.
+template <bool CELLS>
+__global__ __launch_bounds__(kThreads) void k_cast_lane(SceneView sv, const vpx_ray* __restrict__ rays, uint32_t n,
+                                                        vpx_ray_filter f, vpx_hit* __restrict__ hits,
+                                                        vpx_hit_cell* __restrict__ cells) {
+    const uint32_t i = blockIdx.x * kThreads + threadIdx.x;
+    if (i >= n) return;
+    Ray r = ray_from(rays[i], f.flags);
+    if (CELLS) {
+        vpx_hit_cell c;
+        hits[i] = cells_query(sv, r, f, c);
+        cells[i] = c;
+    } else {
+        Counters k{0u, 0u, 0u};
+        const int32_t vox = find_nearest_filtered(sv, r, k, f.first_volume, f.mat_lo, f.mat_hi, !(f.flags & VPX_QUERY_NO_SHAPES));
+        vpx_hit h;
+        h.t = r.t;
+        h.normal[0] = r.N.x, h.normal[1] = r.N.y, h.normal[2] = r.N.z;
+        h.vox_index = vox;
+        h.material = r.mat;
+        h.cells = k.cells;
+        h.inside_glass = r.inside ? 1u : 0u;
+        hits[i] = h;
+    }
+}
+
+__global__ __launch_bounds__(kThreads) void k_cast_occluded_lane(SceneView sv, const vpx_ray* __restrict__ rays, uint32_t n,
+                                                                 vpx_ray_filter f, uint8_t* __restrict__ occ) {
+    const uint32_t i = blockIdx.x * kThreads + threadIdx.x;
+    if (i >= n) return;
+    const Ray r = ray_from(rays[i], f.flags);
+    Counters k{0u, 0u, 0u};
+    occ[i] = is_occluded(sv, r, k, f.first_volume, !(f.flags & VPX_QUERY_NO_SHAPES)) ? 1 : 0;
+}
+
+// Pool form (batches that visit exactly one volume, the scene's last: first_volume == count - 1).
+// The halves of find_nearest_filtered's visit of that volume around the walk: the walk state of
+// ray `in` (false: the cull or Setup3DDDA refuses it, no cell is read), and the records from the
+// finished walk.  The end re-reads the ray (as nearest_end_v does), so only the walk state, the
+// bound and the cell counter live across the walk.
+__device__ __forceinline__ bool cast_nearest_begin(const SceneView& sv, const vpx_volume& vol, uint32_t vi, uint32_t gn,
+                                                   const vpx_ray& in, uint32_t flags, skip::Walk& wk, float& bound) {
+    const Ray r = ray_from(in, flags);
+    bound = r.t;
+    ORay o;
+    o.D = xform_vec_ssem(r.D, vol.inv_matrix);
+    if (!(sv.x86.tab && (rcp_nan(o.D.x) || rcp_nan(o.D.y) || rcp_nan(o.D.z))) &&
+        misses_volume_u(sv.vbounds, vi, r.O, world_inv(r.D), r.t))
+        return false;
+    o.O = xform_pos_ssem(r.O, vol.inv_matrix);
+    o.rD = nearest_rd(o.D, sv.x86);
+    Dda s;
+    if (!dda_setup(vol, gn, o, s)) return false;
+    wk = to_walk(s);
+    return true;
+}
+template <bool CELLS>
+__device__ __forceinline__ void cast_nearest_end(const SceneView& sv, const vpx_volume& vol, uint32_t vi, uint32_t gn,
+                                                 const vpx_ray& in, const vpx_ray_filter& f, const skip::Walk& wk, bool hit,
+                                                 uint32_t mat, int last, uint32_t ncells, vpx_hit* hit_out,
+                                                 vpx_hit_cell* cell_out) {
+    Ray r = ray_from(in, f.flags);
+    int32_t vox = -2;
+    if (hit) {
+        r.t = wk.t;
+        ORay o;
+        o.O = xform_pos_ssem(r.O, vol.inv_matrix);
+        o.D = xform_vec_ssem(r.D, vol.inv_matrix);
+        r.N = normal_voxel(o, r.t, gn, vol.matrix);
+        r.mat = mat;
+        vox = (int32_t)vi;
+    }
+    if (!(f.flags & VPX_QUERY_NO_SHAPES) && (sv.num_spheres | sv.num_triangles)) {
+        Ray sh = make_ray(r.O, r.D);
+        for (uint32_t i = 0; i < sv.num_spheres; ++i) sphere_hit(sv.spheres[i], sh);
+        for (uint32_t i = 0; i < sv.num_triangles; ++i) tri_hit(sv.triangles[i], sh);
+        if (r.t > sh.t) {
+            r.t = sh.t;
+            r.mat = sh.mat;
+            r.N = sh.N;
+            r.inside = sh.inside;
+            vox = -1;
+        }
+    }
+    vpx_hit h;
+    h.t = r.t;
+    h.normal[0] = r.N.x, h.normal[1] = r.N.y, h.normal[2] = r.N.z;
+    h.vox_index = vox;
+    h.material = r.mat;
+    h.cells = ncells;
+    h.inside_glass = r.inside ? 1u : 0u;
+    *hit_out = h;
+    if (CELLS) {  // hit_cell_record's words, as two 16-byte stores
+        int4 a = make_int4(0, 0, 0, 0), b = make_int4(0, 0, 0, 0);
+        if (vox >= 0) {
+            a = make_int4((int32_t)wk.X, (int32_t)wk.Y, (int32_t)wk.Z, (int32_t)vol.grid_id);
+            uint32_t fl = VPX_CELL_HIT;
+            if (last >= 0) {
+                const int32_t step = last == 0 ? wk.sx : (last == 1 ? wk.sy : wk.sz);
+                b = make_int4(a.x - (last == 0 ? step : 0), a.y - (last == 1 ? step : 0), a.z - (last == 2 ? step : 0), 0);
+                const int32_t fc = last == 0 ? b.x : (last == 1 ? b.y : b.z);
+                fl |= VPX_CELL_FACE | (uint32_t)last << 8 | (step < 0 ? 1u : 0u) << 10 |
+                      (fc >= 0 && fc < (int32_t)gn ? VPX_CELL_FACE_IN : 0u);
+            }
+            b.w = (int32_t)fl;
+        }
+        int4* out = reinterpret_cast<int4*>(cell_out);
+        out[0] = a;
+        out[1] = b;
+    }
+}
+
+// Waves per SIMD of the cast pools: 5 (96 VGPRs, as k_nearest_pool); the hit-cell form carries
+// the last step's axis through the walk as well and spills 24 to 32 VGPRs there, so it takes 4.
+#ifndef VPX_WPE_CAST
+#define VPX_WPE_CAST 5
+#endif
+#ifndef VPX_WPE_CAST_CELLS
+#define VPX_WPE_CAST_CELLS 4
+#endif
+// FindNearest (filtered) for a device batch on persistent waves that refill their finished lanes:
+// k_nearest_pool's scheme with the rays taken from the batch itself, kPoolChunk per grab, each
+// lane under its own bound (the ray's tmax).  A lane that hit an excepted cell takes the cell's
+// leaving event (find_nearest_filtered's pass-through) and stays in the walk, so the pool needs
+// no re-entry rounds of its own.  Every ray is walked by exactly the per-lane sequence of
+// find_nearest_filtered's visit of the volume (same cells, same counts, same records); a lane's
+// cell counter starts from zero with each ray it takes, so the record holds that ray's cells.
+// Why the outer loop ends.  Every pass of the refill loop either hands out at least one ray
+// (avail > 0 and an idle lane: take >= 1), or takes one grab (the counter only grows, so at most
+// `chunks` succeed per wave and the next clears `more`), or leaves; n is finite, so it leaves,
+// and a last chunk of n % kPoolChunk rays is avail = n - cur, never past the batch.  A lane whose
+// setup fails keeps its ray with mode kWalkMiss: the pass then goes round without the walk, the
+// top writes the miss record and frees the lane, and the refill hands it another ray; each such
+// round retires at least one ray, so a grab whose rays all fail setup, or a batch of misses only,
+// costs n / 64 rounds at most and never enters the walk.  Otherwise every lane with a ray walks.
+// While `more` holds all 64 do, the walk starts with no finished lane and returns only after
+// kPoolLeave walks ended, and a lane that then passes through an excepted cell has advanced one
+// cell of a finite grid: progress either way.  With `more == false` the walk runs with leave = 65,
+// which no count of lanes reaches, until every lane has finished; pass-through re-entries are
+// bounded by the cells on the rays; no lane takes a ray any more, each round retires the finished
+// ones, and the ballot over q ends the loop.  One wave alone drains the whole batch the same way.
+template <bool X86, bool CELLS>
+__global__ __launch_bounds__(kPoolWg) VPX_WPE(CELLS ? VPX_WPE_CAST_CELLS : VPX_WPE_CAST) void k_cast_pool(SceneView sv_, const vpx_ray* __restrict__ rays,
+                                                                           uint32_t n, vpx_ray_filter f,
+                                                                           uint32_t* __restrict__ grab, uint32_t waves,
+                                                                           vpx_hit* __restrict__ hits,
+                                                                           vpx_hit_cell* __restrict__ cells) {
+    if (blockIdx.x * (kPoolWg / 64u) + (threadIdx.x >> 6) >= waves) return;  // max_waves: the last workgroup's spare waves
+    const SceneView sv = arith_view<X86>(sv_);
+    const uint32_t vi = sv.num_volumes - 1u;
+    const vpx_volume* vol = uni_ptr(&sv.volumes[vi]);
+    const DevGrid g = sv.grids[vol->grid_id];
+    const skip::GridView gv = grid_view(g);
+    const uint32_t chunks = (n + kPoolChunk - 1u) / kPoolChunk;
+    skip::Walk wk;
+    uint32_t q = ~0u;  // the ray this lane walks (~0u: none)
+    int mode = kWalkMiss, last = -1;
+    float bound = 0.f;
+    uint32_t ncells = 0u;
+    uint32_t avail = 0u, cur = 0u;  // grabbed rays not yet handed out, and where they start
+    bool more = true;               // rays may be left in the batch
+    uint32_t line = pool_line0();
+    for (;;) {
+        if (q != ~0u && mode >= kWalkMiss) {
+            uint32_t mat = kNone;
+            if (mode == kWalkHit) {
+                mat = gv.cells[(uint64_t)wk.X + (uint64_t)wk.Y * gv.n + (uint64_t)wk.Z * ((uint64_t)gv.n * gv.n)];
+                if (mat >= f.mat_lo && mat <= f.mat_hi) {  // scene.cpp:826: passed through
+                    const uint32_t ox = wk.X, oy = wk.Y;
+                    const bool on = skip::step1<BounceWalk::min2>(wk, gv.n);
+                    if (CELLS) last = stepped_axis(wk, ox, oy);
+                    mode = on ? kWalkStep : kWalkMiss;
+                }
+            }
+            if (mode >= kWalkMiss) {  // finished: its records
+                asm volatile("" ::: "memory");  // re-read the ray instead of keeping it live
+                cast_nearest_end<CELLS>(sv, *vol, vi, g.n, rays[q], f, wk, mode == kWalkHit, mat, last, ncells, &hits[q],
+                                        CELLS ? &cells[q] : nullptr);
+                q = ~0u;
+            }
+        }
+        while (more) {
+            const uint64_t idle = __ballot(q == ~0u);
+            if (!idle) break;
+            if (avail == 0u) {
+                const uint32_t gi = pool_grab(grab, chunks, line);
+                if (gi == ~0u) {
+                    more = false;
+                    break;
+                }
+                cur = gi * kPoolChunk;
+                avail = min(kPoolChunk, n - cur);
+                continue;
+            }
+            const uint32_t take = min((uint32_t)__popcll(idle), avail);
+            const uint32_t r = lane_rank(idle);
+            if (q == ~0u && r < take) {
+                q = cur + r;
+                ncells = 0u;
+                last = -1;
+                mode = cast_nearest_begin(sv, *vol, vi, g.n, rays[q], f.flags, wk, bound) ? kWalkStep : kWalkMiss;
+            }
+            cur += take;
+            avail -= take;
+        }
+        if (!__ballot(q != ~0u)) break;  // the batch is done and every lane is done
+        // lanes whose setup failed: their miss records (above) and other rays in their place first
+        if (__ballot(q != ~0u && mode >= kWalkMiss)) continue;
+        walk_wave<BounceWalk, true, CELLS>(gv, wk, bound, ncells, &mode, more ? kPoolLeave : 65u, &last);
+    }
+}
+
+// IsOccluded (filtered: one visited volume, the shapes unless VPX_QUERY_NO_SHAPES) for a device
+// batch, on the same pool: is_occluded's visit of the volume per lane (scalar transforms, exact
+// 1 / D in both arithmetic modes), then its shape tests for the rays the volume left unoccluded.
+// The outer loop ends as k_cast_pool's does (no pass-through here).
+__global__ __launch_bounds__(kPoolWg) VPX_WPE(VPX_WPE_CAST) void k_cast_occluded_pool(SceneView sv, const vpx_ray* __restrict__ rays,
+                                                                                    uint32_t n, vpx_ray_filter f,
+                                                                                    uint32_t* __restrict__ grab, uint32_t waves,
+                                                                                    uint8_t* __restrict__ occ) {
+    if (blockIdx.x * (kPoolWg / 64u) + (threadIdx.x >> 6) >= waves) return;
+    const uint32_t vi = sv.num_volumes - 1u;
+    const vpx_volume* vol = uni_ptr(&sv.volumes[vi]);
+    const DevGrid g = sv.grids[vol->grid_id];
+    const skip::GridView gv = grid_view(g);
+    const uint32_t chunks = (n + kPoolChunk - 1u) / kPoolChunk;
+    const bool shapes = !(f.flags & VPX_QUERY_NO_SHAPES);
+    auto finish = [&](uint32_t i, bool hit) {
+        bool o = hit;
+        if (!o && shapes) {
+            const Ray r = ray_from(rays[i], f.flags);
+            for (uint32_t j = 0; j < sv.num_spheres && !o; ++j) o = sphere_is_hit(sv.spheres[j], r);
+            for (uint32_t j = 0; j < sv.num_triangles && !o; ++j) o = tri_is_hit(sv.triangles[j], r);
+        }
+        occ[i] = o ? 1 : 0;
+    };
+    skip::Walk wk;
+    uint32_t q = ~0u;
+    int mode = kWalkMiss;
+    float bound = 0.f;
+    uint32_t ncells = 0u;
+    uint32_t avail = 0u, cur = 0u;
+    bool more = true;
+    uint32_t line = pool_line0();
+    for (;;) {
+        if (q != ~0u && mode >= kWalkMiss) {
+            asm volatile("" ::: "memory");
+            finish(q, mode == kWalkHit);
+            q = ~0u;
+        }
+        while (more) {
+            const uint64_t idle = __ballot(q == ~0u);
+            if (!idle) break;
+            if (avail == 0u) {
+                const uint32_t gi = pool_grab(grab, chunks, line);
+                if (gi == ~0u) {
+                    more = false;
+                    break;
+                }
+                cur = gi * kPoolChunk;
+                avail = min(kPoolChunk, n - cur);
+                continue;
+            }
+            const uint32_t take = min((uint32_t)__popcll(idle), avail);
+            const uint32_t r = lane_rank(idle);
+            if (q == ~0u && r < take) {
+                q = cur + r;
+                const Ray ry = ray_from(rays[q], f.flags);
+                bound = ry.t;
+                bool ok = !misses_volume_u(sv.vbounds, vi, ry.O, world_inv(ry.D), ry.t);
+                if (ok) {
+                    ORay o;
+                    o.O = xform_pos(ry.O, vol->inv_matrix);
+                    o.D = xform_vec(ry.D, vol->inv_matrix);
+                    o.rD = mk(__fdiv_rn(1.0f, o.D.x), __fdiv_rn(1.0f, o.D.y), __fdiv_rn(1.0f, o.D.z));
+                    Dda s;
+                    ok = dda_setup(*vol, g.n, o, s);
+                    if (ok) wk = to_walk(s);
+                }
+                mode = ok ? kWalkStep : kWalkMiss;  // a miss: the volume reads no cell, the shapes answer
+            }
+            cur += take;
+            avail -= take;
+        }
+        if (!__ballot(q != ~0u)) break;
+        if (__ballot(q != ~0u && mode >= kWalkMiss)) continue;  // setup failed: their bytes first, as k_cast_pool
+        walk_wave<ShadowPoolWalk, true>(gv, wk, bound, ncells, &mode, more ? kPoolLeave : 65u);
+    }
 }
 
 // ------------------------------------------------------------------ plane-keyed denoise
@@ -1311,6 +1607,10 @@ struct vpx_ctx {
     // ran more than one pass; carved per call for the call's size
     void* dn_buf = nullptr;
     size_t dn_bytes = 0;
+    // vpx_cast_*: the pool form's grab block (kGrabBlock words, zeroed on the stream per call; comes
+    // with the first call), and what the last call launched (vpx_debug_last_cast_kernel)
+    uint32_t* cast_grab = nullptr;
+    int last_cast = 0;
     // device set (vpx_create_multi): one member context per device; this context only
     // forwards (VPX_GROUP_*) and runs the tile-sharded vpx_render (group_render)
     std::vector<vpx_ctx*> members;
@@ -2063,6 +2363,7 @@ int vpx_destroy(vpx_ctx* c) {
     if (c->rp_buf) (void)hipFree(c->rp_buf);
     if (c->win_buf) (void)hipFree(c->win_buf);
     if (c->dn_buf) (void)hipFree(c->dn_buf);
+    if (c->cast_grab) (void)hipFree(c->cast_grab);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     if (c->ev2) (void)hipEventDestroy(c->ev2);
@@ -3508,6 +3809,106 @@ int vpx_render_ids(vpx_ctx* c, const vpx_frame_params* p, const vpx_ray_filter* 
                        reinterpret_cast<uint4*>(ids));
     VPX_HIP(c, hipGetLastError());
     return VPX_OK;
+}
+
+// vpx_cast_*: the shared checks (the filter as vpx_find_nearest_cells takes it, NULL = neutral;
+// the options), and which form serves the batch: the pool only where the batch visits exactly one
+// volume, the scene's last.  What flags == 0 takes there was decided on incoherent rays (origins
+// uniform in the world box, directions uniform on the sphere, 2^22 rays, one run, median [p5, p95]
+// ms; DESIGN.md section 4, "Device ray batches"): FindNearest with cells C1 pool 1.716 [1.647,
+// 1.791] vs per lane 2.186 [2.175, 2.197], C2 1.407 [1.381, 1.426] vs 2.105 [2.096, 2.130]: the
+// pool; IsOccluded C1 1.693 [1.577, 1.735] vs 1.688 [1.664, 1.710], inside the spread (C2 1.366
+// vs 1.612): per lane.  Rays in pixel order are the other way round (C1 0.506 vs 0.340): such a
+// caller asks for VPX_CAST_PER_LANE.
+constexpr bool kCastNearestDefaultPool = true, kCastOccludedDefaultPool = false;
+static int cast_begin(vpx_ctx* c, uint32_t n, const vpx_ray_filter* f, const vpx_cast* opt, bool occlusion,
+                      vpx_ray_filter& flt, vpx_cast& o, bool& pool) {
+    c->last_cast = 0;
+    if (n > (1u << 30)) return fail(c, VPX_E_INVALID, "more than 2^30 rays in one batch");
+    flt = f ? *f : vpx_ray_filter{0u, 1u, 0u, 0u};
+    int rc = check_filter(c, &flt, occlusion);
+    if (rc) return rc;
+    o = opt ? *opt : vpx_cast{0u, 0u, {0u, 0u}};
+    if (o.flags & ~(VPX_CAST_PER_LANE | VPX_CAST_POOL)) return fail(c, VPX_E_INVALID, "unknown VPX_CAST_* flag");
+    if ((o.flags & VPX_CAST_PER_LANE) && (o.flags & VPX_CAST_POOL))
+        return fail(c, VPX_E_INVALID, "VPX_CAST_PER_LANE and VPX_CAST_POOL together");
+    if (o.reserved[0] | o.reserved[1]) return fail(c, VPX_E_INVALID, "vpx_cast.reserved must be 0");
+    if ((rc = check_ready(c))) return rc;
+    const bool reach = (uint64_t)flt.first_volume + 1u == c->volumes.size();
+    pool = reach && ((o.flags & VPX_CAST_POOL) || (o.flags == 0u && (occlusion ? kCastOccludedDefaultPool : kCastNearestDefaultPool)));
+    return VPX_OK;
+}
+// The pool's launch: its grab block zeroed on the stream, then at most max_waves persistent waves
+// (whole workgroups are launched; the last one's waves beyond the count leave at once), never more
+// than the batch has grabs or the device holds at once (wpe: the kernel's waves per SIMD).
+static int cast_pool_grid(vpx_ctx* c, uint32_t n, const vpx_cast& o, uint32_t wpe, uint32_t& waves, uint32_t& blocks) {
+    if (!c->cast_grab) VPX_HIP(c, hipMalloc(&c->cast_grab, sizeof(uint32_t) * kGrabBlock));
+    VPX_HIP(c, hipMemsetAsync(c->cast_grab, 0, sizeof(uint32_t) * kGrabBlock, c->stream));
+    const uint32_t chunks = (n + kPoolChunk - 1u) / kPoolChunk, wpb = kPoolWg / 64u;
+    waves = std::min(chunks, c->cus * 4u * wpe);
+    if (o.max_waves) waves = std::min(waves, o.max_waves);
+    blocks = (waves + wpb - 1u) / wpb;
+    return VPX_OK;
+}
+
+int vpx_cast_nearest(vpx_ctx* c, const vpx_ray* rays, uint32_t n, const vpx_ray_filter* f, const vpx_cast* opt,
+                     vpx_hit* hits, vpx_hit_cell* cells) {
+    VPX_GROUP_FIRST(c, vpx_cast_nearest(m_, rays, n, f, opt, hits, cells));
+    if (!c || (n && (!rays || !hits))) return fail(c, VPX_E_INVALID, "null argument");
+    vpx_ray_filter flt;
+    vpx_cast o;
+    bool pool = false;
+    int rc = cast_begin(c, n, f, opt, false, flt, o, pool);
+    if (rc) return rc;
+    if (n == 0) return VPX_OK;
+    VPX_HIP(c, hipSetDevice(c->device));
+    const float sky[3] = {0.392f, 0.584f, 0.829f};
+    const SceneView sv = view_of(c, sky, 3);
+    if (pool) {
+        uint32_t waves = 0, blocks = 0;
+        if ((rc = cast_pool_grid(c, n, o, cells ? VPX_WPE_CAST_CELLS : VPX_WPE_CAST, waves, blocks))) return rc;
+        const bool x86 = sv.x86.tab != nullptr;
+        auto k = cells ? (x86 ? k_cast_pool<true, true> : k_cast_pool<false, true>)
+                       : (x86 ? k_cast_pool<true, false> : k_cast_pool<false, false>);
+        hipLaunchKernelGGL(k, dim3(blocks), dim3(kPoolWg), 0, c->stream, sv, rays, n, flt, c->cast_grab, waves, hits, cells);
+    } else {
+        hipLaunchKernelGGL(cells ? k_cast_lane<true> : k_cast_lane<false>, dim3((n + kThreads - 1) / kThreads), dim3(kThreads),
+                           0, c->stream, sv, rays, n, flt, hits, cells);
+    }
+    VPX_HIP(c, hipGetLastError());
+    c->last_cast = pool ? 2 : 1;
+    return VPX_OK;
+}
+
+int vpx_cast_occluded(vpx_ctx* c, const vpx_ray* rays, uint32_t n, const vpx_ray_filter* f, const vpx_cast* opt,
+                      uint8_t* occ) {
+    VPX_GROUP_FIRST(c, vpx_cast_occluded(m_, rays, n, f, opt, occ));
+    if (!c || (n && (!rays || !occ))) return fail(c, VPX_E_INVALID, "null argument");
+    vpx_ray_filter flt;
+    vpx_cast o;
+    bool pool = false;
+    int rc = cast_begin(c, n, f, opt, true, flt, o, pool);
+    if (rc) return rc;
+    if (n == 0) return VPX_OK;
+    VPX_HIP(c, hipSetDevice(c->device));
+    const float sky[3] = {0.392f, 0.584f, 0.829f};
+    const SceneView sv = view_of(c, sky, 3);
+    if (pool) {
+        uint32_t waves = 0, blocks = 0;
+        if ((rc = cast_pool_grid(c, n, o, VPX_WPE_CAST, waves, blocks))) return rc;
+        hipLaunchKernelGGL(k_cast_occluded_pool, dim3(blocks), dim3(kPoolWg), 0, c->stream, sv, rays, n, flt, c->cast_grab, waves, occ);
+    } else {
+        hipLaunchKernelGGL(k_cast_occluded_lane, dim3((n + kThreads - 1) / kThreads), dim3(kThreads), 0, c->stream, sv, rays, n,
+                           flt, occ);
+    }
+    VPX_HIP(c, hipGetLastError());
+    c->last_cast = pool ? 2 : 1;
+    return VPX_OK;
+}
+
+int vpx_debug_last_cast_kernel(vpx_ctx* c) {
+    if (!c) return 0;
+    return c->members.empty() ? c->last_cast : c->members[0]->last_cast;
 }
 
 int vpx_denoise_ids(vpx_ctx* c, const vpx_frame_params* p, const uint32_t* ids, const float* in, float* out,

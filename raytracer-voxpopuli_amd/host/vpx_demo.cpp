@@ -26,6 +26,11 @@
 // usage: vpx_demo pick [n] [width] [height] [x] [y]
 //   renders nothing: the same world and camera, then Renderer::PickPixel(x, y) (vpx_pick_pixel,
 //   everything visible) and the hit and its cell record as one JSON line.
+// usage: vpx_demo cast [n] [width] [height] [form] [max_waves]
+//   renders nothing: the same world, 129 rays from the camera's position over a fan of directions
+//   copied to the device, Renderer::CastRays (form: 0 the library's choice, 1 per lane, 2 pool)
+//   and Renderer::CastOccluded on them, and per ray its bits, hit, cell record and occlusion byte
+//   as one JSON line, with the form that ran.
 //   devices: comma-separated HIP devices, e.g. 0,1,2,3 — a device set (vpx_create_multi:
 //   tiles over the devices, RCCL gather to the first); default: device 0 alone.
 #include <chrono>
@@ -34,6 +39,8 @@
 #include <cstdlib>
 #include <cstring>
 #include <vector>
+
+#include <hip/hip_runtime_api.h>
 
 #include "vpx_renderer.h"
 
@@ -209,9 +216,62 @@ static int generators(vpxhost::Renderer& r, uint32_t n) {
     return 0;
 }
 
+// The cast sub-command: 129 rays (two full waves and one lane) through the mirror's device entries.
+static int cast_rays(vpxhost::Renderer& r, const float pos[3], const float target[3], uint32_t form, uint32_t max_waves) {
+    const uint32_t n = 129;
+    std::vector<vpx_ray> rays(n);
+    for (uint32_t i = 0; i < n; ++i) {
+        const float u = (float)((int)(i % 13u) - 6) * 0.125f, v = (float)((int)(i / 13u) - 5) * 0.125f;
+        vpx_ray& q = rays[i];
+        for (int k = 0; k < 3; ++k) q.origin[k] = pos[k];
+        q.direction[0] = (target[0] - pos[0]) + u;
+        q.direction[1] = (target[1] - pos[1]) + v;
+        q.direction[2] = (target[2] - pos[2]) + u * 0.5f;
+        q.tmax = i % 5u == 4u ? 0.75f : 1e34f;
+        q.inside_glass = 0u;
+    }
+    vpx_ray* d_rays = nullptr;
+    vpx_hit* d_hits = nullptr;
+    vpx_hit_cell* d_cells = nullptr;
+    uint8_t* d_occ = nullptr;
+    if (hipMalloc(&d_rays, sizeof(vpx_ray) * n) != hipSuccess || hipMalloc(&d_hits, sizeof(vpx_hit) * n) != hipSuccess ||
+        hipMalloc(&d_cells, sizeof(vpx_hit_cell) * n) != hipSuccess || hipMalloc(&d_occ, n) != hipSuccess ||
+        hipMemcpy(d_rays, rays.data(), sizeof(vpx_ray) * n, hipMemcpyHostToDevice) != hipSuccess)
+        return 1;
+    const vpx_cast opt{form, max_waves, {0u, 0u}};
+    CHECK(r.CastRays(d_rays, n, nullptr, &opt, d_hits, d_cells));
+    const int ran = vpx_debug_last_cast_kernel(r.Context());
+    CHECK(r.CastOccluded(d_rays, n, nullptr, &opt, d_occ));
+    CHECK(vpx_synchronize(r.Context()));
+    std::vector<vpx_hit> hits(n);
+    std::vector<vpx_hit_cell> cells(n);
+    std::vector<uint8_t> occ(n);
+    if (hipMemcpy(hits.data(), d_hits, sizeof(vpx_hit) * n, hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(cells.data(), d_cells, sizeof(vpx_hit_cell) * n, hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(occ.data(), d_occ, n, hipMemcpyDeviceToHost) != hipSuccess)
+        return 1;
+    (void)hipFree(d_rays), (void)hipFree(d_hits), (void)hipFree(d_cells), (void)hipFree(d_occ);
+    auto words = [](const void* p, int k) {
+        uint32_t w;
+        std::memcpy(&w, (const char*)p + 4 * k, 4);
+        return w;
+    };
+    std::printf("{\"cast\": {\"n\": %u, \"form\": %d, \"rows\": [", n, ran);
+    for (uint32_t i = 0; i < n; ++i) {
+        std::printf("%s[", i ? ", " : "");
+        for (int k = 0; k < 8; ++k) std::printf("%u, ", words(&rays[i], k));
+        for (int k = 0; k < 8; ++k) std::printf("%u, ", words(&hits[i], k));
+        for (int k = 0; k < 8; ++k) std::printf("%u, ", words(&cells[i], k));
+        std::printf("%u]", (unsigned)occ[i]);
+    }
+    std::printf("]}}\n");
+    return 0;
+}
+
 int main(int argc, char** argv) {
     const bool pick = argc > 1 && std::strcmp(argv[1], "pick") == 0;
-    if (pick) --argc, ++argv;  // the pixel takes the places of frames and max_bounces
+    const bool cast = argc > 1 && std::strcmp(argv[1], "cast") == 0;
+    if (pick || cast) --argc, ++argv;  // the pixel (the form and the wave cap) takes the places of frames and max_bounces
     const uint32_t n = argc > 1 ? (uint32_t)atoi(argv[1]) : 256;
     const uint32_t W = argc > 2 ? (uint32_t)atoi(argv[2]) : 640;
     const uint32_t H = argc > 3 ? (uint32_t)atoi(argv[3]) : 360;
@@ -259,6 +319,7 @@ int main(int argc, char** argv) {
     CHECK(r.SetShapes({}, {}));
     const float pos[3] = {1.25f, 0.9f, -0.35f}, target[3] = {0.45f, 0.15f, 0.55f};
     CHECK(r.LookAt(pos, target));
+    if (cast) return cast_rays(r, pos, target, (uint32_t)frames, (uint32_t)bounces);
     if (pick) {
         vpx_hit h{};
         vpx_hit_cell c{};

@@ -339,6 +339,18 @@ int Renderer::Denoise(uint32_t passes, float sigma_l) {
     return UnmapScreen(vpx_denoise_ids(ctx_, &p, ids_, accumulator_, denoised_, target, &d));
 }
 
+int Renderer::CastRays(const vpx_ray* rays, uint32_t n, const vpx_ray_filter* filter, const vpx_cast* opt, vpx_hit* hits,
+                       vpx_hit_cell* cells) {
+    if (status_) return status_;
+    return vpx_cast_nearest(ctx_, rays, n, filter, opt, hits, cells);
+}
+
+int Renderer::CastOccluded(const vpx_ray* rays, uint32_t n, const vpx_ray_filter* filter, const vpx_cast* opt,
+                           uint8_t* occluded) {
+    if (status_) return status_;
+    return vpx_cast_occluded(ctx_, rays, n, filter, opt, occluded);
+}
+
 int Renderer::CopyDenoised(float* host_rgba) const {
     if (status_) return status_;
     if (!denoised_) return VPX_E_STATE;

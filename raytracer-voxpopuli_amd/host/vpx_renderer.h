@@ -124,6 +124,14 @@ public:
     // image (CopyDenoised) and tonemapped into the screen.  Queued on the context's stream.
     int Denoise(uint32_t passes = 5, float sigma_l = 0.0f);
     int CopyDenoised(float* host_rgba) const;
+    // Ray batches that already live on the device (vpx_cast_nearest / vpx_cast_occluded; no reference
+    // counterpart: per ray the records of Renderer::FindNearest / IsOccluded): rays, hits, cells and
+    // occluded are DEVICE pointers of n elements, cells may be NULL; filter NULL = everything, opt
+    // NULL = the library's choice of form.  Queued on the context's stream like Denoise, no
+    // synchronisation: read the records after vpx_synchronize or from a later kernel on that stream.
+    int CastRays(const vpx_ray* rays, uint32_t n, const vpx_ray_filter* filter, const vpx_cast* opt, vpx_hit* hits,
+                 vpx_hit_cell* cells);
+    int CastOccluded(const vpx_ray* rays, uint32_t n, const vpx_ray_filter* filter, const vpx_cast* opt, uint8_t* occluded);
     // Renderer::IsOccludedPlayerClimbable (renderer.cpp:245-273).
     int IsOccludedPlayerClimbable(const PlayerRay& ray, bool* occluded);
 

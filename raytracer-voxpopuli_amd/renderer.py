@@ -201,6 +201,19 @@ class Renderer:
         self.ctx.denoise(p, self.ids, self.accumulator, self.denoised, passes, sigma_l, self.screen.data_ptr())
         return self.denoised
 
+    def CastRays(self, rays, filter=None, cells=True, form=None, max_waves=0):
+        """A batch of rays that already live on the device (no reference counterpart; per ray the
+        records of Renderer::FindNearest with the hit cell): ctx.cast_nearest on the renderer's
+        stream, unsynchronised.  Returns (hits, cells) device tensors."""
+        with torch.cuda.stream(self.stream):  # the tensors belong to the stream their kernel runs on
+            return self.ctx.cast_nearest(rays, filter=filter, cells=cells, form=form, max_waves=max_waves)
+
+    def CastOccluded(self, rays, filter=None, form=None, max_waves=0):
+        """Renderer::IsOccluded per ray of a device batch: ctx.cast_occluded on the renderer's stream,
+        unsynchronised.  Returns a uint8 device tensor."""
+        with torch.cuda.stream(self.stream):
+            return self.ctx.cast_occluded(rays, filter=filter, form=form, max_waves=max_waves)
+
     def denoised_host(self):
         self.synchronize()
         return self.denoised.cpu().numpy().reshape(self.scene.height, self.scene.width, 4)
