@@ -2,7 +2,8 @@
 triangle generator against the oracle restatement, and structural properties of the tree.
 
 The traversal itself runs on the device (vpx_bvh_intersect); its bit-exact parity with
-oracle_bvh_intersect is in test_gpu_parity.py.  Parity against the reference itself is
+oracle_bvh_intersect is in test_gpu_parity.py, and both are pinned to an independent restatement
+of IntersectBVH (tests/shapes_ref.py) in test_kat_shapes.py / test_kat_shapes_gpu.py.  Parity against the reference itself is
 unpinned; the reference's own construction (64 random triangles) is
 reproduced from its RandomFloat stream with the three draws of a float3 taken left to right.
 """
