@@ -32,6 +32,9 @@
  *                              Scene::FindNearest's return, template/scene.cpp:751-811
  *   vpx_cast_nearest / vpx_cast_occluded / vpx_debug_last_cast_kernel   no reference counterpart; the
  *                              records of Renderer::FindNearest / IsOccluded per ray, on device memory
+ *   vpx_reproject_ids / vpx_reproject_ids_host   no reference counterpart; temporal accumulation
+ *                              under camera motion, its rejection test the vpx_render_ids record
+ *                              (Camera::PointToUV template/camera.h:34-49, TransformPosition tmpl8math.cpp:345-353)
  *   vpx_get_player_light  Renderer::inLight           renderer.h:231; set renderer.cpp:1228-1240,
  *                                                     1438-1450; read :2112-2118, cleared :2206
  *   vpx_trace_probe       Trace's smoke-branch probe  renderer.cpp:1228-1240 (per ray)
@@ -794,6 +797,85 @@ int vpx_denoise_ids(vpx_ctx* ctx, const vpx_frame_params* p /* only width, heigh
    (csrc/vpx_denoise.hpp).  VPX_E_NOMEM when its scratch cannot be allocated. */
 int vpx_denoise_host(uint32_t width, uint32_t height, const uint32_t* ids, const float* in, float* out,
                      uint32_t* rgb8 /* may be NULL */, const vpx_denoise* d);
+/* Plane-keyed reprojection: temporal accumulation under camera motion (no reference counterpart:
+   Renderer::Tick resets its accumulator when the camera moves, and vpx_render_reproject's history,
+   renderer.cpp:1996-2101, holds only while it stands still).  The history of the previous frame is
+   carried to the current camera and blended with this frame's samples; a history pixel is taken
+   only where its vpx_render_ids record has the current pixel's key (vpx_denoise_ids' key: volume,
+   material, entry face, hit-cell coordinate along the face's axis), an integer equality in place
+   of depth / normal / albedo thresholds.  hist.w carries the history length as a float.  Every
+   operation rounds once to float32, nothing is contracted; the result is defined bit for bit (NaN
+   payloads apart).  Per pixel q = (x, y), with W, H = p->width, p->height:
+   0. No history, out = (cur.rgb, 1.0f), when Key(q) is invalid; when q's material (.y >> 16 & 255)
+      lies in nohist_lo..nohist_hi; when ids_prev / hist_in are NULL; when max_history is 1 (the
+      blend below would have a = 1, and h + (cur - h) is not cur in float32: the arm is defined,
+      not computed); and wherever a step below says so.
+   1. Key(q) is vpx_denoise_ids' key of ids_cur[q].
+   2. q's ray is vpx_pick_pixel's: Camera::GetPrimaryRayNoDOF (camera.h:103-110) from r->cur through
+      Ray::Ray, exact arithmetic: u = (float)x * (1.0f / (float)W), v likewise, E = (top_left +
+      (top_right - top_left) * u) + (bottom_left - top_left) * v, d = E - cam_pos, D = d * (1.0f /
+      sqrtf(d.x*d.x + d.y*d.y + d.z*d.z)).  With t the float whose bits are ids_cur[q].x the hit
+      point is P = cam_pos + t * D per component (the product, then the sum).
+   3. n_volumes > 0 (moving volumes): v = (.y & 0xffff) - 2; v >= n_volumes: no history; when
+      cur_volumes[v] and prev_volumes[v] differ in a byte of matrix or inv_matrix, P =
+      TransformPosition(TransformPosition(P, cur_volumes[v].inv_matrix), prev_volumes[v].matrix),
+      rows 0-2, m[0]*x + m[1]*y + m[2]*z + m[3]*1.0f summed left to right (tmpl8math.cpp:345-353);
+      else P stays.  The key is in object space and survives the move.
+   4. Camera::PointToUV (camera.h:34-49) into r->prev: delta = P - cam_pos, ld / rd / td / bd =
+      dot(left / right / top / bottom normal, delta) (n.x*d.x + n.y*d.y + n.z*d.z, left to right).
+      No history unless all four are > 0: SetFrustumNormals' normals point into the pyramid, so a
+      point behind the previous camera or outside its view fails (the reference has no such test;
+      its IsValid tests u, v, which a point behind the camera can pass).  px = (ld / (ld + rd)) * W,
+      py = (td / (td + bd)) * H, no half-pixel offsets: pixel x's ray passes through u = x / W.
+      (px or py NaN, from inf / inf: no history.)  tlx = trunc(px), fx = px - (float)tlx, gx =
+      1.0f - fx; likewise tly, fy, gy.
+   5. The taps, in this order: (tlx, tly), (tlx+1, tly), (tlx, tly+1), (tlx+1, tly+1), weights
+      gx*gy, fx*gy, gx*fy, fx*fy.  A tap r is usable iff it is inside the image, its weight is
+      > 0, Key(ids_prev[r]) equals Key(q), and hist_in[r].w >= 1.0f (a NaN fails).  An unusable tap
+      never enters the arithmetic (no multiplication by zero: a NaN on another surface stays
+      there).  No usable tap: no history.
+   6. Over the usable taps in order: hs = hs + w * hist_in[r].rgb per channel, ws = ws + w; then
+      h = hs / ws, n = min(min over the usable taps of hist_in[r].w, max_history - 1) + 1,
+      a = 1.0f / n, out.rgb = h + (cur.rgb - h) * a, out.w = n.
+   7. rgb8, when not NULL, receives the frame's tonemap (as vpx_denoise_ids') of out, same launch.
+   Per tick of a moving camera: vpx_render at frame_index 0 into `cur`, vpx_render_ids, this call,
+   vpx_denoise_ids on hist_out, RGB8.  Feed hist_out, not the denoised image, back as the next
+   hist_in, and this frame's ids as the next ids_prev.
+   vpx_reproject_ids runs on the context's stream without synchronising, ordered like
+   vpx_denoise_ids; adds nothing to the work counters or the player-light record; needs no camera
+   and no world in the context; on a device set it runs on devices[0].  Its scratch (the volume
+   table: 2 * n_volumes * 12 floats and a moved flag per volume, uploaded on the stream) belongs
+   to the context and grows with the size: VPX_E_NOMEM when that fails.  VPX_E_INVALID: a null p,
+   ids_cur, cur, hist_out or r; exactly one of ids_prev / hist_in null; a zero size or one beyond
+   vpx_frame_params' limits; max_history not integer-valued in 1..65536; nohist_hi > 255 with
+   nohist_lo <= nohist_hi; nonzero flags or reserved; n_volumes > 65534; n_volumes > 0 with a null
+   volume array; hist_out equal to any input.  Any other overlap is the caller's error.
+   Limits: sky, shape and first-cell pixels (invalid keys) never accumulate; the ids guide the
+   un-jittered pixel-centre ray, so with VPX_FLAG_AA / VPX_FLAG_DOF the samples belong to a
+   slightly different ray; a path through glass, smoke or a mirror is view-dependent and keyed by
+   its first hit only (hence nohist_lo..hi); a lighting change fades in over max_history frames:
+   there is no neighbourhood clamp. */
+typedef struct vpx_reproject {    /* 168 bytes */
+    vpx_camera      cur;          /* the camera ids_cur was rendered with (vpx_render_ids' ray) */
+    vpx_prev_camera prev;         /* the camera ids_prev / hist_in were rendered with            */
+    float    max_history;         /* integer-valued, 1..65536: the history length's cap          */
+    uint32_t nohist_lo, nohist_hi;/* first-hit materials that take no history (view-dependent:
+                                     5..14 = metal, glass, smoke); lo > hi: none                 */
+    uint32_t n_volumes;           /* 0: static world; else the length of the two arrays below   */
+    uint32_t flags, reserved;     /* 0 */
+} vpx_reproject;
+int vpx_reproject_ids(vpx_ctx* ctx, const vpx_frame_params* p /* only width, height */,
+                      const uint32_t* ids_cur, const uint32_t* ids_prev /* uint4[W*H], DEVICE; prev may be NULL */,
+                      const float* cur /* float4[W*H], DEVICE: this frame's samples */,
+                      const float* hist_in /* float4[W*H], DEVICE; NULL with ids_prev */,
+                      float* hist_out /* float4[W*H], DEVICE */, uint32_t* rgb8 /* uint32[W*H], DEVICE, may be NULL */,
+                      const vpx_reproject* r,
+                      const vpx_volume* cur_volumes, const vpx_volume* prev_volumes /* HOST, n_volumes each, or NULL */);
+/* The same pass on host memory (no device, no context): the CPU path of the same code
+   (csrc/vpx_reproject.hpp).  VPX_E_NOMEM when the volume table cannot be allocated. */
+int vpx_reproject_ids_host(uint32_t width, uint32_t height, const uint32_t* ids_cur, const uint32_t* ids_prev,
+                           const float* cur, const float* hist_in, float* hist_out, uint32_t* rgb8 /* may be NULL */,
+                           const vpx_reproject* r, const vpx_volume* cur_volumes, const vpx_volume* prev_volumes);
 /* Focus ray of Renderer::Tick (world-space ray against every Scene::FindNearest). */
 int vpx_focus_distance(vpx_ctx* ctx, uint32_t width, uint32_t height, float* focal_distance);
 

@@ -183,6 +183,11 @@ class PrevCamera(C.Structure):
                 ("bottom_normal", f3), ("pad", C.c_float)]
 
 
+class Reproject(C.Structure):  # vpx_reproject: the two cameras, the history cap, the materials without history
+    _fields_ = [("cur", Camera), ("prev", PrevCamera), ("max_history", C.c_float), ("nohist_lo", C.c_uint32),
+                ("nohist_hi", C.c_uint32), ("n_volumes", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class Profile(C.Structure):
     _fields_ = [("stage_ms", C.c_float * 8), ("stage_launches", C.c_uint32 * 8), ("stage_cells", C.c_uint64 * 8),
                 ("stage_busy_ms", C.c_float * 8)]
@@ -205,7 +210,7 @@ STAGES = ("primary", "shade", "shadow", "resolve", "bounce", "finish", "frame", 
 STRUCT_SIZES = {PrevCamera: 64, Profile: 160, Volume: 160, Material: 32, PointLight: 24, SpotLight: 40, AreaLight: 32, DirLight: 24,
                 Sphere: 32, Triangle: 64, Camera: 80, FrameParams: 48, Ray: 32, Hit: 32, Stats: 40,
                 BvhTri: 36, BvhNode: 32, PlayerLight: 24, RayProbe: 16, RayFilter: 16, HitCell: 32, ModelLoad: 40, ModelResult: 16,
-                NoiseGen: 16, NoiseResult: 16, Brush: 48, BrushResult: 16, Denoise: 16, Cast: 16}
+                NoiseGen: 16, NoiseResult: 16, Brush: 48, BrushResult: 16, Denoise: 16, Cast: 16, Reproject: 168}
 
 
 def np_dtype(struct):
@@ -293,6 +298,10 @@ SIGNATURES = {
                                   C.POINTER(Denoise)]),
     "vpx_denoise_host": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.POINTER(Denoise)]),
+    "vpx_reproject_ids": (C.c_int, [C.c_void_p, C.POINTER(FrameParams)] + [C.c_void_p] * 6 +
+                          [C.POINTER(Reproject), C.POINTER(Volume), C.POINTER(Volume)]),
+    "vpx_reproject_ids_host": (C.c_int, [C.c_uint32, C.c_uint32] + [C.c_void_p] * 6 +
+                               [C.POINTER(Reproject), C.POINTER(Volume), C.POINTER(Volume)]),
     "vpx_focus_distance": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_float)]),
     "vpx_camera_look_at": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_uint32, C.c_uint32,
                                      C.POINTER(Camera)]),

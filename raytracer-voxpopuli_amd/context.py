@@ -449,6 +449,29 @@ class Context:
     def denoise_host(self, width, height, ids, src, passes=5, sigma_l=0.0, rgb=False):
         return denoise_host(width, height, ids, src, passes, sigma_l, rgb, lib=self.lib)
 
+    def reproject(self, params, ids_cur, ids_prev, cur, hist_in, camera, prev_camera, out=None, max_history=32,
+                  nohist=(1, 0), cur_volumes=None, prev_volumes=None, rgb_ptr=None):
+        """vpx_reproject_ids: the previous frame's history `hist_in` (float32 torch tensor, 4 * W * H,
+        .w the history length) carried from `prev_camera` (abi.PrevCamera) to `camera` (abi.Camera)
+        and blended with this frame's samples `cur`, a history pixel taken only where its record in
+        `ids_prev` has the key of the pixel's record in `ids_cur` (render_ids' tensors).  ids_prev
+        and hist_in None together: no history yet.  nohist: the (lo, hi) range of first-hit materials
+        that take none; cur_volumes / prev_volumes: sequences of abi.Volume when volumes move.
+        Returns `out` (allocated like cur when None; never an input).  Runs on the context's stream,
+        unsynchronised."""
+        import torch
+
+        if out is None:
+            out = torch.empty_like(cur)
+        r, cv, pv = reproject_desc(camera, prev_camera, max_history, nohist, cur_volumes, prev_volumes)
+        ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None else 0)  # noqa: E731
+        self._chk(self.lib.vpx_reproject_ids(self.h, C.byref(params), ptr(ids_cur), ptr(ids_prev), ptr(cur), ptr(hist_in),
+                                             ptr(out), C.c_void_p(rgb_ptr or 0), C.byref(r), cv, pv), "vpx_reproject_ids")
+        return out
+
+    def reproject_host(self, width, height, ids_cur, ids_prev, cur, hist_in, camera, prev_camera, **kw):
+        return reproject_host(width, height, ids_cur, ids_prev, cur, hist_in, camera, prev_camera, lib=self.lib, **kw)
+
     def trace(self, rays, seeds, depth, sky=abi.SKY_DEFAULT, area_samples=3):
         """Renderer::Trace per ray; sky=None samples the sky texture (activateSky)."""
         n = len(rays)
@@ -555,4 +578,38 @@ def denoise_host(width, height, ids, src, passes=5, sigma_l=0.0, rgb=False, lib=
     d = abi.Denoise(int(passes), float(sigma_l), 0, 0)
     abi.check(lib, None, lib.vpx_denoise_host(w, h, abi.as_ptr(i), abi.as_ptr(s), abi.as_ptr(out), abi.as_ptr(rgb8),
                                               C.byref(d)), "vpx_denoise_host")
+    return (out, rgb8) if rgb else out
+
+
+def reproject_desc(camera, prev_camera, max_history=32, nohist=(1, 0), cur_volumes=None, prev_volumes=None):
+    """(vpx_reproject, cur volume array or None, prev volume array or None) for the two reproject entries."""
+    r = abi.Reproject()
+    r.cur, r.prev = camera, prev_camera
+    r.max_history = float(max_history)
+    r.nohist_lo, r.nohist_hi = int(nohist[0]), int(nohist[1])
+    n = len(cur_volumes) if cur_volumes is not None else 0
+    if n != (len(prev_volumes) if prev_volumes is not None else 0):
+        raise ValueError("cur_volumes and prev_volumes differ in length")
+    r.n_volumes = n
+    cv = (abi.Volume * n)(*cur_volumes) if n else None
+    pv = (abi.Volume * n)(*prev_volumes) if n else None
+    return r, cv, pv
+
+
+def reproject_host(width, height, ids_cur, ids_prev, cur, hist_in, camera, prev_camera, max_history=32, nohist=(1, 0),
+                   cur_volumes=None, prev_volumes=None, rgb=False, lib=None):
+    """vpx_reproject_ids_host: the same pass on numpy arrays, no device.  ids: uint32 [H, W, 4], cur /
+    hist_in: float32 [H, W, 4]; ids_prev and hist_in None together.  Returns hist_out [H, W, 4], or
+    (hist_out, rgb8 [H, W]) with rgb=True."""
+    lib = lib or abi.load_library()
+    w, h = int(width), int(height)
+    ids = lambda a: None if a is None else np.ascontiguousarray(a).view(np.uint32).reshape(h, w, 4)  # noqa: E731
+    img = lambda a: None if a is None else np.ascontiguousarray(a, np.float32).reshape(h, w, 4)  # noqa: E731
+    ic, ip, c, hi = ids(ids_cur), ids(ids_prev), img(cur), img(hist_in)
+    out = np.empty_like(c)
+    rgb8 = np.empty((h, w), np.uint32) if rgb else None
+    r, cv, pv = reproject_desc(camera, prev_camera, max_history, nohist, cur_volumes, prev_volumes)
+    abi.check(lib, None, lib.vpx_reproject_ids_host(w, h, abi.as_ptr(ic), abi.as_ptr(ip), abi.as_ptr(c), abi.as_ptr(hi),
+                                                    abi.as_ptr(out), abi.as_ptr(rgb8), C.byref(r), cv, pv),
+              "vpx_reproject_ids_host")
     return (out, rgb8) if rgb else out

@@ -16,6 +16,7 @@
 #include "vpx_noise.hpp"
 #include "vpx_brush.hpp"
 #include "vpx_denoise.hpp"
+#include "vpx_reproject.hpp"
 #include "vpx_skip.hpp"
 
 namespace {
@@ -620,5 +621,24 @@ int vpx_denoise_host(uint32_t width, uint32_t height, const uint32_t* ids, const
 }
 
 static_assert(sizeof(vpx_denoise) == 16 && sizeof(vpx::denoise::Key) == 8, "denoise layout");
+
+// vpx_reproject_ids on host memory: vpx_reproject.hpp's host loop over the pixel function the kernel shares.
+int vpx_reproject_ids_host(uint32_t width, uint32_t height, const uint32_t* ids_cur, const uint32_t* ids_prev,
+                           const float* cur, const float* hist_in, float* hist_out, uint32_t* rgb8, const vpx_reproject* r,
+                           const vpx_volume* cur_volumes, const vpx_volume* prev_volumes) {
+    if (vpx::reproject::check_call(width, height, ids_cur, ids_prev, cur, hist_in, hist_out, r, cur_volumes, prev_volumes))
+        return VPX_E_INVALID;
+    try {
+        std::vector<float> tab((size_t)r->n_volumes * vpx::reproject::kTabFloats);
+        std::vector<uint32_t> moved(r->n_volumes);
+        vpx::reproject::build_table(r->n_volumes, cur_volumes, prev_volumes, tab.data(), moved.data());
+        vpx::reproject::run_host(width, height, ids_cur, ids_prev, cur, hist_in, hist_out, rgb8, *r, tab.data(), moved.data());
+    } catch (const std::bad_alloc&) {
+        return VPX_E_NOMEM;
+    }
+    return VPX_OK;
+}
+
+static_assert(sizeof(vpx_reproject) == 168, "reproject layout");
 
 }  // extern "C"

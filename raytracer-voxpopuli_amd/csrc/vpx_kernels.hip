@@ -14,6 +14,7 @@
 //   smoke_gen_k / noise_mark_k / noise_scan_k / noise_draw_k   the noise generators (vpx_noise.hpp).
 //   brush_k                       one brush edit (vpx_brush.hpp).
 //   k_plane_key / k_atrous_lds / k_atrous_gather   the plane-keyed denoise (vpx_denoise.hpp).
+//   k_reproject_ids               the plane-keyed temporal reprojection (vpx_reproject.hpp).
 //   refresh_l1_k / df_mark_k / df_diag_k / df_planes_box_k / axis_box_k / wide_box_k   the
 //                                 region-local level refresh after an edit (refresh_levels).
 #include <hip/hip_runtime.h>
@@ -35,6 +36,7 @@
 #include "vpx_noise.hpp"
 #include "vpx_brush.hpp"
 #include "vpx_denoise.hpp"
+#include "vpx_reproject.hpp"
 
 using namespace vpx;
 
@@ -65,6 +67,9 @@ constexpr int kTile = 16;  // 16x16 pixels per tile / 256-thread workgroup
 #define VPX_TAIL_MIN_DEPTH 8
 #endif
 constexpr int kThreads = 256;
+#ifndef VPX_REPROJECT_PREKEY
+#define VPX_REPROJECT_PREKEY 0  // vpx_reproject_ids reads the previous ids themselves (1: k_plane_key's keys)
+#endif
 #ifndef VPX_DENOISE_LDS
 #define VPX_DENOISE_LDS 1  // denoise steps 1 and 2 stage tile + halo in LDS (0: every step gathers from global memory)
 #endif
@@ -704,6 +709,56 @@ void launch_atrous(hipStream_t st, uint32_t tiles, const DenoiseArgs& a, const u
     }
 #endif
     hipLaunchKernelGGL((k_atrous_gather<LUM>), dim3(tiles), dim3(kThreads), 0, st, a, keys, src, dst, rgb8);
+}
+
+// ------------------------------------------------------------------ plane-keyed reprojection
+// vpx_reproject_ids (vpx_reproject.hpp holds the definition and the arithmetic: reproject::pixel).
+// One lane per pixel, a 16x16 tile per workgroup, lane t at (t & 15, t >> 4) as the denoise; the
+// record and the sample are one 16-byte load each, the result one 16-byte store.  pixel() asks for
+// the four previous keys from clamped addresses before any history colour, so the four loads go
+// out together, and for a colour only under a tap that is in the image, weighs and has the key.
+// PREKEY: the previous keys come from k_plane_key's uint2 array (8 bytes per tap, one more
+// launch) instead of the ids themselves (16 bytes per tap, 12 of them used).  MOVING = false
+// carries no volume table, RGB8 = false no tonemap.
+template <bool MOVING, bool RGB8, bool PREKEY>
+__global__ __launch_bounds__(kThreads) void k_reproject_ids(reproject::Args a, uint32_t tiles_x,
+                                                            const uint4* __restrict__ ids_cur,
+                                                            const void* __restrict__ prev, const float4* __restrict__ cur,
+                                                            const float4* __restrict__ hist_in,
+                                                            float4* __restrict__ hist_out, uint32_t* __restrict__ rgb8,
+                                                            const float* __restrict__ tab,
+                                                            const uint32_t* __restrict__ moved) {
+    const uint32_t x = (blockIdx.x % tiles_x) * kTile + (threadIdx.x & 15u);
+    const uint32_t y = (blockIdx.x / tiles_x) * kTile + (threadIdx.x >> 4);
+    if (x >= a.width || y >= a.height) return;
+    const uint64_t q = (uint64_t)y * a.width + x;
+    const uint4 id = ids_cur[q];
+    const float4 c = cur[q];
+    auto prev_key = [prev](uint64_t i) {
+        if (PREKEY) {
+            const uint2 k = reinterpret_cast<const uint2*>(prev)[i];
+            return denoise::Key{k.x, k.y};
+        }
+        const uint4 r = reinterpret_cast<const uint4*>(prev)[i];
+        return denoise::plane_key(r.y, r.z, r.w);
+    };
+    auto hist = [hist_in](uint64_t i) {
+        const float4 h = hist_in[i];
+        return reproject::Rgbw{h.x, h.y, h.z, h.w};
+    };
+    const reproject::Rgbw o = reproject::pixel<MOVING>(a, x, y, reproject::Id{id.x, id.y, id.z, id.w},
+                                                       reproject::Rgbw{c.x, c.y, c.z, c.w}, prev_key, hist, tab, moved);
+    const float4 out = make_float4(o.r, o.g, o.b, o.w);
+    hist_out[q] = out;
+    if (RGB8) rgb8[q] = tonemap_pack(out);
+}
+
+template <bool MOVING, bool RGB8>
+void launch_reproject(hipStream_t st, uint32_t tiles, const reproject::Args& a, uint32_t tiles_x, const uint4* ids_cur,
+                      const void* prev, const float4* cur, const float4* hist_in, float4* hist_out, uint32_t* rgb8,
+                      const float* tab, const uint32_t* moved) {
+    hipLaunchKernelGGL((k_reproject_ids<MOVING, RGB8, VPX_REPROJECT_PREKEY != 0>), dim3(tiles), dim3(kThreads), 0, st, a,
+                       tiles_x, ids_cur, prev, cur, hist_in, hist_out, rgb8, tab, moved);
 }
 
 // BasicBVH::IntersectBVH (src/BVH/BasicBVH.cpp:19-70), one ray per lane.  The workgroup
@@ -1607,6 +1662,16 @@ struct vpx_ctx {
     // ran more than one pass; carved per call for the call's size
     void* dn_buf = nullptr;
     size_t dn_bytes = 0;
+    // vpx_reproject_ids' scratch: the volume table (24 floats per volume, then a moved flag per
+    // volume) and, in the VPX_REPROJECT_PREKEY form, the previous keys; rj_host: the table's pinned
+    // staging copy, rewritten only after rj_ev (its last upload) has passed; rj_last: the table the
+    // device holds, so that an unchanged one is not uploaded again
+    void* rj_buf = nullptr;
+    size_t rj_bytes = 0;
+    void* rj_host = nullptr;
+    size_t rj_host_bytes = 0;
+    hipEvent_t rj_ev = nullptr;
+    std::vector<uint32_t> rj_last;
     // vpx_cast_*: the pool form's grab block (kGrabBlock words, zeroed on the stream per call; comes
     // with the first call), and what the last call launched (vpx_debug_last_cast_kernel)
     uint32_t* cast_grab = nullptr;
@@ -2363,6 +2428,9 @@ int vpx_destroy(vpx_ctx* c) {
     if (c->rp_buf) (void)hipFree(c->rp_buf);
     if (c->win_buf) (void)hipFree(c->win_buf);
     if (c->dn_buf) (void)hipFree(c->dn_buf);
+    if (c->rj_buf) (void)hipFree(c->rj_buf);
+    if (c->rj_host) (void)hipHostFree(c->rj_host);
+    if (c->rj_ev) (void)hipEventDestroy(c->rj_ev);
     if (c->cast_grab) (void)hipFree(c->cast_grab);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
@@ -3947,6 +4015,97 @@ int vpx_denoise_ids(vpx_ctx* c, const vpx_frame_params* p, const uint32_t* ids, 
         else
             launch_atrous<false>(c->stream, tiles, a, keys, src, dst, last ? rgb8 : nullptr);
         src = dst;
+    }
+    VPX_HIP(c, hipGetLastError());
+    return VPX_OK;
+}
+
+// The volume table of a vpx_reproject_ids call into c->rj_buf, on the stream; skipped when the
+// device already holds these bytes.
+static int reproject_table(vpx_ctx* c, uint32_t n, const vpx_volume* cur_volumes, const vpx_volume* prev_volumes) {
+    const size_t words = (size_t)n * (reproject::kTabFloats + 1u);
+    std::vector<uint32_t> t;
+    try {
+        t.resize(words);
+    } catch (const std::bad_alloc&) {
+        return fail(c, VPX_E_NOMEM, "reproject volume table");
+    }
+    reproject::build_table(n, cur_volumes, prev_volumes, reinterpret_cast<float*>(t.data()),
+                           t.data() + (size_t)n * reproject::kTabFloats);
+    if (t == c->rj_last) return VPX_OK;
+    if (!c->rj_ev) VPX_HIP(c, hipEventCreateWithFlags(&c->rj_ev, hipEventDisableTiming));
+    VPX_HIP(c, hipEventSynchronize(c->rj_ev));  // the staging copy's last upload (long past, as a rule)
+    if (words * 4 > c->rj_host_bytes) {
+        if (c->rj_host) (void)hipHostFree(c->rj_host);
+        c->rj_host = nullptr;
+        c->rj_host_bytes = 0;
+        if (hipHostMalloc(&c->rj_host, words * 4) != hipSuccess) {
+            c->rj_host = nullptr;
+            return fail(c, VPX_E_NOMEM, "reproject volume table staging");
+        }
+        c->rj_host_bytes = words * 4;
+    }
+    memcpy(c->rj_host, t.data(), words * 4);
+    c->rj_last.clear();
+    VPX_HIP(c, hipMemcpyAsync(c->rj_buf, c->rj_host, words * 4, hipMemcpyHostToDevice, c->stream));
+    VPX_HIP(c, hipEventRecord(c->rj_ev, c->stream));
+    c->rj_last.swap(t);
+    return VPX_OK;
+}
+
+int vpx_reproject_ids(vpx_ctx* c, const vpx_frame_params* p, const uint32_t* ids_cur, const uint32_t* ids_prev,
+                      const float* cur, const float* hist_in, float* hist_out, uint32_t* rgb8, const vpx_reproject* r,
+                      const vpx_volume* cur_volumes, const vpx_volume* prev_volumes) {
+    VPX_GROUP_FIRST(c, vpx_reproject_ids(m_, p, ids_cur, ids_prev, cur, hist_in, hist_out, rgb8, r, cur_volumes, prev_volumes));
+    if (!c || !p) return fail(c, VPX_E_INVALID, "null argument");
+    if (const char* why = reproject::check_call(p->width, p->height, ids_cur, ids_prev, cur, hist_in, hist_out, r, cur_volumes,
+                                                prev_volumes))
+        return fail(c, VPX_E_INVALID, why);
+    VPX_HIP(c, hipSetDevice(c->device));
+    const bool have_prev = ids_prev != nullptr;
+    const size_t pixels = (size_t)p->width * p->height;
+    const size_t tab_bytes = ((size_t)r->n_volumes * (reproject::kTabFloats + 1u) * 4 + 255) & ~(size_t)255;
+    const size_t key_bytes = (VPX_REPROJECT_PREKEY && have_prev) ? pixels * sizeof(uint2) : 0;
+    const size_t bytes = tab_bytes + key_bytes;
+    if (bytes > c->rj_bytes) {
+        VPX_HIP(c, sync_all(c));  // an earlier call may still read the old scratch
+        if (c->rj_buf) (void)hipFree(c->rj_buf);
+        c->rj_buf = nullptr;
+        c->rj_bytes = 0;
+        c->rj_last.clear();
+        if (hipMalloc(&c->rj_buf, bytes) != hipSuccess) {
+            c->rj_buf = nullptr;
+            return fail(c, VPX_E_NOMEM, "reproject scratch");
+        }
+        c->rj_bytes = bytes;
+    }
+    const float* tab = reinterpret_cast<const float*>(c->rj_buf);
+    const uint32_t* moved = reinterpret_cast<const uint32_t*>(c->rj_buf) + (size_t)r->n_volumes * reproject::kTabFloats;
+    if (r->n_volumes)
+        if (int rc = reproject_table(c, r->n_volumes, cur_volumes, prev_volumes)) return rc;
+    const void* prev = ids_prev;
+    if (key_bytes) {
+        uint2* keys = reinterpret_cast<uint2*>((char*)c->rj_buf + tab_bytes);
+        hipLaunchKernelGGL(k_plane_key, dim3((uint32_t)((pixels + kThreads - 1) / kThreads)), dim3(kThreads), 0, c->stream,
+                           (uint32_t)pixels, reinterpret_cast<const uint4*>(ids_prev), keys);
+        prev = keys;
+    }
+    const reproject::Args a = reproject::make_args(p->width, p->height, *r, have_prev);
+    const uint32_t tiles_x = (p->width + kTile - 1) / kTile;
+    const uint32_t tiles = tiles_x * ((p->height + kTile - 1) / kTile);
+    const uint4* ic = reinterpret_cast<const uint4*>(ids_cur);
+    const float4 *cu = reinterpret_cast<const float4*>(cur), *hi = reinterpret_cast<const float4*>(hist_in);
+    float4* ho = reinterpret_cast<float4*>(hist_out);
+    if (r->n_volumes) {
+        if (rgb8)
+            launch_reproject<true, true>(c->stream, tiles, a, tiles_x, ic, prev, cu, hi, ho, rgb8, tab, moved);
+        else
+            launch_reproject<true, false>(c->stream, tiles, a, tiles_x, ic, prev, cu, hi, ho, rgb8, tab, moved);
+    } else {
+        if (rgb8)
+            launch_reproject<false, true>(c->stream, tiles, a, tiles_x, ic, prev, cu, hi, ho, rgb8, tab, moved);
+        else
+            launch_reproject<false, false>(c->stream, tiles, a, tiles_x, ic, prev, cu, hi, ho, rgb8, tab, moved);
     }
     VPX_HIP(c, hipGetLastError());
     return VPX_OK;

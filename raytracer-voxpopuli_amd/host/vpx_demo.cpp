@@ -8,7 +8,8 @@
 //   y < 2 + h, h = ((x >> 4) * 7 + (z >> 4) * 13) % 5 * n / 16 -> material 16 + (h % 4).
 //
 // usage: vpx_demo [n] [width] [height] [frames] [max_bounces] [out.rgb8] [mode] [devices]
-//   mode: letters — 's' staticCamera (the reprojection branch of Tick), 'k' activateSky
+//   mode: letters — 's' staticCamera (the reprojection branch of Tick), 't' a moving camera with
+//   temporal accumulation (Renderer::temporal: every tick a step along a path), 'k' activateSky
 //   with the demo sky texture (demo_sky below; tests rebuild it with numpy); 'p' puts a block
 //   of player smoke (SMOKE_PLAYER, cells x in [3n/4, 7n/8), y in [2, 2 + n/4), z in [n/4, 3n/8),
 //   albedo (0.8, 0.75, 0.7)) into the world under a point light of colour 8, tracks the player
@@ -280,9 +281,9 @@ int main(int argc, char** argv) {
     const char* out = argc > 6 && argv[6][0] != '-' ? argv[6] : nullptr;
     const char* mode = argc > 7 ? argv[7] : "";
     bool is_static = false, sky = false, player_light = false, player_cast = false, prop_edit = false,
-         generate = false;
+         generate = false, temporal = false;
     for (const char* m = mode; *m; ++m)
-        is_static |= *m == 's', sky |= *m == 'k', player_light |= *m == 'p', player_cast |= *m == 'w', prop_edit |= *m == 'm',
+        temporal |= *m == 't', is_static |= *m == 's', sky |= *m == 'k', player_light |= *m == 'p', player_cast |= *m == 'w', prop_edit |= *m == 'm',
             generate |= *m == 'g';
     std::vector<int> devices;
     if (argc > 8)
@@ -339,6 +340,8 @@ int main(int argc, char** argv) {
         r.activateSky = true;
     }
     r.staticCamera = is_static;
+    if (temporal)  // a moving camera with temporal accumulation: every tick a step along a path, no material left out
+        r.temporal = true, r.temporalNohistLo = 1u, r.temporalNohistHi = 0u;
     r.trackPlayerLight = player_light;
     vpx_player_light run{};  // the Ticks' records, summed
     uint32_t ticks_in_light = 0;
@@ -354,6 +357,10 @@ int main(int argc, char** argv) {
     double primary = 0, shadow = 0;
     const auto t0 = std::chrono::steady_clock::now();
     for (int f = 1; f < frames; ++f) {
+        if (temporal) {
+            const float at[3] = {pos[0] + 0.01f * (float)f, pos[1] + 0.004f * (float)f, pos[2] - 0.008f * (float)f};
+            CHECK(r.LookAt(at, target));
+        }
         CHECK(r.Tick(0.0f, &st));
         note();
         primary += (double)st.primary_rays;

@@ -3,6 +3,8 @@
 
 #include <hip/hip_runtime_api.h>
 
+#include <cstring>
+
 namespace vpxhost {
 
 Renderer::Renderer(int device) : device_(device) { status_ = vpx_create(device, &ctx_); }
@@ -17,6 +19,8 @@ Renderer::~Renderer() {
     if (history_) (void)hipFree(history_);
     if (denoised_) (void)hipFree(denoised_);
     if (ids_) (void)hipFree(ids_);
+    for (void* b : {(void*)tIds_[0], (void*)tIds_[1], (void*)tHist_[0], (void*)tHist_[1]})
+        if (b) (void)hipFree(b);
     if (ctx_) vpx_destroy(ctx_);
 }
 
@@ -39,6 +43,12 @@ int Renderer::Init(uint32_t width, uint32_t height) {
         hipMemset(screen_, 0, sizeof(uint32_t) * width * height) != hipSuccess) {
         err_ = "frame buffer allocation failed";
         return VPX_E_NOMEM;
+    }
+    if (width != width_ || height != height_) {  // a resize drops the temporal history and its buffers
+        for (void* b : {(void*)tIds_[0], (void*)tIds_[1], (void*)tHist_[0], (void*)tHist_[1]})
+            if (b) (void)hipFree(b);
+        tIds_[0] = tIds_[1] = nullptr, tHist_[0] = tHist_[1] = nullptr;
+        tValid_ = false;
     }
     width_ = width, height_ = height;
     numRenderedFrames = 0;
@@ -264,7 +274,85 @@ int Renderer::Tick(float /*deltaTime*/, vpx_stats* stats) {
         rc = vpx_set_camera(ctx_, &camera);
         if (rc) return rc;
     }
-    return ReadPlayerLight(Update(stats));
+    return ReadPlayerLight(temporal ? UpdateTemporal(stats) : Update(stats));
+}
+
+// The moving-camera branch with temporal accumulation (no reference counterpart): vpx_render at
+// frame_index 0 (the accumulator holds this tick's samples alone; the seed stream is the tick
+// number's), vpx_render_ids, vpx_reproject_ids from the previous tick's ids, history and camera,
+// then optionally vpx_denoise_ids on the new history; the screen shows the last of them.  The
+// history, not the denoised image, is what the next tick reads.  Volumes whose matrices changed
+// since the previous tick are followed.  Queued on the context's stream.
+int Renderer::UpdateTemporal(vpx_stats* stats) {
+    if (status_) return status_;
+    if (!accumulator_) return VPX_E_STATE;
+    const size_t pixels = (size_t)width_ * height_;
+    if (!tHist_[0]) {
+        if (hipSetDevice(device_) != hipSuccess || hipMalloc(&tIds_[0], 16 * pixels) != hipSuccess ||
+            hipMalloc(&tIds_[1], 16 * pixels) != hipSuccess || hipMalloc(&tHist_[0], 16 * pixels) != hipSuccess ||
+            hipMalloc(&tHist_[1], 16 * pixels) != hipSuccess ||
+            (temporalDenoisePasses && !denoised_ && hipMalloc(&denoised_, 16 * pixels) != hipSuccess)) {
+            err_ = "temporal buffer allocation failed";
+            return VPX_E_NOMEM;
+        }
+        tValid_ = false;
+    }
+    if (temporalDenoisePasses && !denoised_ && hipMalloc(&denoised_, 16 * pixels) != hipSuccess) {
+        err_ = "denoise buffer allocation failed";
+        return VPX_E_NOMEM;
+    }
+    vpx_frame_params p{};
+    p.width = width_, p.height = height_;
+    p.max_bounces = maxBounces;
+    p.frame_index = 0;
+    p.seed_base = tTicks_ * (width_ * height_);
+    p.flags = (flags & ~VPX_FLAG_SKY) | (activateSky ? VPX_FLAG_SKY : 0u);
+    p.aa_strength = antiAliasingStrength;
+    p.area_samples = numCheckShadowsAreaLight;
+    p.sky[0] = sky[0], p.sky[1] = sky[1], p.sky[2] = sky[2];
+    int rc = vpx_render(ctx_, &p, accumulator_, nullptr, stats);
+    if (rc) return rc;
+    numRenderedFrames = 1;
+    const int cur = tCur_, prev = 1 - tCur_;
+    if ((rc = vpx_render_ids(ctx_, &p, nullptr, tIds_[cur]))) return rc;
+    vpx_reproject r{};
+    r.cur = camera;
+    vpx_prev_camera here{};
+    if ((rc = vpx_prev_camera_look_at(camPos_, camTarget_, width_, height_, &here))) return rc;
+    r.prev = tValid_ ? tPrevCamera_ : here;
+    r.max_history = temporalMaxHistory;
+    r.nohist_lo = temporalNohistLo, r.nohist_hi = temporalNohistHi;
+    bool moved = false;
+    if (tValid_ && tPrevVolumes_.size() == volumes_.size())
+        for (size_t v = 0; v < volumes_.size() && !moved; ++v)
+            moved = memcmp(volumes_[v].matrix, tPrevVolumes_[v].matrix, sizeof(volumes_[v].matrix)) != 0 ||
+                    memcmp(volumes_[v].inv_matrix, tPrevVolumes_[v].inv_matrix, sizeof(volumes_[v].inv_matrix)) != 0;
+    r.n_volumes = moved ? (uint32_t)volumes_.size() : 0u;
+    uint32_t* target = nullptr;
+    if ((rc = MapScreen(&target))) return rc;
+    rc = vpx_reproject_ids(ctx_, &p, tIds_[cur], tValid_ ? tIds_[prev] : nullptr, accumulator_,
+                           tValid_ ? tHist_[prev] : nullptr, tHist_[cur], temporalDenoisePasses ? nullptr : target, &r,
+                           moved ? volumes_.data() : nullptr, moved ? tPrevVolumes_.data() : nullptr);
+    if (rc == VPX_OK && temporalDenoisePasses) {
+        const vpx_denoise d{temporalDenoisePasses, temporalSigmaL, 0u, 0u};
+        rc = vpx_denoise_ids(ctx_, &p, tIds_[cur], tHist_[cur], denoised_, target, &d);
+    }
+    rc = UnmapScreen(rc);
+    if (rc) return rc;
+    temporalHistory_ = tHist_[cur];
+    tPrevCamera_ = here, tPrevVolumes_ = volumes_;
+    tCur_ = prev, tValid_ = true, ++tTicks_;
+    return VPX_OK;
+}
+
+int Renderer::CopyTemporalHistory(float* host_rgba) const {
+    if (status_) return status_;
+    if (!temporalHistory_) return VPX_E_STATE;
+    const int rc = vpx_synchronize(ctx_);
+    if (rc) return rc;
+    return hipMemcpy(host_rgba, temporalHistory_, sizeof(float) * 4 * width_ * height_, hipMemcpyDeviceToHost) == hipSuccess
+               ? VPX_OK
+               : VPX_E_DEVICE;
 }
 
 int Renderer::ReadPlayerLight(int rc) {

@@ -124,6 +124,20 @@ public:
     // image (CopyDenoised) and tonemapped into the screen.  Queued on the context's stream.
     int Denoise(uint32_t passes = 5, float sigma_l = 0.0f);
     int CopyDenoised(float* host_rgba) const;
+    // Temporal accumulation under camera motion (vpx_reproject_ids; no reference counterpart: the
+    // reference resets its accumulator when the camera moves).  With `temporal` set, Tick's
+    // moving-camera branch renders one sample per pixel, carries the previous tick's history to the
+    // new camera where the ID buffer names the same plane, and optionally runs the plane-keyed
+    // filter on the result (temporalDenoisePasses > 0); the history image is kept for the next tick
+    // (CopyTemporalHistory reads it, .w the history length).  DropHistory starts afresh; so does a
+    // resize (Init).  Off by default.
+    bool temporal = false;
+    float temporalMaxHistory = 32.0f;
+    uint32_t temporalNohistLo = 5, temporalNohistHi = 14;  // metal, glass, smoke: view-dependent
+    uint32_t temporalDenoisePasses = 0;
+    float temporalSigmaL = 0.0f;
+    void DropHistory() { tValid_ = false; }
+    int CopyTemporalHistory(float* host_rgba) const;
     // Ray batches that already live on the device (vpx_cast_nearest / vpx_cast_occluded; no reference
     // counterpart: per ray the records of Renderer::FindNearest / IsOccluded): rays, hits, cells and
     // occluded are DEVICE pointers of n elements, cells may be NULL; filter NULL = everything, opt
@@ -171,6 +185,7 @@ private:
     std::vector<std::array<float, 3>> scaleModel_;
     size_t numVolumes_ = 0;  // voxelVolumes.size() as SetVolumes left it
     int UpdateStatic(vpx_stats* stats);
+    int UpdateTemporal(vpx_stats* stats);
     int ReadPlayerLight(int rc);  // after a Tick's render (rc: its status)
     int MapScreen(uint32_t** out) const;  // the frame's RGB8 target: the GL buffer or screen_
     int UnmapScreen(int rc) const;
@@ -186,6 +201,14 @@ private:
     uint32_t* screen_ = nullptr;    // uint32[W*H] in HBM
     float* denoised_ = nullptr;     // Denoise(): float4[W*H] in HBM
     uint32_t* ids_ = nullptr;       // ... and its ID buffer, uint4[W*H]
+    uint32_t* tIds_[2] = {nullptr, nullptr};  // UpdateTemporal(): this tick's and the previous tick's ids ...
+    float* tHist_[2] = {nullptr, nullptr};    // ... and history images, swapped per tick
+    float* temporalHistory_ = nullptr;        // the one the last tick wrote
+    int tCur_ = 0;
+    bool tValid_ = false;
+    uint32_t tTicks_ = 0;
+    vpx_prev_camera tPrevCamera_{};
+    std::vector<vpx_volume> tPrevVolumes_;
     std::string err_;
 };
 

@@ -7,6 +7,8 @@ libvpx_hip.so (`vpx_render`) instead of the execution::par pixel loop
 0x00RRGGBB, template/surface.h) live in HBM as torch tensors; `screen_host()` copies the
 8-bit frame out for display.  The C++ twin of this class is host/vpx_renderer.{h,cpp}.
 """
+import ctypes as C
+
 import numpy as np
 import torch
 
@@ -50,8 +52,22 @@ class Ray:
 
 
 class Renderer:
-    def __init__(self, scene, device=0, ctx=None):
+    def __init__(self, scene, device=0, ctx=None, temporal=None):
         self.scene = scene
+        # temporal accumulation under camera motion (vpx_reproject_ids; no reference counterpart).
+        # None / False: Tick's moving-camera branch as the reference has it.  True or a dict of
+        # max_history (32), nohist (the (lo, hi) first-hit materials without history: metal, glass
+        # and smoke, 5..14), denoise (None, or a dict of passes / sigma_l for Denoise's filter on
+        # the result): see _tick_temporal.
+        self.temporal = None
+        if temporal:
+            self.temporal = dict(max_history=32, nohist=(5, 14), denoise=None)
+            if isinstance(temporal, dict):
+                self.temporal.update(temporal)
+        self.history = None           # the temporal mode's current history image, float4[W*H], .w its length
+        self._t_ids, self._t_hist = None, None   # two ID buffers and two history images, swapped per tick
+        self._t_cur, self._t_valid, self._t_ticks = 0, False, 0
+        self._t_prev_camera, self._t_prev_volumes = None, None
         self.device = torch.device("cuda", device)
         self.ctx = ctx or Context(device)
         self.maxBounces = scene.max_bounces               # renderer.h:175
@@ -131,7 +147,7 @@ class Renderer:
             if self.scene.flags & abi.VPX_FLAG_DOF:  # focus ray, renderer.cpp:1987-1991
                 self.scene.camera.focal_distance = self.ctx.focus_distance(self.scene.width, self.scene.height)
                 self.ctx.set_camera(self.scene.camera)
-            st = self.Update(stats=stats)
+            st = self._tick_temporal(stats) if self.temporal else self.Update(stats=stats)
             self._read_player_light()
             return st
         # static branch (renderer.cpp:1996-2101): TraceReproject + history reprojection
@@ -147,6 +163,70 @@ class Renderer:
         self.numRenderedFrames += 1
         self._read_player_light()
         return st
+
+    def LookAt(self, pos, target):
+        """Move the camera (Camera::HandleInput's basis, vpx_camera_look_at) and hand it to the context."""
+        from .scene import look_at
+        self.scene.camera = look_at(pos, target, self.scene.width, self.scene.height)
+        self.scene._cam_pos, self.scene._cam_target = tuple(pos), tuple(target)
+        self.ctx.set_camera(self.scene.camera)
+
+    def DropHistory(self):
+        """Forget the temporal mode's history: the next Tick starts from its own samples."""
+        self._t_valid = False
+
+    def _tick_temporal(self, stats=False):
+        """One Tick of a moving camera with temporal accumulation, queued on the renderer's stream
+        without synchronising: vpx_render with frame_index 0 (the accumulator holds this tick's
+        samples alone; the seed stream is the tick number's, so that a camera that stands still for
+        a tick does not draw the same noise again), vpx_render_ids, vpx_reproject_ids from the
+        previous tick's ids, history and camera into self.history, then optionally vpx_denoise_ids
+        on self.history into self.denoised; the screen shows the last of them.  The history, not
+        the denoised image, is what the next tick reads.  A change of the frame's size drops the
+        history; so does DropHistory().  Volumes whose matrices changed since the previous tick are
+        followed (vpx_reproject's moving volumes)."""
+        from .scene import prev_camera
+        t = self.temporal
+        w, h = self.scene.width, self.scene.height
+        if self._t_hist is None or self._t_hist[0].numel() != w * h * 4:
+            with torch.cuda.stream(self.stream):
+                self._t_ids = [torch.empty(w * h * 4, dtype=torch.int32, device=self.device) for _ in range(2)]
+                self._t_hist = [torch.empty(w * h * 4, dtype=torch.float32, device=self.device) for _ in range(2)]
+            self._t_valid = False
+        p = self._frame_params()
+        p.frame_index = 0
+        p.seed_base = (p.seed_base + self._t_ticks * w * h) & 0xFFFFFFFF
+        p.aa_strength = self.antiAliasingStrength
+        self.last_stats = self.ctx.render(p, self.accumulator.data_ptr(), None, stats=stats)
+        self.numRenderedFrames = 1
+        cur, prev = self._t_cur, 1 - self._t_cur
+        ids, hist = self._t_ids, self._t_hist
+        self.ctx._chk(self.ctx.lib.vpx_render_ids(self.ctx.h, C.byref(p), None, C.c_void_p(ids[cur].data_ptr())),
+                      "vpx_render_ids")
+        volumes = [abi.Volume.from_buffer_copy(v) for v in self.scene.volumes]
+        here = prev_camera(self.scene._cam_pos, self.scene._cam_target, w, h)
+        moved = (self._t_valid and self._t_prev_volumes is not None and len(self._t_prev_volumes) == len(volumes) and
+                 any(bytes(a) != bytes(b) for a, b in zip(volumes, self._t_prev_volumes)))
+        with torch.cuda.stream(self.stream):
+            if t["denoise"] and self.denoised is None:
+                self.denoised = torch.empty_like(self.accumulator)
+        self.ctx.reproject(p, ids[cur], ids[prev] if self._t_valid else None, self.accumulator,
+                           hist[prev] if self._t_valid else None, self.scene.camera,
+                           self._t_prev_camera if self._t_valid else here, out=hist[cur], max_history=t["max_history"],
+                           nohist=t["nohist"], cur_volumes=volumes if moved else None,
+                           prev_volumes=self._t_prev_volumes if moved else None,
+                           rgb_ptr=None if t["denoise"] else self.screen.data_ptr())
+        if t["denoise"]:
+            self.ctx.denoise(p, ids[cur], hist[cur], self.denoised, t["denoise"].get("passes", 5),
+                             t["denoise"].get("sigma_l", 0.0), self.screen.data_ptr())
+        self.history, self.ids = hist[cur], ids[cur]
+        self._t_prev_camera, self._t_prev_volumes = here, volumes
+        self._t_cur, self._t_valid, self._t_ticks = prev, True, self._t_ticks + 1
+        return self.last_stats
+
+    def temporal_history_host(self):
+        self.synchronize()
+        return self.history.cpu().numpy().reshape(self.scene.height, self.scene.width, 4)
 
     def _read_player_light(self):
         """The frame's flag, read and cleared after the render on both branches: the reference's

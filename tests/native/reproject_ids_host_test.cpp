@@ -1,0 +1,136 @@
+// reproject_ids_host_test.cpp — csrc/vpx_reproject.hpp's host path in a stand-alone program, meant
+// to be built with -fsanitize=address,undefined: every buffer is a heap block of exactly the size
+// the call is entitled to, so a tap read outside the image, a volume index past the table or a
+// record used as an index is a report.  The ids are a plane facing the camera (t so that the hit
+// point lies on z = 4), striped into two keys, with a band of invalid records, arbitrary bits where
+// the key does not read, and volume numbers up to 65535; the previous camera stands beside, behind
+// or exactly where the current one stands; sizes 1x1, 5x3 and 67x35; static and moving volumes,
+// with and without rgb8, with and without a previous frame.  Checked here: the no-history output is
+// (cur.rgb, 1), lengths stay in 1..max_history, a constant image comes back within 16 ulp, and
+// rgb8 is the tonemap of the output.  (The bits are tests/test_reproject_ids.py's business.)
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+#include <vector>
+
+#include "vpx_reproject.hpp"
+
+using namespace vpx::reproject;
+
+static uint32_t rng_state = 0x2468ace1u;
+static uint32_t rnd() {
+    rng_state ^= rng_state << 13, rng_state ^= rng_state >> 17, rng_state ^= rng_state << 5;
+    return rng_state;
+}
+
+// A camera at `pos` looking down +z: the image plane two units ahead, 2 * aspect wide and 2 high.
+static vpx_camera camera_at(float x, float y, float z, float aspect) {
+    vpx_camera c{};
+    const float p[3] = {x, y, z};
+    for (int k = 0; k < 3; ++k) c.cam_pos[k] = c.top_left[k] = c.top_right[k] = c.bottom_left[k] = p[k];
+    c.top_left[0] -= aspect, c.top_left[1] += 1.f, c.top_left[2] += 2.f;
+    c.top_right[0] += aspect, c.top_right[1] += 1.f, c.top_right[2] += 2.f;
+    c.bottom_left[0] -= aspect, c.bottom_left[1] -= 1.f, c.bottom_left[2] += 2.f;
+    return c;
+}
+// Its frustum normals, pointing into the pyramid (Camera::SetFrustumNormals); sign: -1 looks down -z.
+static vpx_prev_camera prev_at(float x, float y, float z, float aspect, float sign) {
+    vpx_prev_camera p{};
+    p.cam_pos[0] = x, p.cam_pos[1] = y, p.cam_pos[2] = z;
+    p.left_normal[0] = 2.f, p.left_normal[2] = aspect * sign;
+    p.right_normal[0] = -2.f, p.right_normal[2] = aspect * sign;
+    p.top_normal[1] = -2.f, p.top_normal[2] = sign;
+    p.bottom_normal[1] = 2.f, p.bottom_normal[2] = sign;
+    return p;
+}
+
+static std::vector<uint32_t> make_ids(uint32_t W, uint32_t H, const vpx_camera& c, uint32_t n_volumes) {
+    std::vector<uint32_t> ids((size_t)W * H * 4);
+    for (uint32_t y = 0; y < H; ++y)
+        for (uint32_t x = 0; x < W; ++x) {
+            uint32_t* r = &ids[4 * ((size_t)y * W + x)];
+            // the ray's length to the plane z = 4
+            const float u = (float)x / (float)W, v = (float)y / (float)H;
+            const float dx = (c.top_left[0] + (c.top_right[0] - c.top_left[0]) * u) - c.cam_pos[0];
+            const float dy = (c.top_left[1] + (c.bottom_left[1] - c.top_left[1]) * v) - c.cam_pos[1];
+            const float t = (4.f - c.cam_pos[2]) * std::sqrt(dx * dx + dy * dy + 4.f) / 2.f;
+            memcpy(&r[0], &t, 4);
+            r[2] = rnd(), r[3] = (x / 3u) % 2u;  // face 5: axis 2, the coordinate in .w
+            const uint32_t kind = y * 5 < H * 4 ? 0u : 1u + x * 4 / W;
+            uint32_t vol = 2u + (n_volumes ? rnd() % (n_volumes + 1u) : 0u);  // one past the table too
+            if ((rnd() & 31u) == 0u) vol = 65535u;
+            const uint32_t v16 = kind == 1 ? 0u : kind == 2 ? 1u : vol;
+            const uint32_t face = kind == 0 ? 5u : kind == 1 ? 0u : kind == 2 ? 2u : kind == 3 ? 0u : 7u + (rnd() & 0xf8u);
+            r[1] = v16 | (kind == 0 ? 3u + (rnd() & 3u) : rnd() & 0xffu) << 16 | face << 24;
+            if (kind != 0) r[0] = rnd();  // any t at all, NaN and infinity included
+        }
+    return ids;
+}
+
+static long ulps(float a, float b) {
+    int32_t ia, ib;
+    memcpy(&ia, &a, 4), memcpy(&ib, &b, 4);
+    return ia > ib ? (long)ia - ib : (long)ib - ia;
+}
+
+int main() {
+    long bad = 0, calls = 0, took = 0;
+    const uint32_t sizes[3][2] = {{1, 1}, {5, 3}, {67, 35}};
+    const float prevs[4][4] = {{0.f, 0.f, 0.f, 1.f}, {0.15f, -0.1f, 0.2f, 1.f}, {0.f, 0.f, -0.5f, 1.f}, {0.f, 0.f, 8.f, -1.f}};
+    for (const auto& sz : sizes)
+        for (const auto& pv : prevs)
+            for (uint32_t n_volumes = 0; n_volumes <= 3; n_volumes += 3)
+                for (int with_prev = 0; with_prev < 2; ++with_prev)
+                    for (int constant = 0; constant < 2; ++constant) {
+                        const uint32_t W = sz[0], H = sz[1];
+                        const size_t n = (size_t)W * H;
+                        const float aspect = (float)W / (float)H;
+                        vpx_reproject r{};
+                        r.cur = camera_at(0.f, 0.f, 0.f, aspect);
+                        r.prev = prev_at(pv[0], pv[1], pv[2], aspect, pv[3]);
+                        r.max_history = constant ? 65536.f : 8.f;
+                        r.nohist_lo = 6u, r.nohist_hi = 6u;
+                        r.n_volumes = n_volumes;
+                        std::vector<vpx_volume> cv(n_volumes), pvol(n_volumes);
+                        for (uint32_t v = 0; v < n_volumes; ++v) {
+                            for (int k = 0; k < 4; ++k)
+                                cv[v].matrix[5 * k] = cv[v].inv_matrix[5 * k] = pvol[v].matrix[5 * k] = pvol[v].inv_matrix[5 * k] = 1.f;
+                            if (v == 1) pvol[v].matrix[3] = 0.05f, pvol[v].inv_matrix[3] = -0.05f;  // moved along x
+                        }
+                        const std::vector<uint32_t> ids_cur = make_ids(W, H, r.cur, n_volumes);
+                        const std::vector<uint32_t> ids_prev = make_ids(W, H, camera_at(pv[0], pv[1], pv[2], aspect), n_volumes);
+                        std::vector<float> cur(4 * n), hist(4 * n), out(4 * n, -1.f);
+                        std::vector<uint32_t> rgb(n);
+                        for (size_t p = 0; p < n; ++p) {
+                            for (int k = 0; k < 3; ++k) {
+                                cur[4 * p + k] = constant ? 0.7f : 0.015625f * (float)(1u + rnd() % 4096u);
+                                hist[4 * p + k] = constant ? 0.7f : 0.015625f * (float)(1u + rnd() % 4096u);
+                            }
+                            const uint32_t wbits = rnd();
+                            memcpy(&cur[4 * p + 3], &wbits, 4);
+                            hist[4 * p + 3] = (rnd() & 7u) == 0u ? 0.5f : (float)(1u + rnd() % 20u);
+                        }
+                        const uint32_t* ip = with_prev ? ids_prev.data() : nullptr;
+                        const float* hi = with_prev ? hist.data() : nullptr;
+                        if (check_call(W, H, ids_cur.data(), ip, cur.data(), hi, out.data(), &r, cv.data(), pvol.data())) ++bad;
+                        std::vector<float> tab((size_t)n_volumes * kTabFloats);
+                        std::vector<uint32_t> moved(n_volumes);
+                        build_table(n_volumes, cv.data(), pvol.data(), tab.data(), moved.data());
+                        run_host(W, H, ids_cur.data(), ip, cur.data(), hi, out.data(), (calls & 1) ? rgb.data() : nullptr, r,
+                                 tab.data(), moved.data());
+                        for (size_t p = 0; p < n; ++p) {
+                            const float len = out[4 * p + 3];
+                            if (!(len >= 1.f && len <= r.max_history)) ++bad;
+                            if (len == 1.f && memcmp(&out[4 * p], &cur[4 * p], 12)) ++bad;
+                            if (len > 1.f) ++took;
+                            if (len > 1.f && !with_prev) ++bad;
+                            if (constant)
+                                for (int k = 0; k < 3; ++k)
+                                    if (ulps(out[4 * p + k], 0.7f) > 16) ++bad;
+                            if ((calls & 1) && rgb[p] != vpx::denoise::tonemap_pack_host(&out[4 * p])) ++bad;
+                        }
+                        ++calls;
+                    }
+    std::printf("reproject host: calls=%ld took_history=%s bad=%ld\n", calls, took > 1000 ? "yes" : "no", bad);
+    return bad || took <= 1000 ? 1 : 0;
+}
