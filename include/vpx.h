@@ -623,6 +623,10 @@ float vpx_profile_busy_union(const float* se, uint32_t n);
    top (no spot or area lights, constant sky, no VPX_FLAG_DOF).  The forms compute the same
    bits; tests use it to know which one they compared.  Host state only, no synchronisation. */
 int vpx_debug_last_frame_kernel(vpx_ctx* ctx);
+/* Debug: the device and pinned-host allocations the library holds right now, over every context
+   of the process.  A context gives all of its allocations back in vpx_destroy, so the count
+   after it equals the count before vpx_create.  Host state only, no GPU call. */
+uint64_t vpx_debug_live_buffers(void);
 
 /* ---- unit entries (host pointers; mirror the reference per-ray functions) ---------- */
 int vpx_find_nearest(vpx_ctx* ctx, const vpx_ray* rays, uint32_t n, vpx_hit* hits);

@@ -277,6 +277,7 @@ SIGNATURES = {
     "vpx_profile_read": (C.c_int, [C.c_void_p, C.POINTER(Profile), C.c_int]),
     "vpx_profile_busy_union": (C.c_float, [C.POINTER(C.c_float), C.c_uint32]),
     "vpx_debug_last_frame_kernel": (C.c_int, [C.c_void_p]),
+    "vpx_debug_live_buffers": (C.c_uint64, []),
     "vpx_find_nearest": (C.c_int, [C.c_void_p, C.POINTER(Ray), C.c_uint32, C.POINTER(Hit)]),
     "vpx_is_occluded": (C.c_int, [C.c_void_p, C.POINTER(Ray), C.c_uint32, C.c_void_p]),
     "vpx_trace": (C.c_int, [C.c_void_p, C.POINTER(Ray), C.c_void_p, C.c_uint32, C.c_int32, C.POINTER(C.c_float),

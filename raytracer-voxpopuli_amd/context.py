@@ -296,6 +296,10 @@ class Context:
         last render launched: 0 none, 1 specialised on its launch condition, 2 the lean form."""
         return int(self.lib.vpx_debug_last_frame_kernel(self.h))
 
+    def live_buffers(self):
+        """Debug (vpx_debug_live_buffers): device and pinned allocations the library holds, process-wide."""
+        return int(self.lib.vpx_debug_live_buffers())
+
     def counters(self, reset=False):
         st = abi.Stats()
         self._chk(self.lib.vpx_get_counters(self.h, C.byref(st), 1 if reset else 0), "vpx_get_counters")

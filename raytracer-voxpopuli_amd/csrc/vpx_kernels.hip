@@ -29,6 +29,8 @@
 #include <string>
 #include <array>
 #include <atomic>
+#include <initializer_list>
+#include <utility>
 #include <vector>
 
 #include "vpx_wavefront.hpp"
@@ -1548,6 +1550,97 @@ __global__ void checksum_k(const uint8_t* __restrict__ cells, uint64_t count, un
 }  // namespace
 
 // =========================================================================== host side
+struct vpx_ctx;
+namespace {
+int fail(vpx_ctx* c, int code, const std::string& msg);
+hipError_t sync_all(vpx_ctx* c);
+}  // namespace
+
+#define VPX_HIP(c, expr)                                                                            \
+    do {                                                                                            \
+        hipError_t e_ = (expr);                                                                     \
+        if (e_ != hipSuccess)                                                                       \
+            return fail((c), e_ == hipErrorOutOfMemory ? VPX_E_NOMEM : VPX_E_DEVICE,                \
+                        std::string(#expr) + ": " + hipGetErrorString(e_));                         \
+    } while (0)
+
+// Every device or pinned allocation of the library is held by an Owned: move-only, it knows its
+// pointer and its size in bytes and frees in its destructor (the current device is the
+// allocation's: vpx_destroy sets it before `delete`).  g_live_buffers counts what the Owneds of
+// the process hold (vpx_debug_live_buffers); it is touched in alloc and release only.
+static std::atomic<uint64_t> g_live_buffers{0};
+template <typename T, bool kHost = false>  // kHost: pinned host memory instead of device memory
+struct Owned {
+    T* p = nullptr;
+    size_t bytes = 0;
+    Owned() = default;
+    Owned(const Owned&) = delete;
+    Owned& operator=(const Owned&) = delete;
+    Owned(Owned&& o) noexcept : p(o.p), bytes(o.bytes) { o.p = nullptr, o.bytes = 0; }
+    Owned& operator=(Owned&& o) noexcept {
+        if (this != &o) {
+            release();
+            p = o.p, bytes = o.bytes;
+            o.p = nullptr, o.bytes = 0;
+        }
+        return *this;
+    }
+    ~Owned() { release(); }
+    void release() {
+        if (p) {
+            (void)(kHost ? hipHostFree(p) : hipFree(p));
+            g_live_buffers.fetch_sub(1);
+        }
+        p = nullptr, bytes = 0;
+    }
+    // exactly n bytes (what it held is freed first); on failure empty
+    hipError_t alloc(size_t n) {
+        release();
+        void* q = nullptr;
+        const hipError_t e = kHost ? hipHostMalloc(&q, n) : hipMalloc(&q, n);
+        if (e != hipSuccess || !q) return e;
+        p = static_cast<T*>(q), bytes = n;
+        g_live_buffers.fetch_add(1);
+        return hipSuccess;
+    }
+    // at least n bytes: a larger one replaces a smaller (wait: after everything the context has
+    // queued, which may still read the old one); on failure empty
+    int grow(vpx_ctx* c, size_t n, bool wait) {
+        if (n <= bytes) return VPX_OK;
+        if (wait && p) VPX_HIP(c, sync_all(c));
+        VPX_HIP(c, alloc(n));
+        return VPX_OK;
+    }
+    T* get() const { return p; }
+    operator T*() const { return p; }
+    template <typename U>
+    U* as() const {
+        return reinterpret_cast<U*>(p);
+    }
+};
+template <typename T>
+using Pinned = Owned<T, true>;
+// a table of n records: the count travels with the pointer (upload_table)
+template <typename T>
+struct Table {
+    Owned<T> buf;
+    uint32_t n = 0;
+};
+
+// One allocation divided into sub-buffers, each starting 256-byte aligned.  On a null base the
+// same sequence of takes gives the bytes the allocation needs (used()).
+struct Carve {
+    uintptr_t base, q;
+    explicit Carve(void* b) : base((uintptr_t)b), q((uintptr_t)b) {}
+    template <typename T = void>
+    T* take(size_t n) {
+        const uintptr_t r = q;
+        q += (n + 255) & ~(size_t)255;
+        return reinterpret_cast<T*>(r);
+    }
+    size_t used() const { return (size_t)(q - base); }
+};
+
 struct vpx_ctx {
     int device = 0;
     uint32_t cus = 256;  // compute units of the device (the bounce pool's grid)
@@ -1555,10 +1648,9 @@ struct vpx_ctx {
     hipStream_t stream = nullptr;
     std::string err;
     struct GridBuf {
-        uint8_t* ptr = nullptr;
-        uint64_t* l1 = nullptr;
-        uint64_t* l2 = nullptr;
-        uint8_t* dfp = nullptr;  // distance-field octant planes (build_planes_k)
+        Owned<uint8_t> ptr;
+        Owned<uint64_t> l1, l2;
+        Owned<uint8_t> dfp;  // distance-field octant planes (build_planes_k)
         uint32_t n = 0, nb1 = 0, nb2 = 0, nb3 = 0;
         uint64_t plane() const { return 64ull * nb2 * nb2 * nb2; }
     };
@@ -1567,62 +1659,63 @@ struct vpx_ctx {
     // model so that vpx_grid_load_model allocates nothing: the xorshift32 jump tables followed
     // by the load's plan (d_model_aux, the plan staged in the pinned h_plan)
     struct ModelBuf {
-        uint8_t* vox = nullptr;  // voxel_data, sx*sy*sz bytes
-        uint8_t* mat = nullptr;  // random materials, whole chunks of model::kChunk
+        Owned<uint8_t> vox;  // voxel_data, sx*sy*sz bytes
+        Owned<uint8_t> mat;  // random materials, whole chunks of model::kChunk
         uint32_t sx = 0, sy = 0, sz = 0;
     };
     std::vector<ModelBuf> models;
-    uint8_t* d_model_aux = nullptr;
-    uint8_t* h_plan = nullptr;
+    Owned<uint8_t> d_model_aux;
+    Pinned<uint8_t> h_plan;
     // the level refresh's record (refresh_begin), allocated with the context's first edit: the
     // device copy, and pinned [0] its initial state, [1] the read-back
-    RefreshDev* d_refresh = nullptr;
-    RefreshDev* h_refresh = nullptr;
-    DevGrid* d_grids = nullptr;
-    uint32_t d_grids_cap = 0;
+    Owned<RefreshDev> d_refresh;
+    Pinned<RefreshDev> h_refresh;
+    Owned<DevGrid> d_grids;  // grown for grids.size() records (sync_grids)
+    // the volumes: the host copy (its size is the kernels' count), the device table with each
+    // volume's inflated world box (lo, hi: volume_bounds); both grow together (vpx_set_volumes)
     std::vector<vpx_volume> volumes;
-    vpx_volume* d_volumes = nullptr;
-    float4* d_vbounds = nullptr;  // per volume: its cube's inflated world box (lo, hi), see volume_bounds
-    void* d_tlas = nullptr;       // instance TLAS: nodes, then the leaf volume list (build_tlas)
+    Owned<vpx_volume> d_volumes;
+    Owned<float4> d_vbounds;
+    Owned<TlasNode> d_tlas;  // instance TLAS: nodes, then the leaf volume list (build_tlas)
     uint32_t tlas_nodes = 0;
     bool tlas_on = false;
     uint64_t tlas_always = 0;
     int last_frame_kernel = 0;  // the last launch_render's form (vpx_debug_last_frame_kernel)
-    void* d_bvh = nullptr;        // BasicBVH: nodes, then the triangles in tri_idx order (vpx_bvh_set)
-    uint32_t bvh_nodes = 0, bvh_tris = 0;
-    uint32_t d_volumes_cap = 0;
-    vpx_material* d_materials = nullptr;
-    vpx_point_light* d_points = nullptr;
-    vpx_spot_light* d_spots = nullptr;
-    vpx_area_light* d_areas = nullptr;
-    vpx_sphere* d_spheres = nullptr;
-    vpx_triangle* d_triangles = nullptr;
-    uint32_t n_points = 0, n_spots = 0, n_areas = 0, n_spheres = 0, n_triangles = 0;
+    struct Bvh {  // BasicBVH: nodes, then the triangles in tri_idx order (vpx_bvh_set)
+        Owned<uint32_t> img;
+        uint32_t nodes = 0, tris = 0;
+    } bvh;
+    Owned<vpx_material> d_materials;
+    Table<vpx_point_light> points;
+    Table<vpx_spot_light> spots;
+    Table<vpx_area_light> areas;
+    Table<vpx_sphere> spheres;
+    Table<vpx_triangle> triangles;
     vpx_dir_light dir{{1, 0, 0}, {0, 0, 0}};  // DirectionalLight default (DirectionalLight.h:12)
     vpx_camera cam{};
     bool have_materials = false, have_camera = false;
     // sky dome (vpx_set_sky): RGB float texels, equirectangular
-    float* d_sky = nullptr;
-    uint32_t sky_w = 0, sky_h = 0;
+    struct Sky {
+        Owned<float> px;
+        uint32_t w = 0, h = 0;
+    } sky;
     float sky_hdr = 1.0f;
     // reference arithmetic (vpx_set_arithmetic): the host's captured rcpss / rsqrtss tables
-    uint32_t* d_x86 = nullptr;
+    Owned<uint32_t> d_x86;
     X86Arith x86{nullptr, 0u, 0u, 0u, 0u};
-    unsigned long long* d_ctr = nullptr;  // striped work counters (vpx_wavefront.hpp flush_counters)
+    Owned<unsigned long long> d_ctr;  // striped work counters (vpx_wavefront.hpp flush_counters)
     // per-stage profile: event pairs around stage launches while enabled
     std::vector<hipEvent_t> prof_ev;
     std::vector<int> prof_stage;
     uint32_t prof_cap = 0, prof_used = 0;
     uint32_t prof_mask = 0xffffffffu;  // stages timed (vpx_profile_select)
-    unsigned long long* d_sum = nullptr;
-    void* d_scratch = nullptr;
-    size_t scratch_bytes = 0;
+    Owned<unsigned long long> d_sum;
+    Owned<void> d_scratch;  // the host-memory entries' staging (run_batch); every user ends in sync_all
     hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr;
     // wavefront path state (vpx_wavefront.hpp), grown on demand: one store per stream that
     // renders (the caller's stream, and each pipeline lane)
     struct WaveStore {
-        void* d = nullptr;
-        size_t bytes = 0;
+        Owned<void> d;
         WaveBufs w{};
         // the level fork (launch_render): a second stream for the bounce walks, forked after a
         // level's shade and joined before the next one's, so that they overlap the shadow walks
@@ -1638,9 +1731,8 @@ struct vpx_ctx {
     struct Lane {
         hipStream_t s = nullptr;
         WaveStore ws;
-        float4* packed = nullptr;  // the lane's frame: one float4 sample per path (tile order)
-        float4* packed2 = nullptr; // its second buffer (frames alternate: VPX_LANE_DOUBLE)
-        size_t packed_len = 0;
+        Owned<float4> packed;   // the lane's frame: one float4 sample per path (tile order)
+        Owned<float4> packed2;  // its second buffer (frames alternate: VPX_LANE_DOUBLE)
         hipEvent_t rendered = nullptr, consumed = nullptr, consumed2 = nullptr;
         bool used2 = false;
         uint32_t flip = 0;
@@ -1653,39 +1745,36 @@ struct vpx_ctx {
     std::vector<Lane> lanes;
     uint32_t lane_next = 0;
     // static-camera path images (float4[W*H] each): albedo, illumination, ray data, temp
-    float4* rp_buf = nullptr;
-    size_t rp_pixels = 0;
+    Owned<float4> rp_buf;
     // a window chain's samples when no lanes run (vpx_render_window)
-    float4* win_buf = nullptr;
-    size_t win_len = 0;
+    Owned<float4> win_buf;
     // vpx_denoise_ids' scratch: the keys (uint2 per pixel), then two float4 images when a call
     // ran more than one pass; carved per call for the call's size
-    void* dn_buf = nullptr;
-    size_t dn_bytes = 0;
+    Owned<void> dn_buf;
     // vpx_reproject_ids' scratch: the volume table (24 floats per volume, then a moved flag per
     // volume) and, in the VPX_REPROJECT_PREKEY form, the previous keys; rj_host: the table's pinned
     // staging copy, rewritten only after rj_ev (its last upload) has passed; rj_last: the table the
     // device holds, so that an unchanged one is not uploaded again
-    void* rj_buf = nullptr;
-    size_t rj_bytes = 0;
-    void* rj_host = nullptr;
-    size_t rj_host_bytes = 0;
+    Owned<void> rj_buf;
+    Pinned<void> rj_host;
     hipEvent_t rj_ev = nullptr;
     std::vector<uint32_t> rj_last;
     // vpx_cast_*: the pool form's grab block (kGrabBlock words, zeroed on the stream per call; comes
     // with the first call), and what the last call launched (vpx_debug_last_cast_kernel)
-    uint32_t* cast_grab = nullptr;
+    Owned<uint32_t> cast_grab;
     int last_cast = 0;
     // device set (vpx_create_multi): one member context per device; this context only
     // forwards (VPX_GROUP_*) and runs the tile-sharded vpx_render (group_render)
-    std::vector<vpx_ctx*> members;
-    std::vector<ncclComm_t> comms;      // RCCL, one per member (distinct devices only)
-    std::vector<void*> g_packed;        // per member: packed float4 samples / RGB8 (member device)
-    std::vector<float*> g_accum;        // per member: packed accumulator (accum == NULL mode)
-    void* g_gathered = nullptr;         // member 0's device: the members' packed buffers back to back
-    size_t g_len = 0;                   // float4 elements per member buffer the above were sized for
-    std::vector<hipEvent_t> g_ev;       // per member: its render done (copy path)
-    hipEvent_t g_copied = nullptr;      // member 0: gather copies done (copy path)
+    struct Member {
+        vpx_ctx* ctx = nullptr;
+        Owned<void> packed;       // packed float4 samples / RGB8 (member device)
+        Owned<float> accum;       // packed accumulator (accum == NULL mode)
+        hipEvent_t ev = nullptr;  // its render done (copy path)
+    };
+    std::vector<Member> members;
+    std::vector<ncclComm_t> comms;  // RCCL, one per member (distinct devices only)
+    Owned<void> g_gathered;         // member 0's device: the members' packed buffers back to back
+    hipEvent_t g_copied = nullptr;  // member 0: gather copies done (copy path)
     // display interop (vpx_gl_*): a registered GL pixel-unpack buffer on this context's
     // device (device set: devices[0]); mapped between vpx_gl_map and vpx_gl_unmap
     hipGraphicsResource_t gl_res = nullptr;
@@ -1728,7 +1817,8 @@ struct DeviceGuard {
 template <class F>
 int group_all(vpx_ctx* c, F f) {
     DeviceGuard keep;
-    for (vpx_ctx* m : c->members) {
+    for (const auto& mem : c->members) {
+        vpx_ctx* m = mem.ctx;
         if (hipSetDevice(m->device) != hipSuccess) return fail(c, VPX_E_DEVICE, "hipSetDevice");
         const int rc = f(m);
         if (rc) return fail(c, rc, "device " + std::to_string(m->device) + ": " + m->err);
@@ -1738,7 +1828,7 @@ int group_all(vpx_ctx* c, F f) {
 template <class F>
 int group_first(vpx_ctx* c, F f) {
     DeviceGuard keep;
-    vpx_ctx* m = c->members[0];
+    vpx_ctx* m = c->members[0].ctx;
     if (hipSetDevice(m->device) != hipSuccess) return fail(c, VPX_E_DEVICE, "hipSetDevice");
     const int rc = f(m);
     return rc ? fail(c, rc, m->err) : VPX_OK;
@@ -1748,36 +1838,63 @@ int group_first(vpx_ctx* c, F f) {
 #define VPX_GROUP_FIRST(c, call) \
     if ((c) && !(c)->members.empty()) return group_first((c), [&](vpx_ctx* m_) { return call; })
 
-#define VPX_HIP(c, expr)                                                                            \
-    do {                                                                                            \
-        hipError_t e_ = (expr);                                                                     \
-        if (e_ != hipSuccess)                                                                       \
-            return fail((c), e_ == hipErrorOutOfMemory ? VPX_E_NOMEM : VPX_E_DEVICE,                \
-                        std::string(#expr) + ": " + hipGetErrorString(e_));                         \
-    } while (0)
-
+// A table replaced: the old one goes first and the count with it, so a failure leaves the table
+// empty with count 0 (the caller has waited for the frames that read it).
 template <typename T>
-int upload_table(vpx_ctx* c, T*& dst, const T* src, uint32_t n) {
-    if (dst) {
-        (void)hipFree(dst);
-        dst = nullptr;
-    }
+int upload_table(vpx_ctx* c, Table<T>& t, const T* src, uint32_t n) {
+    t.buf.release();
+    t.n = 0;
     if (n == 0) return VPX_OK;
     if (!src) return fail(c, VPX_E_INVALID, "null table with non-zero count");
-    VPX_HIP(c, hipMalloc(&dst, sizeof(T) * n));
-    VPX_HIP(c, hipMemcpyAsync(dst, src, sizeof(T) * n, hipMemcpyHostToDevice, c->stream));
+    VPX_HIP(c, t.buf.alloc(sizeof(T) * n));
+    VPX_HIP(c, hipMemcpyAsync(t.buf, src, sizeof(T) * n, hipMemcpyHostToDevice, c->stream));
+    t.n = n;
     return VPX_OK;
 }
 
-int ensure_scratch(vpx_ctx* c, size_t bytes) {
-    if (bytes <= c->scratch_bytes) return VPX_OK;
-    if (c->d_scratch) (void)hipFree(c->d_scratch);
-    c->d_scratch = nullptr;
-    c->scratch_bytes = 0;
-    VPX_HIP(c, hipMalloc(&c->d_scratch, bytes));
-    c->scratch_bytes = bytes;
+// No wait before the old scratch goes: every user of d_scratch ends in sync_all, so nothing
+// queued still reads it.
+int ensure_scratch(vpx_ctx* c, size_t bytes) { return c->d_scratch.grow(c, bytes, false); }
+
+// The entries that take and return host memory: the inputs are uploaded into the scratch, `run`
+// launches on c->stream with the device pointers (din[i], dout[j], in the order given), the
+// outputs come back, and the call ends synchronised.  An output with a null host pointer still
+// gets its device buffer; it is only not fetched.
+struct HostIn {
+    const void* host;
+    size_t bytes;
+};
+struct HostOut {
+    void* host;
+    size_t bytes;
+};
+template <typename Run>
+int run_batch(vpx_ctx* c, std::initializer_list<HostIn> in, std::initializer_list<HostOut> out, Run run) {
+    constexpr size_t kMost = 4;
+    void *din[kMost] = {}, *dout[kMost] = {};
+    if (in.size() > kMost || out.size() > kMost) return fail(c, VPX_E_INVALID, "run_batch: too many buffers");
+    auto carve = [&](Carve cv) {
+        size_t i = 0, o = 0;
+        for (const HostIn& b : in) din[i++] = cv.take(b.bytes);
+        for (const HostOut& b : out) dout[o++] = cv.take(b.bytes);
+        return cv.used();
+    };
+    if (int rc = ensure_scratch(c, carve(Carve(nullptr)))) return rc;
+    carve(Carve(c->d_scratch));
+    size_t i = 0, o = 0;
+    for (const HostIn& b : in) VPX_HIP(c, hipMemcpyAsync(din[i++], b.host, b.bytes, hipMemcpyHostToDevice, c->stream));
+    run(din, dout);
+    VPX_HIP(c, hipGetLastError());
+    for (const HostOut& b : out) {
+        if (b.host) VPX_HIP(c, hipMemcpyAsync(b.host, dout[o], b.bytes, hipMemcpyDeviceToHost, c->stream));
+        ++o;
+    }
+    VPX_HIP(c, sync_all(c));
     return VPX_OK;
 }
+
+// the constant sky of the query entries (misses report it; vpx_focus_distance has its own)
+constexpr float kQuerySky[3] = {0.392f, 0.584f, 0.829f};
 
 int check_ready(vpx_ctx* c) {
     if (c->volumes.empty()) return fail(c, VPX_E_STATE, "no volumes set (vpx_set_volumes)");
@@ -1791,12 +1908,8 @@ int check_ready(vpx_ctx* c) {
 
 int sync_grids(vpx_ctx* c) {
     const uint32_t n = (uint32_t)c->grids.size();
-    if (n > c->d_grids_cap) {
-        if (c->d_grids) (void)hipFree(c->d_grids);
-        c->d_grids = nullptr;
-        VPX_HIP(c, hipMalloc(&c->d_grids, sizeof(DevGrid) * n));
-        c->d_grids_cap = n;
-    }
+    // no wait of its own: its callers (alloc_grid's) have waited for the frames in flight
+    if (int rc = c->d_grids.grow(c, sizeof(DevGrid) * n, false)) return rc;
     std::vector<DevGrid> h(n);
     for (uint32_t i = 0; i < n; ++i) {
         const auto& g = c->grids[i];
@@ -1811,29 +1924,29 @@ SceneView view_of(const vpx_ctx* c, const float sky[3], int32_t area_samples, bo
     sv.grids = c->d_grids;
     sv.volumes = c->d_volumes;
     sv.vbounds = c->d_vbounds;
-    sv.tlas = (const TlasNode*)c->d_tlas;
+    sv.tlas = c->d_tlas;
     sv.tlas_on = c->tlas_on ? 1u : 0u;
     sv.tlas_nodes = c->tlas_nodes;
     sv.tlas_always = c->tlas_always;
     sv.materials = c->d_materials;
-    sv.points = c->d_points;
-    sv.spots = c->d_spots;
-    sv.areas = c->d_areas;
-    sv.spheres = c->d_spheres;
-    sv.triangles = c->d_triangles;
+    sv.points = c->points.buf;
+    sv.spots = c->spots.buf;
+    sv.areas = c->areas.buf;
+    sv.spheres = c->spheres.buf;
+    sv.triangles = c->triangles.buf;
     sv.num_volumes = (uint32_t)c->volumes.size();
-    sv.num_points = c->n_points;
-    sv.num_spots = c->n_spots;
-    sv.num_areas = c->n_areas;
-    sv.num_spheres = c->n_spheres;
-    sv.num_triangles = c->n_triangles;
+    sv.num_points = c->points.n;
+    sv.num_spots = c->spots.n;
+    sv.num_areas = c->areas.n;
+    sv.num_spheres = c->spheres.n;
+    sv.num_triangles = c->triangles.n;
     sv.dir = c->dir;
     sv.sky[0] = sky[0], sv.sky[1] = sky[1], sv.sky[2] = sky[2];
     sv.area_samples = area_samples;
-    sv.sky_px = c->d_sky;
-    sv.sky_w = c->sky_w, sv.sky_h = c->sky_h;
+    sv.sky_px = c->sky.px;
+    sv.sky_w = c->sky.w, sv.sky_h = c->sky.h;
     sv.sky_hdr = c->sky_hdr;
-    sv.sky_tex = (sky_tex && c->d_sky) ? 1u : 0u;
+    sv.sky_tex = (sky_tex && c->sky.px) ? 1u : 0u;
     sv.x86 = c->x86;
     // one grid for every volume after the world: lane_volumes (vpx_trace.hpp)
     sv.inst_grid = -1;
@@ -1878,57 +1991,48 @@ int validate_frame(vpx_ctx* c, const vpx_frame_params* p) {
         return fail(c, VPX_E_INVALID, "max_bounces must be in [-1, 14]");
     if (p->area_samples < 0 || p->area_samples > 15) return fail(c, VPX_E_INVALID, "area_samples must be in [0, 15]");
     if (!c->have_camera) return fail(c, VPX_E_STATE, "no camera set (vpx_set_camera)");
-    if ((p->flags & VPX_FLAG_SKY) && !c->d_sky)
+    if ((p->flags & VPX_FLAG_SKY) && !c->sky.px)
         return fail(c, VPX_E_STATE, "VPX_FLAG_SKY without a sky texture (vpx_set_sky)");
     return check_ready(c);
 }
 
-// Carve the wavefront buffers for P paths, L levels and S shadow slots out of one
-// device allocation (grown on demand; never inside a capture).
-int ensure_wave(vpx_ctx* c, vpx_ctx::WaveStore& ws, uint32_t P, uint32_t L, uint32_t S) {
+// The wavefront buffers for P paths, L levels and S shadow slots, taken in this order from one
+// allocation: the same sequence sizes it (on a null base) and divides it.
+void carve_wave(Carve& cv, WaveBufs& w, uint32_t P, uint32_t L, uint32_t S) {
     const size_t f4 = sizeof(float4);
-    const size_t bytes = (size_t)P * (f4 * (5 + 2 * (size_t)L + 3 * (size_t)S + 1) + 3 * sizeof(uint32_t)) +
-                         sizeof(uint32_t) * (size_t)P * 3 + (size_t)P / 8 + sizeof(uint32_t) * kPoolWords +
-                         (size_t)P * S + sizeof(uint32_t) * (size_t)P * S + 22 * 256;
-    if (bytes > ws.bytes) {
-        if (ws.d) {
-            VPX_HIP(c, sync_all(c));
-            (void)hipFree(ws.d);
-        }
-        ws.d = nullptr;
-        ws.bytes = 0;
-        VPX_HIP(c, hipMalloc(&ws.d, bytes));
-        ws.bytes = bytes;
-    }
-    char* q = (char*)ws.d;
-    auto take = [&](size_t n) {
-        char* r = q;
-        q += (n + 255) & ~(size_t)255;
-        return (void*)r;
-    };
-    WaveBufs& w = ws.w;
     w.P = P;
     w.S = S;
-    w.O = (float4*)take(f4 * P);
-    w.D = (float4*)take(f4 * P);
-    w.H = (float4*)take(f4 * P);
-    w.leaf = (float4*)take(f4 * P);
-    w.SM = (float4*)take(f4 * P);
-    w.LA = (float4*)take(f4 * P * (size_t)L);
-    w.LB = (float4*)take(f4 * P * (size_t)L);
-    w.SO = (float4*)take(f4 * P * (size_t)S);
-    w.SD = (float4*)take(f4 * P * (size_t)S);
-    w.SL = (float4*)take(f4 * P * (size_t)S);
-    w.HM = (uint32_t*)take(4 * (size_t)P);
-    w.depth = (int32_t*)take(4 * (size_t)P);
-    w.forms = (uint32_t*)take(4 * (size_t)P);
-    w.smask = (uint32_t*)take(4 * (size_t)P);
-    w.live0 = (uint32_t*)take(4 * (size_t)P);
-    w.live1 = (uint32_t*)take(4 * (size_t)P);
-    w.amask = (uint64_t*)take((size_t)P / 8);  // P is a multiple of 256
-    w.pool = (uint32_t*)take(sizeof(uint32_t) * kPoolWords);
-    w.occb = (uint8_t*)take((size_t)P * S);
-    (void)take(sizeof(uint32_t) * (size_t)P * S);  // slot_list (vpx_wavefront.hpp), right after occb
+    w.O = cv.take<float4>(f4 * P);
+    w.D = cv.take<float4>(f4 * P);
+    w.H = cv.take<float4>(f4 * P);
+    w.leaf = cv.take<float4>(f4 * P);
+    w.SM = cv.take<float4>(f4 * P);
+    w.LA = cv.take<float4>(f4 * P * (size_t)L);
+    w.LB = cv.take<float4>(f4 * P * (size_t)L);
+    w.SO = cv.take<float4>(f4 * P * (size_t)S);
+    w.SD = cv.take<float4>(f4 * P * (size_t)S);
+    w.SL = cv.take<float4>(f4 * P * (size_t)S);
+    w.HM = cv.take<uint32_t>(4 * (size_t)P);
+    w.depth = cv.take<int32_t>(4 * (size_t)P);
+    w.forms = cv.take<uint32_t>(4 * (size_t)P);
+    w.smask = cv.take<uint32_t>(4 * (size_t)P);
+    w.live0 = cv.take<uint32_t>(4 * (size_t)P);
+    w.live1 = cv.take<uint32_t>(4 * (size_t)P);
+    w.amask = cv.take<uint64_t>((size_t)P / 8);  // P is a multiple of 256
+    w.pool = cv.take<uint32_t>(sizeof(uint32_t) * kPoolWords);
+    w.occb = cv.take<uint8_t>((size_t)P * S);
+    (void)cv.take(sizeof(uint32_t) * (size_t)P * S);  // slot_list (vpx_wavefront.hpp), right after occb
+}
+
+// Grown on demand, never inside a capture; a store that is replaced waits for the frames in
+// flight, which still walk in the old one.
+int ensure_wave(vpx_ctx* c, vpx_ctx::WaveStore& ws, uint32_t P, uint32_t L, uint32_t S) {
+    Carve size(nullptr);
+    WaveBufs sized{};
+    carve_wave(size, sized, P, L, S);
+    if (int rc = ws.d.grow(c, size.used(), true)) return rc;
+    Carve cv(ws.d);
+    carve_wave(cv, ws.w, P, L, S);
     return VPX_OK;
 }
 
@@ -2271,17 +2375,11 @@ int lane_render(vpx_ctx* c, const SceneView& sv, const FrameArgs& f, uint32_t ti
     L.flip = VPX_LANE_DOUBLE ? L.flip ^ 1u : 0u;
     if (!dst) {
         const size_t need = (size_t)tiles * kTilePix;
-        if (L.packed_len < need) {
-            VPX_HIP(c, sync_all(c));
-            if (L.packed) (void)hipFree(L.packed);
-            if (L.packed2) (void)hipFree(L.packed2);
-            L.packed = L.packed2 = nullptr;
-            L.packed_len = 0;
-            VPX_HIP(c, hipMalloc(&L.packed, sizeof(float4) * need));
-            if (VPX_LANE_DOUBLE) VPX_HIP(c, hipMalloc(&L.packed2, sizeof(float4) * need));
-            L.packed_len = need;
-        }
-        dst = b ? L.packed2 : L.packed;
+        // blends queued on the caller's stream still read the old samples: wait
+        if (int rc = L.packed.grow(c, sizeof(float4) * need, true)) return rc;
+        if (VPX_LANE_DOUBLE)
+            if (int rc = L.packed2.grow(c, sizeof(float4) * need, true)) return rc;
+        dst = b ? L.packed2.get() : L.packed.get();
     }
     bool& used = b ? L.used2 : L.used;
     L.cur = dst;
@@ -2307,16 +2405,13 @@ void free_lanes(vpx_ctx* c) {
         if (L.dedicated) g_lane_queues.fetch_sub(1);
         if (L.s) (void)hipStreamSynchronize(L.s);
         free_fork(L.ws);
-        if (L.ws.d) (void)hipFree(L.ws.d);
-        if (L.packed) (void)hipFree(L.packed);
-        if (L.packed2) (void)hipFree(L.packed2);
         if (L.rendered) (void)hipEventDestroy(L.rendered);
         if (L.consumed) (void)hipEventDestroy(L.consumed);
         if (L.consumed2) (void)hipEventDestroy(L.consumed2);
         if (L.caller) (void)hipEventDestroy(L.caller);
         if (L.s) (void)hipStreamDestroy(L.s);
     }
-    c->lanes.clear();
+    c->lanes.clear();  // the lanes' buffers go with them
     c->lane_next = 0;
 }
 
@@ -2360,8 +2455,8 @@ int vpx_create(int device, vpx_ctx** out) {
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0)
         c->cus = (uint32_t)cus;
     if (hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking) != hipSuccess ||
-        hipMalloc(&c->d_ctr, kCtrWords * kCtrStripes * sizeof(unsigned long long)) != hipSuccess ||
-        hipMalloc(&c->d_sum, sizeof(unsigned long long)) != hipSuccess ||
+        c->d_ctr.alloc(kCtrWords * kCtrStripes * sizeof(unsigned long long)) != hipSuccess ||
+        c->d_sum.alloc(sizeof(unsigned long long)) != hipSuccess ||
         hipEventCreate(&c->ev0) != hipSuccess || hipEventCreate(&c->ev1) != hipSuccess ||
         hipEventCreate(&c->ev2) != hipSuccess) {
         vpx_destroy(c);
@@ -2376,29 +2471,29 @@ int vpx_create(int device, vpx_ctx** out) {
 int vpx_destroy(vpx_ctx* c) {
     if (!c) return VPX_E_INVALID;
     if (c->gl_res) {  // a context destroyed while its GL buffer is mapped: unmap, then unregister
-        vpx_ctx* h = c->members.empty() ? c : c->members[0];
+        vpx_ctx* h = c->members.empty() ? c : c->members[0].ctx;
         (void)hipSetDevice(h->device);
         if (c->gl_mapped) (void)hipGraphicsUnmapResources(1, &c->gl_res, h->stream);
         (void)hipGraphicsUnregisterResource(c->gl_res);
         c->gl_res = nullptr;
         c->gl_mapped = false;
     }
-    if (!c->members.empty()) {  // device set: its buffers, communicators and members
+    // Only what depends on an order is released by hand; every buffer is an Owned and goes with
+    // its holder, on the device that is current then.
+    if (!c->members.empty()) {  // device set: its events, communicators and members
         DeviceGuard keep;
-        for (size_t r = 0; r < c->members.size(); ++r) {
-            vpx_ctx* m = c->members[r];
-            (void)hipSetDevice(m->device);
-            (void)hipStreamSynchronize(m->stream);
-            if (r < c->g_packed.size() && c->g_packed[r]) (void)hipFree(c->g_packed[r]);
-            if (r < c->g_accum.size() && c->g_accum[r]) (void)hipFree(c->g_accum[r]);
-            if (r < c->g_ev.size() && c->g_ev[r]) (void)hipEventDestroy(c->g_ev[r]);
-            if (r == 0) {
-                if (c->g_gathered) (void)hipFree(c->g_gathered);
-                if (c->g_copied) (void)hipEventDestroy(c->g_copied);
-            }
+        for (auto& slot : c->members) {
+            const vpx_ctx::Member mem = std::move(slot);  // its buffers go with `mem`, on its device
+            (void)hipSetDevice(mem.ctx->device);
+            (void)hipStreamSynchronize(mem.ctx->stream);
+            if (mem.ev) (void)hipEventDestroy(mem.ev);
         }
+        const int first = c->members[0].ctx->device;  // where the gathered buffer lives
+        (void)hipSetDevice(first);
+        if (c->g_copied) (void)hipEventDestroy(c->g_copied);
         for (ncclComm_t cm : c->comms) (void)ncclCommDestroy(cm);
-        for (vpx_ctx* m : c->members) vpx_destroy(m);
+        for (const auto& slot : c->members) vpx_destroy(slot.ctx);
+        (void)hipSetDevice(first);
         delete c;
         return VPX_OK;
     }
@@ -2406,32 +2501,8 @@ int vpx_destroy(vpx_ctx* c) {
     if (c->stream) (void)sync_all(c);
     free_lanes(c);
     free_fork(c->wave);
-    for (auto& g : c->grids) {
-        if (g.ptr) (void)hipFree(g.ptr);
-        if (g.l1) (void)hipFree(g.l1);
-        if (g.l2) (void)hipFree(g.l2);
-        if (g.dfp) (void)hipFree(g.dfp);
-    }
-    for (auto& m : c->models) {
-        if (m.vox) (void)hipFree(m.vox);
-        if (m.mat) (void)hipFree(m.mat);
-    }
-    if (c->d_model_aux) (void)hipFree(c->d_model_aux);
-    if (c->h_plan) (void)hipHostFree(c->h_plan);
-    if (c->d_refresh) (void)hipFree(c->d_refresh);
-    if (c->h_refresh) (void)hipHostFree(c->h_refresh);
-    void* ptrs[] = {c->d_grids, c->d_volumes, c->d_vbounds, c->d_tlas, c->d_bvh, c->d_materials, c->d_points, c->d_spots, c->d_areas,
-                    c->d_spheres, c->d_triangles, c->d_ctr, c->d_sum, c->d_scratch, c->wave.d, c->d_sky, c->d_x86};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
     for (hipEvent_t e : c->prof_ev) (void)hipEventDestroy(e);
-    if (c->rp_buf) (void)hipFree(c->rp_buf);
-    if (c->win_buf) (void)hipFree(c->win_buf);
-    if (c->dn_buf) (void)hipFree(c->dn_buf);
-    if (c->rj_buf) (void)hipFree(c->rj_buf);
-    if (c->rj_host) (void)hipHostFree(c->rj_host);
     if (c->rj_ev) (void)hipEventDestroy(c->rj_ev);
-    if (c->cast_grab) (void)hipFree(c->cast_grab);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     if (c->ev2) (void)hipEventDestroy(c->ev2);
@@ -2444,7 +2515,7 @@ const char* vpx_last_error(const vpx_ctx* c) { return c ? c->err.c_str() : "null
 
 int vpx_set_stream(vpx_ctx* c, void* s) {
     if (!c) return VPX_E_INVALID;
-    if (!c->members.empty()) return vpx_set_stream(c->members[0], s);  // a stream of the first device
+    if (!c->members.empty()) return vpx_set_stream(c->members[0].ctx, s);  // a stream of the first device
     VPX_HIP(c, sync_all(c));
     // (the context's own stream is kept while unused: releasing it measured slower with
     // pipeline lanes — C2 3.75 vs 2.97 ms at 3 lanes — the lanes' hardware-queue sharing
@@ -2499,7 +2570,7 @@ int vpx_set_pipeline(vpx_ctx* c, uint32_t depth) {
 // the RGB8 pack writes into a GL pixel-unpack buffer the host registered once, and the host
 // updates its texture from that buffer (glTexSubImage2D with the PBO bound) — the frame stays
 // on the GPU.  A device set registers and maps on devices[0], where vpx_render composites.
-static vpx_ctx* gl_home(vpx_ctx* c) { return c->members.empty() ? c : c->members[0]; }
+static vpx_ctx* gl_home(vpx_ctx* c) { return c->members.empty() ? c : c->members[0].ctx; }
 
 int vpx_gl_register_buffer(vpx_ctx* c, unsigned int gl_buffer) {
     if (!c) return VPX_E_INVALID;
@@ -2565,23 +2636,19 @@ static int alloc_grid(vpx_ctx* c, uint32_t id, uint32_t n) {
     if (id >= c->grids.size()) c->grids.resize(id + 1);
     auto& g = c->grids[id];
     const size_t bytes = (size_t)n * n * n;
-    if (g.ptr && g.n != n) {
-        VPX_HIP(c, sync_all(c));
-        (void)hipFree(g.ptr);
-        (void)hipFree(g.l1);
-        (void)hipFree(g.l2);
-        (void)hipFree(g.dfp);
-        g.ptr = nullptr, g.l1 = nullptr, g.l2 = nullptr, g.dfp = nullptr;
-    }
-    g.n = n;
-    g.nb1 = (n + 3) / 4;
-    g.nb2 = (g.nb1 + 3) / 4;
-    g.nb3 = (g.nb2 + 3) / 4;
-    if (!g.ptr) {
-        VPX_HIP(c, hipMalloc(&g.ptr, bytes));
-        VPX_HIP(c, hipMalloc(&g.l1, sizeof(uint64_t) * (size_t)g.nb2 * g.nb2 * g.nb2 * 64));
-        VPX_HIP(c, hipMalloc(&g.l2, sizeof(uint64_t) * (size_t)g.nb3 * g.nb3 * g.nb3 * 64));
-        VPX_HIP(c, hipMalloc(&g.dfp, (8 + 4 * 24) * g.plane()));  // 8 octant planes of bytes, 24 axis planes of 32-bit words
+    if (!g.ptr || g.n != n) {  // a grid of another size is a new grid; a failure leaves none
+        if (g.ptr) VPX_HIP(c, sync_all(c));
+        vpx_ctx::GridBuf fresh;
+        fresh.n = n;
+        fresh.nb1 = (n + 3) / 4;
+        fresh.nb2 = (fresh.nb1 + 3) / 4;
+        fresh.nb3 = (fresh.nb2 + 3) / 4;
+        g = vpx_ctx::GridBuf{};
+        VPX_HIP(c, fresh.ptr.alloc(bytes));
+        VPX_HIP(c, fresh.l1.alloc(sizeof(uint64_t) * (size_t)fresh.nb2 * fresh.nb2 * fresh.nb2 * 64));
+        VPX_HIP(c, fresh.l2.alloc(sizeof(uint64_t) * (size_t)fresh.nb3 * fresh.nb3 * fresh.nb3 * 64));
+        VPX_HIP(c, fresh.dfp.alloc((8 + 4 * 24) * fresh.plane()));  // 8 octant planes of bytes, 24 axis planes of 32-bit words
+        g = std::move(fresh);
     }
     return sync_grids(c);
 }
@@ -2593,7 +2660,7 @@ static int build_df(vpx_ctx* c, const vpx_ctx::GridBuf& g) {
     const uint64_t threads = (uint64_t)g.nb1 * g.nb1 * 8;
     const unsigned blocks = (unsigned)((threads + 255) / 256);
     for (uint32_t s = 3 * (g.nb1 - 1) + 1; s-- > 0;) {
-        hipLaunchKernelGGL(df_plane_k, dim3(blocks), dim3(256), 0, c->stream, (uint8_t*)g.l1, g.l2, g.nb1, g.nb2, g.nb3, s);
+        hipLaunchKernelGGL(df_plane_k, dim3(blocks), dim3(256), 0, c->stream, g.l1.as<uint8_t>(), g.l2, g.nb1, g.nb2, g.nb3, s);
         VPX_HIP(c, hipGetLastError());
     }
     hipLaunchKernelGGL(build_planes_k, dim3(2048), dim3(256), 0, c->stream, g.l1, g.l2, g.nb2, g.nb3, g.dfp);
@@ -2620,8 +2687,8 @@ static int build_masks(vpx_ctx* c, uint32_t id) {
 // The refresh's record, reset on the stream; before the first launch that counts into it.
 static int refresh_begin(vpx_ctx* c) {
     if (!c->d_refresh) {
-        VPX_HIP(c, hipHostMalloc((void**)&c->h_refresh, 2 * sizeof(RefreshDev)));
-        VPX_HIP(c, hipMalloc(&c->d_refresh, sizeof(RefreshDev)));
+        VPX_HIP(c, c->h_refresh.alloc(2 * sizeof(RefreshDev)));
+        VPX_HIP(c, c->d_refresh.alloc(sizeof(RefreshDev)));
         RefreshDev& init = c->h_refresh[0];
         std::memset(&init, 0, sizeof(init));
         init.E = skip::box_none();
@@ -2669,7 +2736,7 @@ static int refresh_levels(vpx_ctx* c, const vpx_ctx::GridBuf& g, const skip::Box
         cand.b[o] = skip::box_behind(E, o, reach, g.nb1);
         most = std::max(most, volume(cand.b[o]));
     }
-    hipLaunchKernelGGL(df_mark_k, dim3(blocks(most, 2048), 8), dim3(256), 0, c->stream, (const uint8_t*)g.dfp, plane, g.nb2, cand, E, rd);
+    hipLaunchKernelGGL(df_mark_k, dim3(blocks(most, 2048), 8), dim3(256), 0, c->stream, g.dfp, plane, g.nb2, cand, E, rd);
     VPX_HIP(c, hipGetLastError());
     VPX_HIP(c, hipMemcpyAsync(back.C, (const uint8_t*)rd + offsetof(RefreshDev, C), sizeof(back.C), hipMemcpyDeviceToHost, c->stream));
     VPX_HIP(c, hipStreamSynchronize(c->stream));
@@ -2693,13 +2760,13 @@ static int refresh_levels(vpx_ctx* c, const vpx_ctx::GridBuf& g, const skip::Box
         }
     }
     for (uint32_t s = 0; s < diagonals; ++s) {
-        hipLaunchKernelGGL(df_diag_k, dim3(blocks(face, ~0ull), 8), dim3(256), 0, c->stream, (uint8_t*)g.l1, g.l2, g.nb1, g.nb2, g.nb3, C, s);
+        hipLaunchKernelGGL(df_diag_k, dim3(blocks(face, ~0ull), 8), dim3(256), 0, c->stream, g.l1.as<uint8_t>(), g.l2, g.nb1, g.nb2, g.nb3, C, s);
         VPX_HIP(c, hipGetLastError());
     }
-    hipLaunchKernelGGL(df_planes_box_k, dim3(blocks(most_c, 2048), 8), dim3(256), 0, c->stream, (const uint8_t*)g.l1, g.l2, g.nb2, g.nb3,
+    hipLaunchKernelGGL(df_planes_box_k, dim3(blocks(most_c, 2048), 8), dim3(256), 0, c->stream, g.l1.as<const uint8_t>(), g.l2, g.nb2, g.nb3,
                        g.dfp, plane, C);
     VPX_HIP(c, hipGetLastError());
-    hipLaunchKernelGGL(axis_box_k, dim3(blocks(most_a, 1024), 24), dim3(256), 0, c->stream, (const uint8_t*)g.dfp, g.nb1, g.nb2, dfw, C, rd);
+    hipLaunchKernelGGL(axis_box_k, dim3(blocks(most_a, 1024), 24), dim3(256), 0, c->stream, g.dfp, g.nb1, g.nb2, dfw, C, rd);
     VPX_HIP(c, hipGetLastError());
     hipLaunchKernelGGL(wide_box_k, dim3(blocks(most_w / 8, 4096), 24), dim3(256), 0, c->stream, (uint16_t*)dfw, g.nb1, g.nb2,
                        (const RefreshDev*)rd);
@@ -2765,17 +2832,15 @@ int vpx_grid_write_box(vpx_ctx* c, uint32_t id, const uint8_t* src, uint32_t x0,
         return fail(c, VPX_E_INVALID, "box outside the grid");
     const size_t bytes = (size_t)dx * dy * dz;
     if (!bytes) return VPX_OK;
-    uint8_t* d = nullptr;
+    Owned<uint8_t> d;  // the box on the device, for this call
     VPX_HIP(c, sync_all(c));  // frames in flight still read the grid
-    VPX_HIP(c, hipMalloc(&d, bytes));
-    if (hipMemcpyAsync(d, src, bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess) {
-        (void)hipFree(d);
+    VPX_HIP(c, d.alloc(bytes));
+    if (hipMemcpyAsync(d, src, bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess)
         return fail(c, VPX_E_DEVICE, "box upload failed");
-    }
     hipLaunchKernelGGL(write_box_k, dim3((unsigned)std::min<size_t>(4096, (bytes + 255) / 256)), dim3(256), 0, c->stream,
                        g.ptr, g.n, d, x0, y0, z0, dx, dy, dz);
     const hipError_t e = sync_all(c);
-    (void)hipFree(d);
+    d.release();
     if (e != hipSuccess) return fail(c, VPX_E_DEVICE, hipGetErrorString(e));
     return build_masks_box(c, id, x0, y0, z0, x0 + dx, y0 + dy, z0 + dz);
 }
@@ -2818,14 +2883,14 @@ int vpx_generate_tiled_grid(vpx_ctx* c, uint32_t id, uint32_t n, const uint8_t* 
     int rc = alloc_grid(c, id, n);
     if (rc) return rc;
     const size_t mbytes = (size_t)mx * my * mz;
-    uint8_t* dm = nullptr;
-    VPX_HIP(c, hipMalloc(&dm, mbytes));
+    Owned<uint8_t> dm;  // the model on the device, for this call
+    VPX_HIP(c, dm.alloc(mbytes));
     VPX_HIP(c, hipMemcpy(dm, model, mbytes, hipMemcpyHostToDevice));
     hipLaunchKernelGGL(tiled_world_k, dim3(4096), dim3(256), 0, c->stream, c->grids[id].ptr, n, dm, mx, my, mz, px,
                        py, pz, ground);
     VPX_HIP(c, hipGetLastError());
     VPX_HIP(c, sync_all(c));
-    (void)hipFree(dm);
+    dm.release();
     return build_masks(c, id);
 }
 
@@ -2836,15 +2901,12 @@ static int ensure_model_aux(vpx_ctx* c) {
     if (c->d_model_aux) return VPX_OK;
     std::vector<uint32_t> t(32 * model::kJumpDevice);
     model::xs32_build_tables(t.data(), model::kJumpDevice);
-    if (!c->h_plan) VPX_HIP(c, hipHostMalloc((void**)&c->h_plan, model::plan_bytes(4096)));
-    uint8_t* aux = nullptr;
-    VPX_HIP(c, hipMalloc(&aux, kJumpBytes + model::plan_bytes(4096)));
+    if (!c->h_plan) VPX_HIP(c, c->h_plan.alloc(model::plan_bytes(4096)));
+    Owned<uint8_t> aux;  // the context's only once the tables are in it
+    VPX_HIP(c, aux.alloc(kJumpBytes + model::plan_bytes(4096)));
     const hipError_t e = hipMemcpy(aux, t.data(), kJumpBytes, hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        (void)hipFree(aux);
-        return fail(c, VPX_E_DEVICE, std::string("jump tables: ") + hipGetErrorString(e));
-    }
-    c->d_model_aux = aux;
+    if (e != hipSuccess) return fail(c, VPX_E_DEVICE, std::string("jump tables: ") + hipGetErrorString(e));
+    c->d_model_aux = std::move(aux);
     return VPX_OK;
 }
 
@@ -2856,20 +2918,17 @@ int vpx_model_upload(vpx_ctx* c, uint32_t id, const uint8_t* voxels, uint32_t sx
         return fail(c, VPX_E_INVALID, "model dimension outside 1..256");
     VPX_HIP(c, hipSetDevice(c->device));
     VPX_HIP(c, sync_all(c));
-    if (id < c->models.size() && c->models[id].vox) {
-        (void)hipFree(c->models[id].vox);
-        (void)hipFree(c->models[id].mat);
-        c->models[id] = vpx_ctx::ModelBuf{};
-    }
+    if (id < c->models.size()) c->models[id] = vpx_ctx::ModelBuf{};
     if (!voxels) return VPX_OK;
     if (int rc = ensure_model_aux(c)) return rc;
     if (id >= c->models.size()) c->models.resize(id + 1);
-    auto& m = c->models[id];
+    vpx_ctx::ModelBuf m;  // the context's only when complete: a failure leaves the id empty
     const size_t count = (size_t)sx * sy * sz;
-    VPX_HIP(c, hipMalloc(&m.vox, count));
-    VPX_HIP(c, hipMalloc(&m.mat, (count + model::kChunk - 1) / model::kChunk * model::kChunk));
+    VPX_HIP(c, m.vox.alloc(count));
+    VPX_HIP(c, m.mat.alloc((count + model::kChunk - 1) / model::kChunk * model::kChunk));
     VPX_HIP(c, hipMemcpy(m.vox, voxels, count, hipMemcpyHostToDevice));
     m.sx = sx, m.sy = sy, m.sz = sz;
+    c->models[id] = std::move(m);
     return VPX_OK;
 }
 
@@ -2889,21 +2948,21 @@ int vpx_grid_load_model(vpx_ctx* c, uint32_t id, uint32_t n, uint32_t model_id, 
     vpx_model_result res{};
     model::plan_load(c->h_plan, in, m.sx, m.sy, m.sz, n, res.scale_model);
     res.seed = in->seed;
-    uint8_t* d_plan = c->d_model_aux + kJumpBytes;
+    uint8_t* d_plan = c->d_model_aux.get() + kJumpBytes;
     VPX_HIP(c, hipMemcpyAsync(d_plan, c->h_plan, model::plan_bytes(n), hipMemcpyHostToDevice, c->stream));
     const uint64_t count = (uint64_t)m.sx * m.sy * m.sz;
     const uint8_t* mat = m.vox;
     if (in->mode == VPX_LOAD_RANDOM) {
         const uint64_t chunks = (count + model::kChunk - 1) / model::kChunk;
         hipLaunchKernelGGL(model_random_k, dim3((unsigned)std::min<uint64_t>(1024, (chunks + 255) / 256)), dim3(256), 0,
-                           c->stream, (const uint32_t*)c->d_model_aux, in->seed, count, in->rand_lo, in->rand_hi, m.mat);
+                           c->stream, c->d_model_aux.as<const uint32_t>(), in->seed, count, in->rand_lo, in->rand_hi, m.mat);
         VPX_HIP(c, hipGetLastError());
         res.seed = vpx_xorshift32_jump(in->seed, count);
         mat = m.mat;
     }
     const uint64_t threads = (uint64_t)n * n * ((n % 16u) ? n : n / 16);
     hipLaunchKernelGGL(model_gather_k, dim3((unsigned)std::min<uint64_t>(4096, (threads + 255) / 256)), dim3(256), 0,
-                       c->stream, c->grids[id].ptr, n, (const uint8_t*)d_plan, (const uint8_t*)m.vox, mat, m.sx, m.sy);
+                       c->stream, c->grids[id].ptr, n, (const uint8_t*)d_plan, m.vox, mat, m.sx, m.sy);
     VPX_HIP(c, hipGetLastError());
     if (int rc = build_masks(c, id)) return rc;
     if (out) *out = res;
@@ -2924,14 +2983,14 @@ int vpx_grid_generate_noise(vpx_ctx* c, uint32_t id, uint32_t n, const vpx_noise
     uint64_t *d_total = nullptr, *d_offsets = nullptr;
     if (in->mode == VPX_GEN_NOISE) {  // the prefix buffer of this call: total | offsets | counts
         if (int rc = ensure_scratch(c, (size_t)(8 + 12 * blocks))) return rc;
-        d_total = (uint64_t*)c->d_scratch;
+        d_total = c->d_scratch.as<uint64_t>();
         d_offsets = d_total + 1;
         d_counts = (uint32_t*)(d_offsets + blocks);
     }
     if (id >= c->grids.size() || !c->grids[id].ptr || c->grids[id].n != n)
         if (int rc = alloc_grid(c, id, n)) return rc;
     uint8_t* cells = c->grids[id].ptr;
-    const uint32_t* tables = (const uint32_t*)c->d_model_aux;
+    const uint32_t* tables = c->d_model_aux.as<const uint32_t>();
     const uint32_t noise_seed = model::xs32_step(in->seed);
     const dim3 grid((unsigned)std::min<uint64_t>(8192, blocks)), wg(noise::kBlockThreads);
     if (in->mode == VPX_GEN_SMOKE) {
@@ -2976,7 +3035,7 @@ int vpx_grid_read_box(vpx_ctx* c, uint32_t id, uint8_t* dst, uint32_t x0, uint32
     }
     if (int rc = ensure_scratch(c, bytes)) return rc;
     hipLaunchKernelGGL(read_box_k, dim3((unsigned)std::min<size_t>(4096, (bytes + 255) / 256)), dim3(256), 0, c->stream,
-                       g.ptr, g.n, (uint8_t*)c->d_scratch, x0, y0, z0, dx, dy, dz);
+                       g.ptr, g.n, c->d_scratch.as<uint8_t>(), x0, y0, z0, dx, dy, dz);
     VPX_HIP(c, hipGetLastError());
     VPX_HIP(c, hipMemcpyAsync(dst, c->d_scratch, bytes, hipMemcpyDeviceToHost, c->stream));
     VPX_HIP(c, sync_all(c));
@@ -3167,7 +3226,7 @@ int build_tlas(vpx_ctx* c, const std::vector<VolBox>& bounds) {
     }
     if (!b.items.empty()) b.build(0, (uint32_t)b.items.size());
     if (b.nodes.size() > kTlasMaxNodes) return fail(c, VPX_E_INVALID, "TLAS node budget exceeded");
-    if (!c->d_tlas) VPX_HIP(c, hipMalloc(&c->d_tlas, sizeof(TlasNode) * kTlasMaxNodes));
+    if (!c->d_tlas) VPX_HIP(c, c->d_tlas.alloc(sizeof(TlasNode) * kTlasMaxNodes));
     if (!b.nodes.empty())
         VPX_HIP(c, hipMemcpy(c->d_tlas, b.nodes.data(), sizeof(TlasNode) * b.nodes.size(), hipMemcpyHostToDevice));
     c->tlas_nodes = (uint32_t)b.nodes.size();
@@ -3180,14 +3239,14 @@ int vpx_set_volumes(vpx_ctx* c, const vpx_volume* v, uint32_t count) {
     if (!c || (!v && count)) return fail(c, VPX_E_INVALID, "null argument");
     if (count > 65536) return fail(c, VPX_E_INVALID, "too many volumes");
     VPX_HIP(c, sync_all(c));
-    if (count > c->d_volumes_cap) {
-        if (c->d_volumes) (void)hipFree(c->d_volumes);
-        if (c->d_vbounds) (void)hipFree(c->d_vbounds);
-        c->d_volumes = nullptr;
-        c->d_vbounds = nullptr;
-        VPX_HIP(c, hipMalloc(&c->d_volumes, sizeof(vpx_volume) * count));
-        VPX_HIP(c, hipMalloc(&c->d_vbounds, sizeof(VolBox) * count));
-        c->d_volumes_cap = count;
+    if (sizeof(vpx_volume) * count > c->d_volumes.bytes) {
+        // the tables grow together, and the host copy (the kernels' count) is empty until both
+        // are there; the wait above covers the frames that read the old ones
+        c->volumes.clear();
+        c->d_volumes.release();
+        c->d_vbounds.release();
+        VPX_HIP(c, c->d_volumes.alloc(sizeof(vpx_volume) * count));
+        VPX_HIP(c, c->d_vbounds.alloc(sizeof(VolBox) * count));
     }
     // Invariant: d_volumes, d_vbounds and the TLAS (d_tlas) describe the same volumes.  The
     // instance kernels cull by the TLAS root box and the bounding spheres (FindNearest's
@@ -3223,7 +3282,7 @@ int vpx_set_materials(vpx_ctx* c, const vpx_material* m, uint32_t count) {
     // a new table leaves what the record has accumulated
     if (!c->d_materials) {
         static_assert(sizeof(full) == kProbeOffset, "the table's size is the record's offset");
-        VPX_HIP(c, hipMalloc(&c->d_materials, kMaterialTableBytes));
+        VPX_HIP(c, c->d_materials.alloc(kMaterialTableBytes));
         VPX_HIP(c, hipMemsetAsync(probe_record_of(c->d_materials), 0, kProbeBytes, c->stream));
     }
     VPX_HIP(c, hipMemcpyAsync(c->d_materials, full, sizeof(full), hipMemcpyHostToDevice, c->stream));
@@ -3238,11 +3297,10 @@ int vpx_set_lights(vpx_ctx* c, const vpx_point_light* p, uint32_t np, const vpx_
     if (!c) return VPX_E_INVALID;
     VPX_HIP(c, sync_all(c));
     int rc;
-    if ((rc = upload_table(c, c->d_points, p, np))) return rc;
-    if ((rc = upload_table(c, c->d_spots, s, ns))) return rc;
-    if ((rc = upload_table(c, c->d_areas, a, na))) return rc;
+    if ((rc = upload_table(c, c->points, p, np))) return rc;
+    if ((rc = upload_table(c, c->spots, s, ns))) return rc;
+    if ((rc = upload_table(c, c->areas, a, na))) return rc;
     VPX_HIP(c, sync_all(c));
-    c->n_points = np, c->n_spots = ns, c->n_areas = na;
     if (d) c->dir = *d;
     return VPX_OK;
 }
@@ -3252,10 +3310,9 @@ int vpx_set_shapes(vpx_ctx* c, const vpx_sphere* s, uint32_t ns, const vpx_trian
     if (!c) return VPX_E_INVALID;
     VPX_HIP(c, sync_all(c));
     int rc;
-    if ((rc = upload_table(c, c->d_spheres, s, ns))) return rc;
-    if ((rc = upload_table(c, c->d_triangles, t, nt))) return rc;
+    if ((rc = upload_table(c, c->spheres, s, ns))) return rc;
+    if ((rc = upload_table(c, c->triangles, t, nt))) return rc;
     VPX_HIP(c, sync_all(c));
-    c->n_spheres = ns, c->n_triangles = nt;
     return VPX_OK;
 }
 
@@ -3264,27 +3321,21 @@ int vpx_set_sky(vpx_ctx* c, const float* rgb, uint32_t width, uint32_t height, f
     if (!c) return VPX_E_INVALID;
     VPX_HIP(c, hipSetDevice(c->device));
     if (!rgb || !width || !height) {  // remove the texture (misses use the constant sky)
-        if (c->d_sky) {
-            VPX_HIP(c, sync_all(c));
-            (void)hipFree(c->d_sky);
-        }
-        c->d_sky = nullptr;
-        c->sky_w = c->sky_h = 0;
+        if (c->sky.px) VPX_HIP(c, sync_all(c));
+        c->sky = vpx_ctx::Sky{};
         return VPX_OK;
     }
     if ((uint64_t)width * height > (1ull << 28)) return fail(c, VPX_E_INVALID, "sky texture too large");
     const size_t bytes = sizeof(float) * 3 * (size_t)width * height;
-    if ((size_t)c->sky_w * c->sky_h != (size_t)width * height) {
+    if ((size_t)c->sky.w * c->sky.h != (size_t)width * height) {  // no sky until the new one is whole
         VPX_HIP(c, sync_all(c));
-        if (c->d_sky) (void)hipFree(c->d_sky);
-        c->d_sky = nullptr;
-        c->sky_w = c->sky_h = 0;
-        VPX_HIP(c, hipMalloc(&c->d_sky, bytes));
+        c->sky = vpx_ctx::Sky{};
+        VPX_HIP(c, c->sky.px.alloc(bytes));
     }
     VPX_HIP(c, sync_all(c));  // frames in flight still read the texture
-    VPX_HIP(c, hipMemcpyAsync(c->d_sky, rgb, bytes, hipMemcpyHostToDevice, c->stream));
+    VPX_HIP(c, hipMemcpyAsync(c->sky.px, rgb, bytes, hipMemcpyHostToDevice, c->stream));
     VPX_HIP(c, sync_all(c));
-    c->sky_w = width, c->sky_h = height;
+    c->sky.w = width, c->sky.h = height;
     c->sky_hdr = hdr_contribution;
     return VPX_OK;
 }
@@ -3295,8 +3346,7 @@ int vpx_set_arithmetic(vpx_ctx* c, uint32_t mode) {
     if (mode != VPX_ARITH_EXACT && mode != VPX_ARITH_X86_HOST) return fail(c, VPX_E_INVALID, "unknown arithmetic mode");
     VPX_HIP(c, hipSetDevice(c->device));
     VPX_HIP(c, sync_all(c));  // frames in flight read the tables
-    if (c->d_x86) (void)hipFree(c->d_x86);
-    c->d_x86 = nullptr;
+    c->d_x86.release();
     c->x86 = X86Arith{nullptr, 0u, 0u, 0u, 0u};
     if (mode == VPX_ARITH_EXACT) return VPX_OK;
     uint32_t info[4];
@@ -3306,7 +3356,7 @@ int vpx_set_arithmetic(vpx_ctx* c, uint32_t mode) {
         return fail(c, VPX_E_STATE, "the host's rcpss key is wider than the LDS-staged table allows");
     std::vector<uint32_t> tab(info[3]);
     if (vpx_x86_arith_tables(tab.data(), tab.size(), info) != VPX_OK) return fail(c, VPX_E_STATE, "table capture failed");
-    VPX_HIP(c, hipMalloc(&c->d_x86, sizeof(uint32_t) * tab.size()));
+    VPX_HIP(c, c->d_x86.alloc(sizeof(uint32_t) * tab.size()));
     VPX_HIP(c, hipMemcpy(c->d_x86, tab.data(), sizeof(uint32_t) * tab.size(), hipMemcpyHostToDevice));
     c->x86 = X86Arith{c->d_x86, info[0], info[1], info[2], 0u};
     return VPX_OK;
@@ -3389,14 +3439,8 @@ int vpx_render_reproject(vpx_ctx* c, const vpx_frame_params* p, const vpx_prev_c
     if (!prev || !history) return fail(c, VPX_E_INVALID, "prev camera and history (device float4[W*H]) are required");
     VPX_HIP(c, hipSetDevice(c->device));
     const size_t pix = (size_t)p->width * p->height;
-    if (pix > c->rp_pixels) {
-        VPX_HIP(c, sync_all(c));
-        if (c->rp_buf) (void)hipFree(c->rp_buf);
-        c->rp_buf = nullptr;
-        c->rp_pixels = 0;
-        VPX_HIP(c, hipMalloc(&c->rp_buf, sizeof(float4) * 4 * pix));
-        c->rp_pixels = pix;
-    }
+    // an earlier frame of the path may still read the old images: wait
+    if ((rc = c->rp_buf.grow(c, sizeof(float4) * 4 * pix, true))) return rc;
     Reproj rp;
     auto h3 = [](const float* v) { return f3{v[0], v[1], v[2]}; };
     rp.prev = PrevCam{h3(prev->cam_pos), h3(prev->left_normal), h3(prev->right_normal), h3(prev->top_normal),
@@ -3565,14 +3609,9 @@ static int render_window_impl(vpx_ctx* c, const vpx_frame_params* p, uint32_t n,
             samples = L->cur;
         } else {
             const size_t need = (size_t)B * T * kTilePix;
-            if (c->win_len < need) {
-                VPX_HIP(c, hipStreamSynchronize(c->stream));
-                if (c->win_buf) (void)hipFree(c->win_buf);
-                c->win_buf = nullptr;
-                c->win_len = 0;
-                VPX_HIP(c, hipMalloc(&c->win_buf, sizeof(float4) * need));
-                c->win_len = need;
-            }
+            // the previous chain's blend still reads the old samples: wait (no lanes here, so
+            // everything queued is the stream's)
+            if ((rc = c->win_buf.grow(c, sizeof(float4) * need, true))) return rc;
             samples = c->win_buf;
             if ((rc = launch_render<kFinishPackedSample>(c, c->stream, c->wave, sv, f, B * T, nullptr, nullptr,
                                                          samples)))
@@ -3710,17 +3749,10 @@ int vpx_find_nearest(vpx_ctx* c, const vpx_ray* rays, uint32_t n, vpx_hit* hits)
     int rc = check_ready(c);
     if (rc) return rc;
     if (n == 0) return VPX_OK;
-    const size_t rb = sizeof(vpx_ray) * n, hb = sizeof(vpx_hit) * n;
-    if ((rc = ensure_scratch(c, rb + hb))) return rc;
-    vpx_ray* dr = (vpx_ray*)c->d_scratch;
-    vpx_hit* dh = (vpx_hit*)((char*)c->d_scratch + rb);
-    VPX_HIP(c, hipMemcpyAsync(dr, rays, rb, hipMemcpyHostToDevice, c->stream));
-    const float sky[3] = {0.392f, 0.584f, 0.829f};
-    hipLaunchKernelGGL(find_nearest_k, dim3((n + 255) / 256), dim3(256), 0, c->stream, view_of(c, sky, 3), dr, n, dh);
-    VPX_HIP(c, hipGetLastError());
-    VPX_HIP(c, hipMemcpyAsync(hits, dh, hb, hipMemcpyDeviceToHost, c->stream));
-    VPX_HIP(c, sync_all(c));
-    return VPX_OK;
+    return run_batch(c, {{rays, sizeof(vpx_ray) * n}}, {{hits, sizeof(vpx_hit) * n}}, [&](void* const* in, void* const* out) {
+        hipLaunchKernelGGL(find_nearest_k, dim3((n + 255) / 256), dim3(256), 0, c->stream, view_of(c, kQuerySky, 3),
+                           (vpx_ray*)in[0], n, (vpx_hit*)out[0]);
+    });
 }
 
 int vpx_is_occluded(vpx_ctx* c, const vpx_ray* rays, uint32_t n, uint8_t* occ) {
@@ -3729,17 +3761,10 @@ int vpx_is_occluded(vpx_ctx* c, const vpx_ray* rays, uint32_t n, uint8_t* occ) {
     int rc = check_ready(c);
     if (rc) return rc;
     if (n == 0) return VPX_OK;
-    const size_t rb = sizeof(vpx_ray) * n;
-    if ((rc = ensure_scratch(c, rb + n))) return rc;
-    vpx_ray* dr = (vpx_ray*)c->d_scratch;
-    uint8_t* doc = (uint8_t*)c->d_scratch + rb;
-    VPX_HIP(c, hipMemcpyAsync(dr, rays, rb, hipMemcpyHostToDevice, c->stream));
-    const float sky[3] = {0.392f, 0.584f, 0.829f};
-    hipLaunchKernelGGL(is_occluded_k, dim3((n + 255) / 256), dim3(256), 0, c->stream, view_of(c, sky, 3), dr, n, doc);
-    VPX_HIP(c, hipGetLastError());
-    VPX_HIP(c, hipMemcpyAsync(occ, doc, n, hipMemcpyDeviceToHost, c->stream));
-    VPX_HIP(c, sync_all(c));
-    return VPX_OK;
+    return run_batch(c, {{rays, sizeof(vpx_ray) * n}}, {{occ, n}}, [&](void* const* in, void* const* out) {
+        hipLaunchKernelGGL(is_occluded_k, dim3((n + 255) / 256), dim3(256), 0, c->stream, view_of(c, kQuerySky, 3),
+                           (vpx_ray*)in[0], n, (uint8_t*)out[0]);
+    });
 }
 
 // The filter's refusals, the same for n == 0.  occlusion: the reference has no IsOccludedExcept,
@@ -3761,18 +3786,10 @@ int vpx_find_nearest_filtered(vpx_ctx* c, const vpx_ray* rays, uint32_t n, const
     if (rc) return rc;
     if ((rc = check_ready(c))) return rc;
     if (n == 0) return VPX_OK;
-    const size_t rb = sizeof(vpx_ray) * n, hb = sizeof(vpx_hit) * n;
-    if ((rc = ensure_scratch(c, rb + hb))) return rc;
-    vpx_ray* dr = (vpx_ray*)c->d_scratch;
-    vpx_hit* dh = (vpx_hit*)((char*)c->d_scratch + rb);
-    VPX_HIP(c, hipMemcpyAsync(dr, rays, rb, hipMemcpyHostToDevice, c->stream));
-    const float sky[3] = {0.392f, 0.584f, 0.829f};
-    hipLaunchKernelGGL(find_nearest_filtered_k, dim3((n + 255) / 256), dim3(256), 0, c->stream, view_of(c, sky, 3), dr, n,
-                       *f, dh);
-    VPX_HIP(c, hipGetLastError());
-    VPX_HIP(c, hipMemcpyAsync(hits, dh, hb, hipMemcpyDeviceToHost, c->stream));
-    VPX_HIP(c, sync_all(c));
-    return VPX_OK;
+    return run_batch(c, {{rays, sizeof(vpx_ray) * n}}, {{hits, sizeof(vpx_hit) * n}}, [&](void* const* in, void* const* out) {
+        hipLaunchKernelGGL(find_nearest_filtered_k, dim3((n + 255) / 256), dim3(256), 0, c->stream,
+                           view_of(c, kQuerySky, 3), (vpx_ray*)in[0], n, *f, (vpx_hit*)out[0]);
+    });
 }
 
 int vpx_is_occluded_filtered(vpx_ctx* c, const vpx_ray* rays, uint32_t n, const vpx_ray_filter* f, uint8_t* occ) {
@@ -3782,18 +3799,10 @@ int vpx_is_occluded_filtered(vpx_ctx* c, const vpx_ray* rays, uint32_t n, const 
     if (rc) return rc;
     if ((rc = check_ready(c))) return rc;
     if (n == 0) return VPX_OK;
-    const size_t rb = sizeof(vpx_ray) * n;
-    if ((rc = ensure_scratch(c, rb + n))) return rc;
-    vpx_ray* dr = (vpx_ray*)c->d_scratch;
-    uint8_t* doc = (uint8_t*)c->d_scratch + rb;
-    VPX_HIP(c, hipMemcpyAsync(dr, rays, rb, hipMemcpyHostToDevice, c->stream));
-    const float sky[3] = {0.392f, 0.584f, 0.829f};
-    hipLaunchKernelGGL(is_occluded_filtered_k, dim3((n + 255) / 256), dim3(256), 0, c->stream, view_of(c, sky, 3), dr, n,
-                       *f, doc);
-    VPX_HIP(c, hipGetLastError());
-    VPX_HIP(c, hipMemcpyAsync(occ, doc, n, hipMemcpyDeviceToHost, c->stream));
-    VPX_HIP(c, sync_all(c));
-    return VPX_OK;
+    return run_batch(c, {{rays, sizeof(vpx_ray) * n}}, {{occ, n}}, [&](void* const* in, void* const* out) {
+        hipLaunchKernelGGL(is_occluded_filtered_k, dim3((n + 255) / 256), dim3(256), 0, c->stream,
+                           view_of(c, kQuerySky, 3), (vpx_ray*)in[0], n, *f, (uint8_t*)out[0]);
+    });
 }
 
 int vpx_find_nearest_cells(vpx_ctx* c, const vpx_ray* rays, uint32_t n, const vpx_ray_filter* f, vpx_hit* hits,
@@ -3804,20 +3813,12 @@ int vpx_find_nearest_cells(vpx_ctx* c, const vpx_ray* rays, uint32_t n, const vp
     if (rc) return rc;
     if ((rc = check_ready(c))) return rc;
     if (n == 0) return VPX_OK;
-    const size_t rb = sizeof(vpx_ray) * n, hb = sizeof(vpx_hit) * n, cb = sizeof(vpx_hit_cell) * n;
-    if ((rc = ensure_scratch(c, rb + hb + cb))) return rc;
-    vpx_ray* dr = (vpx_ray*)c->d_scratch;
-    vpx_hit* dh = (vpx_hit*)((char*)c->d_scratch + rb);
-    vpx_hit_cell* dc = (vpx_hit_cell*)((char*)c->d_scratch + rb + hb);
-    VPX_HIP(c, hipMemcpyAsync(dr, rays, rb, hipMemcpyHostToDevice, c->stream));
-    const float sky[3] = {0.392f, 0.584f, 0.829f};
-    hipLaunchKernelGGL(find_nearest_cells_k, dim3((n + 255) / 256), dim3(256), 0, c->stream, view_of(c, sky, 3), dr, n,
-                       *f, dh, dc);
-    VPX_HIP(c, hipGetLastError());
-    VPX_HIP(c, hipMemcpyAsync(hits, dh, hb, hipMemcpyDeviceToHost, c->stream));
-    VPX_HIP(c, hipMemcpyAsync(cells, dc, cb, hipMemcpyDeviceToHost, c->stream));
-    VPX_HIP(c, sync_all(c));
-    return VPX_OK;
+    return run_batch(c, {{rays, sizeof(vpx_ray) * n}}, {{hits, sizeof(vpx_hit) * n}, {cells, sizeof(vpx_hit_cell) * n}},
+                     [&](void* const* in, void* const* out) {
+                         hipLaunchKernelGGL(find_nearest_cells_k, dim3((n + 255) / 256), dim3(256), 0, c->stream,
+                                            view_of(c, kQuerySky, 3), (vpx_ray*)in[0], n, *f, (vpx_hit*)out[0],
+                                            (vpx_hit_cell*)out[1]);
+                     });
 }
 
 // The pixel entries' shared checks and frame: the filter (NULL = neutral, no raw directions: the
@@ -3852,16 +3853,10 @@ int vpx_pick_pixel(vpx_ctx* c, uint32_t width, uint32_t height, uint32_t x, uint
     if (rc) return rc;
     if (x >= width || y >= height) return fail(c, VPX_E_INVALID, "pixel outside the frame");
     VPX_HIP(c, hipSetDevice(c->device));
-    if ((rc = ensure_scratch(c, sizeof(vpx_hit) + sizeof(vpx_hit_cell)))) return rc;
-    vpx_hit* dh = (vpx_hit*)c->d_scratch;
-    vpx_hit_cell* dc = (vpx_hit_cell*)((char*)c->d_scratch + sizeof(vpx_hit));
-    const float sky[3] = {0.392f, 0.584f, 0.829f};
-    hipLaunchKernelGGL(pick_pixel_k, dim3(1), dim3(1), 0, c->stream, view_of(c, sky, 3), fa, flt, x, y, dh, dc);
-    VPX_HIP(c, hipGetLastError());
-    VPX_HIP(c, hipMemcpyAsync(hit, dh, sizeof(vpx_hit), hipMemcpyDeviceToHost, c->stream));
-    VPX_HIP(c, hipMemcpyAsync(cell, dc, sizeof(vpx_hit_cell), hipMemcpyDeviceToHost, c->stream));
-    VPX_HIP(c, sync_all(c));
-    return VPX_OK;
+    return run_batch(c, {}, {{hit, sizeof(vpx_hit)}, {cell, sizeof(vpx_hit_cell)}}, [&](void* const*, void* const* out) {
+        hipLaunchKernelGGL(pick_pixel_k, dim3(1), dim3(1), 0, c->stream, view_of(c, kQuerySky, 3), fa, flt, x, y,
+                           (vpx_hit*)out[0], (vpx_hit_cell*)out[1]);
+    });
 }
 
 int vpx_render_ids(vpx_ctx* c, const vpx_frame_params* p, const vpx_ray_filter* f, uint32_t* ids) {
@@ -3872,8 +3867,7 @@ int vpx_render_ids(vpx_ctx* c, const vpx_frame_params* p, const vpx_ray_filter* 
     const int rc = pixel_frame(c, p->width, p->height, f, flt, fa);
     if (rc) return rc;
     VPX_HIP(c, hipSetDevice(c->device));
-    const float sky[3] = {0.392f, 0.584f, 0.829f};
-    hipLaunchKernelGGL(k_ids, dim3(fa.num_tiles), dim3(kThreads), 0, c->stream, view_of(c, sky, 3), fa, flt,
+    hipLaunchKernelGGL(k_ids, dim3(fa.num_tiles), dim3(kThreads), 0, c->stream, view_of(c, kQuerySky, 3), fa, flt,
                        reinterpret_cast<uint4*>(ids));
     VPX_HIP(c, hipGetLastError());
     return VPX_OK;
@@ -3910,7 +3904,7 @@ static int cast_begin(vpx_ctx* c, uint32_t n, const vpx_ray_filter* f, const vpx
 // (whole workgroups are launched; the last one's waves beyond the count leave at once), never more
 // than the batch has grabs or the device holds at once (wpe: the kernel's waves per SIMD).
 static int cast_pool_grid(vpx_ctx* c, uint32_t n, const vpx_cast& o, uint32_t wpe, uint32_t& waves, uint32_t& blocks) {
-    if (!c->cast_grab) VPX_HIP(c, hipMalloc(&c->cast_grab, sizeof(uint32_t) * kGrabBlock));
+    if (!c->cast_grab) VPX_HIP(c, c->cast_grab.alloc(sizeof(uint32_t) * kGrabBlock));
     VPX_HIP(c, hipMemsetAsync(c->cast_grab, 0, sizeof(uint32_t) * kGrabBlock, c->stream));
     const uint32_t chunks = (n + kPoolChunk - 1u) / kPoolChunk, wpb = kPoolWg / 64u;
     waves = std::min(chunks, c->cus * 4u * wpe);
@@ -3930,8 +3924,7 @@ int vpx_cast_nearest(vpx_ctx* c, const vpx_ray* rays, uint32_t n, const vpx_ray_
     if (rc) return rc;
     if (n == 0) return VPX_OK;
     VPX_HIP(c, hipSetDevice(c->device));
-    const float sky[3] = {0.392f, 0.584f, 0.829f};
-    const SceneView sv = view_of(c, sky, 3);
+    const SceneView sv = view_of(c, kQuerySky, 3);
     if (pool) {
         uint32_t waves = 0, blocks = 0;
         if ((rc = cast_pool_grid(c, n, o, cells ? VPX_WPE_CAST_CELLS : VPX_WPE_CAST, waves, blocks))) return rc;
@@ -3959,8 +3952,7 @@ int vpx_cast_occluded(vpx_ctx* c, const vpx_ray* rays, uint32_t n, const vpx_ray
     if (rc) return rc;
     if (n == 0) return VPX_OK;
     VPX_HIP(c, hipSetDevice(c->device));
-    const float sky[3] = {0.392f, 0.584f, 0.829f};
-    const SceneView sv = view_of(c, sky, 3);
+    const SceneView sv = view_of(c, kQuerySky, 3);
     if (pool) {
         uint32_t waves = 0, blocks = 0;
         if ((rc = cast_pool_grid(c, n, o, VPX_WPE_CAST, waves, blocks))) return rc;
@@ -3976,7 +3968,7 @@ int vpx_cast_occluded(vpx_ctx* c, const vpx_ray* rays, uint32_t n, const vpx_ray
 
 int vpx_debug_last_cast_kernel(vpx_ctx* c) {
     if (!c) return 0;
-    return c->members.empty() ? c->last_cast : c->members[0]->last_cast;
+    return c->members.empty() ? c->last_cast : c->members[0].ctx->last_cast;
 }
 
 int vpx_denoise_ids(vpx_ctx* c, const vpx_frame_params* p, const uint32_t* ids, const float* in, float* out,
@@ -3986,19 +3978,17 @@ int vpx_denoise_ids(vpx_ctx* c, const vpx_frame_params* p, const uint32_t* ids, 
     if (const char* why = denoise::check_call(p->width, p->height, ids, in, out, d)) return fail(c, VPX_E_INVALID, why);
     VPX_HIP(c, hipSetDevice(c->device));
     const size_t pixels = (size_t)p->width * p->height;
-    const size_t key_bytes = (pixels * sizeof(uint2) + 255) & ~(size_t)255;
-    const size_t bytes = key_bytes + (d->passes > 1 ? 2 * pixels * sizeof(float4) : 0);
-    if (bytes > c->dn_bytes) {
-        VPX_HIP(c, sync_all(c));  // an earlier call may still read the old scratch
-        if (c->dn_buf) (void)hipFree(c->dn_buf);
-        c->dn_buf = nullptr;
-        c->dn_bytes = 0;
-        VPX_HIP(c, hipMalloc(&c->dn_buf, bytes));
-        c->dn_bytes = bytes;
-    }
-    uint2* keys = reinterpret_cast<uint2*>(c->dn_buf);
-    float4* img[2] = {reinterpret_cast<float4*>((char*)c->dn_buf + key_bytes),
-                      reinterpret_cast<float4*>((char*)c->dn_buf + key_bytes) + pixels};
+    uint2* keys = nullptr;
+    float4* img[2] = {nullptr, nullptr};
+    auto carve = [&](Carve cv) {  // the keys, then the two images of a call with several passes
+        keys = cv.take<uint2>(pixels * sizeof(uint2));
+        if (d->passes > 1)
+            for (auto& i : img) i = cv.take<float4>(pixels * sizeof(float4));
+        return cv.used();
+    };
+    // an earlier call may still read the old scratch: wait
+    if (int rc = c->dn_buf.grow(c, carve(Carve(nullptr)), true)) return rc;
+    carve(Carve(c->dn_buf));
     hipLaunchKernelGGL(k_plane_key, dim3((uint32_t)((pixels + kThreads - 1) / kThreads)), dim3(kThreads), 0, c->stream,
                        (uint32_t)pixels, reinterpret_cast<const uint4*>(ids), keys);
     DenoiseArgs a;
@@ -4035,16 +4025,8 @@ static int reproject_table(vpx_ctx* c, uint32_t n, const vpx_volume* cur_volumes
     if (t == c->rj_last) return VPX_OK;
     if (!c->rj_ev) VPX_HIP(c, hipEventCreateWithFlags(&c->rj_ev, hipEventDisableTiming));
     VPX_HIP(c, hipEventSynchronize(c->rj_ev));  // the staging copy's last upload (long past, as a rule)
-    if (words * 4 > c->rj_host_bytes) {
-        if (c->rj_host) (void)hipHostFree(c->rj_host);
-        c->rj_host = nullptr;
-        c->rj_host_bytes = 0;
-        if (hipHostMalloc(&c->rj_host, words * 4) != hipSuccess) {
-            c->rj_host = nullptr;
-            return fail(c, VPX_E_NOMEM, "reproject volume table staging");
-        }
-        c->rj_host_bytes = words * 4;
-    }
+    // no wait: rj_ev, just above, was this staging copy's only reader
+    if (int rc = c->rj_host.grow(c, words * 4, false)) return rc;
     memcpy(c->rj_host, t.data(), words * 4);
     c->rj_last.clear();
     VPX_HIP(c, hipMemcpyAsync(c->rj_buf, c->rj_host, words * 4, hipMemcpyHostToDevice, c->stream));
@@ -4064,28 +4046,26 @@ int vpx_reproject_ids(vpx_ctx* c, const vpx_frame_params* p, const uint32_t* ids
     VPX_HIP(c, hipSetDevice(c->device));
     const bool have_prev = ids_prev != nullptr;
     const size_t pixels = (size_t)p->width * p->height;
-    const size_t tab_bytes = ((size_t)r->n_volumes * (reproject::kTabFloats + 1u) * 4 + 255) & ~(size_t)255;
-    const size_t key_bytes = (VPX_REPROJECT_PREKEY && have_prev) ? pixels * sizeof(uint2) : 0;
-    const size_t bytes = tab_bytes + key_bytes;
-    if (bytes > c->rj_bytes) {
-        VPX_HIP(c, sync_all(c));  // an earlier call may still read the old scratch
-        if (c->rj_buf) (void)hipFree(c->rj_buf);
-        c->rj_buf = nullptr;
-        c->rj_bytes = 0;
-        c->rj_last.clear();
-        if (hipMalloc(&c->rj_buf, bytes) != hipSuccess) {
-            c->rj_buf = nullptr;
-            return fail(c, VPX_E_NOMEM, "reproject scratch");
-        }
-        c->rj_bytes = bytes;
+    const bool prekey = VPX_REPROJECT_PREKEY && have_prev;
+    const float* tab = nullptr;
+    uint2* keys = nullptr;
+    auto carve = [&](Carve cv) {  // the volume table (at the base: reproject_table), then the optional keys
+        tab = cv.take<const float>((size_t)r->n_volumes * (reproject::kTabFloats + 1u) * 4);
+        if (prekey) keys = cv.take<uint2>(pixels * sizeof(uint2));
+        return cv.used();
+    };
+    const size_t bytes = carve(Carve(nullptr));
+    if (bytes > c->rj_buf.bytes) {
+        c->rj_last.clear();  // the new scratch does not hold the table
+        // an earlier call may still read the old scratch: wait
+        if (int rc = c->rj_buf.grow(c, bytes, true)) return rc;
     }
-    const float* tab = reinterpret_cast<const float*>(c->rj_buf);
-    const uint32_t* moved = reinterpret_cast<const uint32_t*>(c->rj_buf) + (size_t)r->n_volumes * reproject::kTabFloats;
+    carve(Carve(c->rj_buf));
+    const uint32_t* moved = reinterpret_cast<const uint32_t*>(tab) + (size_t)r->n_volumes * reproject::kTabFloats;
     if (r->n_volumes)
         if (int rc = reproject_table(c, r->n_volumes, cur_volumes, prev_volumes)) return rc;
     const void* prev = ids_prev;
-    if (key_bytes) {
-        uint2* keys = reinterpret_cast<uint2*>((char*)c->rj_buf + tab_bytes);
+    if (prekey) {
         hipLaunchKernelGGL(k_plane_key, dim3((uint32_t)((pixels + kThreads - 1) / kThreads)), dim3(kThreads), 0, c->stream,
                            (uint32_t)pixels, reinterpret_cast<const uint4*>(ids_prev), keys);
         prev = keys;
@@ -4116,42 +4096,35 @@ int vpx_reproject_ids(vpx_ctx* c, const vpx_frame_params* p, const uint32_t* ids
 static int trace_rays(vpx_ctx* c, const vpx_ray* rays, const uint32_t* seeds, uint32_t n, int32_t depth,
                       const float sky[3], int32_t area_samples, float* radiance, vpx_ray_probe* probes) {
     if (depth < -1 || depth > kMaxLevels - 2) return fail(c, VPX_E_INVALID, "depth must be in [-1, 14]");
-    if (!sky && !c->d_sky) return fail(c, VPX_E_STATE, "sky == NULL (textured sky) without vpx_set_sky");
+    if (!sky && !c->sky.px) return fail(c, VPX_E_STATE, "sky == NULL (textured sky) without vpx_set_sky");
     int rc = check_ready(c);
     if (rc) return rc;
     static const float kNoSky[3] = {0.f, 0.f, 0.f};
     if (n == 0) return VPX_OK;
-    const size_t rb = sizeof(vpx_ray) * n, sb = 4ull * n, ob = 12ull * n;
-    const size_t pb = probes ? sizeof(vpx_ray_probe) * n : 0;
-    if ((rc = ensure_scratch(c, rb + sb + ob + pb + 16))) return rc;
-    vpx_ray* dr = (vpx_ray*)c->d_scratch;
-    uint32_t* ds = (uint32_t*)((char*)c->d_scratch + rb);
-    float* dout = (float*)((char*)c->d_scratch + rb + sb);
-    // (16-byte records: rb and sb + ob are multiples of 16 only together with the padding)
-    vpx_ray_probe* dp = (vpx_ray_probe*)((char*)c->d_scratch + ((rb + sb + ob + 15) & ~(size_t)15));
-    VPX_HIP(c, hipMemcpyAsync(dr, rays, rb, hipMemcpyHostToDevice, c->stream));
-    VPX_HIP(c, hipMemcpyAsync(ds, seeds, sb, hipMemcpyHostToDevice, c->stream));
     const SceneView sv = view_of(c, sky ? sky : kNoSky, area_samples, sky == nullptr);
     const dim3 g((n + 255) / 256), b(256);
-    if (probes) {
-        float* po = radiance ? dout : nullptr;
-        if (depth <= 0)
-            hipLaunchKernelGGL(trace_probe_k<1>, g, b, 0, c->stream, sv, dr, ds, n, depth, po, dp);
-        else if (depth <= 4)
-            hipLaunchKernelGGL(trace_probe_k<5>, g, b, 0, c->stream, sv, dr, ds, n, depth, po, dp);
-        else
-            hipLaunchKernelGGL(trace_probe_k<kMaxLevels>, g, b, 0, c->stream, sv, dr, ds, n, depth, po, dp);
-    } else if (depth <= 0)
-        hipLaunchKernelGGL(trace_k<1>, g, b, 0, c->stream, sv, dr, ds, n, depth, dout);
-    else if (depth <= 4)
-        hipLaunchKernelGGL(trace_k<5>, g, b, 0, c->stream, sv, dr, ds, n, depth, dout);
-    else
-        hipLaunchKernelGGL(trace_k<kMaxLevels>, g, b, 0, c->stream, sv, dr, ds, n, depth, dout);
-    VPX_HIP(c, hipGetLastError());
-    if (radiance) VPX_HIP(c, hipMemcpyAsync(radiance, dout, ob, hipMemcpyDeviceToHost, c->stream));
-    if (probes) VPX_HIP(c, hipMemcpyAsync(probes, dp, pb, hipMemcpyDeviceToHost, c->stream));
-    VPX_HIP(c, sync_all(c));
-    return VPX_OK;
+    return run_batch(c, {{rays, sizeof(vpx_ray) * n}, {seeds, 4ull * n}},
+                     {{radiance, 12ull * n}, {probes, probes ? sizeof(vpx_ray_probe) * n : 0}},
+                     [&](void* const* in, void* const* out) {
+                         vpx_ray* dr = (vpx_ray*)in[0];
+                         uint32_t* ds = (uint32_t*)in[1];
+                         float* dout = (float*)out[0];
+                         vpx_ray_probe* dp = (vpx_ray_probe*)out[1];
+                         if (probes) {
+                             float* po = radiance ? dout : nullptr;
+                             if (depth <= 0)
+                                 hipLaunchKernelGGL(trace_probe_k<1>, g, b, 0, c->stream, sv, dr, ds, n, depth, po, dp);
+                             else if (depth <= 4)
+                                 hipLaunchKernelGGL(trace_probe_k<5>, g, b, 0, c->stream, sv, dr, ds, n, depth, po, dp);
+                             else
+                                 hipLaunchKernelGGL(trace_probe_k<kMaxLevels>, g, b, 0, c->stream, sv, dr, ds, n, depth, po, dp);
+                         } else if (depth <= 0)
+                             hipLaunchKernelGGL(trace_k<1>, g, b, 0, c->stream, sv, dr, ds, n, depth, dout);
+                         else if (depth <= 4)
+                             hipLaunchKernelGGL(trace_k<5>, g, b, 0, c->stream, sv, dr, ds, n, depth, dout);
+                         else
+                             hipLaunchKernelGGL(trace_k<kMaxLevels>, g, b, 0, c->stream, sv, dr, ds, n, depth, dout);
+                     });
 }
 
 int vpx_trace(vpx_ctx* c, const vpx_ray* rays, const uint32_t* seeds, uint32_t n, int32_t depth, const float sky[3],
@@ -4173,9 +4146,7 @@ int vpx_bvh_set(vpx_ctx* c, const vpx_bvh_tri* tris, uint32_t n) {
     if (!c || (n && !tris)) return fail(c, VPX_E_INVALID, "null argument");
     if (n > VPX_BVH_MAX_TRIS) return fail(c, VPX_E_INVALID, "more triangles than VPX_BVH_MAX_TRIS");
     VPX_HIP(c, sync_all(c));
-    if (c->d_bvh) (void)hipFree(c->d_bvh);
-    c->d_bvh = nullptr;
-    c->bvh_nodes = c->bvh_tris = 0;
+    c->bvh = vpx_ctx::Bvh{};
     if (!n) return VPX_OK;
     std::vector<vpx_bvh_node> nodes(2 * (size_t)n - 1);
     std::vector<uint32_t> idx(n);
@@ -4189,30 +4160,25 @@ int vpx_bvh_set(vpx_ctx* c, const vpx_bvh_tri* tris, uint32_t n) {
     std::vector<uint32_t> img(used * 8u + n * 9u);
     std::memcpy(img.data(), nodes.data(), sizeof(vpx_bvh_node) * used);
     for (uint32_t k = 0; k < n; ++k) std::memcpy(&img[used * 8u + k * 9u], &tris[idx[k]], sizeof(vpx_bvh_tri));
-    VPX_HIP(c, hipMalloc(&c->d_bvh, sizeof(uint32_t) * img.size()));
-    VPX_HIP(c, hipMemcpy(c->d_bvh, img.data(), sizeof(uint32_t) * img.size(), hipMemcpyHostToDevice));
-    c->bvh_nodes = used, c->bvh_tris = n;
+    vpx_ctx::Bvh bvh;  // the context's only with its image and counts together
+    VPX_HIP(c, bvh.img.alloc(sizeof(uint32_t) * img.size()));
+    VPX_HIP(c, hipMemcpy(bvh.img, img.data(), sizeof(uint32_t) * img.size(), hipMemcpyHostToDevice));
+    bvh.nodes = used, bvh.tris = n;
+    c->bvh = std::move(bvh);
     return VPX_OK;
 }
 
 int vpx_bvh_intersect(vpx_ctx* c, const vpx_ray* rays, uint32_t n, float* t_out) {
     VPX_GROUP_FIRST(c, vpx_bvh_intersect(m_, rays, n, t_out));
     if (!c || (n && (!rays || !t_out))) return fail(c, VPX_E_INVALID, "null argument");
-    if (!c->d_bvh) return fail(c, VPX_E_STATE, "no BVH set (vpx_bvh_set)");
+    if (!c->bvh.img) return fail(c, VPX_E_STATE, "no BVH set (vpx_bvh_set)");
     if (n == 0) return VPX_OK;
-    const size_t rb = sizeof(vpx_ray) * n, tb = sizeof(float) * n;
-    int rc = ensure_scratch(c, rb + tb);
-    if (rc) return rc;
-    vpx_ray* dr = (vpx_ray*)c->d_scratch;
-    float* dt = (float*)((char*)c->d_scratch + rb);
-    VPX_HIP(c, hipMemcpyAsync(dr, rays, rb, hipMemcpyHostToDevice, c->stream));
-    const size_t lds = sizeof(uint32_t) * (c->bvh_nodes * 8u + c->bvh_tris * 9u);  // <= 51 KiB (512 triangles)
-    hipLaunchKernelGGL(bvh_intersect_k, dim3((n + 255) / 256), dim3(256), lds, c->stream, (const uint32_t*)c->d_bvh,
-                       c->bvh_nodes, c->bvh_tris, dr, n, dt);
-    VPX_HIP(c, hipGetLastError());
-    VPX_HIP(c, hipMemcpyAsync(t_out, dt, tb, hipMemcpyDeviceToHost, c->stream));
-    VPX_HIP(c, sync_all(c));
-    return VPX_OK;
+    const vpx_ctx::Bvh& bvh = c->bvh;
+    const size_t lds = sizeof(uint32_t) * (bvh.nodes * 8u + bvh.tris * 9u);  // <= 51 KiB (512 triangles)
+    return run_batch(c, {{rays, sizeof(vpx_ray) * n}}, {{t_out, sizeof(float) * n}}, [&](void* const* in, void* const* out) {
+        hipLaunchKernelGGL(bvh_intersect_k, dim3((n + 255) / 256), dim3(256), lds, c->stream, bvh.img,
+                           bvh.nodes, bvh.tris, (vpx_ray*)in[0], n, (float*)out[0]);
+    });
 }
 
 int vpx_focus_distance(vpx_ctx* c, uint32_t width, uint32_t height, float* fd) {
@@ -4221,16 +4187,12 @@ int vpx_focus_distance(vpx_ctx* c, uint32_t width, uint32_t height, float* fd) {
     int rc = check_ready(c);
     if (rc) return rc;
     if (!c->have_camera) return fail(c, VPX_E_STATE, "no camera set");
-    if ((rc = ensure_scratch(c, 16))) return rc;
     vpx_frame_params p{};
     p.width = width, p.height = height;
     const float sky[3] = {0, 0, 0};
-    hipLaunchKernelGGL(focus_k, dim3(1), dim3(1), 0, c->stream, view_of(c, sky, 3), frame_of(c, &p, 0, 1),
-                       (float*)c->d_scratch);
-    VPX_HIP(c, hipGetLastError());
-    VPX_HIP(c, hipMemcpyAsync(fd, c->d_scratch, sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    VPX_HIP(c, sync_all(c));
-    return VPX_OK;
+    return run_batch(c, {}, {{fd, sizeof(float)}}, [&](void* const*, void* const* out) {
+        hipLaunchKernelGGL(focus_k, dim3(1), dim3(1), 0, c->stream, view_of(c, sky, 3), frame_of(c, &p, 0, 1), (float*)out[0]);
+    });
 }
 
 uint32_t vpx_pixel_seed(uint32_t base, uint32_t frame, uint32_t w, uint32_t h, uint32_t x, uint32_t y) {
@@ -4260,26 +4222,23 @@ static int group_render(vpx_ctx* c, const vpx_frame_params* p, float* accum, uin
     const bool samples = accum != nullptr;
     const size_t elem = samples ? sizeof(float4) : sizeof(uint32_t);
     int rc;
-    if (c->g_len < L) {  // (re)size the per-member buffers
+    // (re)size the per-member buffers, all of them together: each waits for its member's queued
+    // work (which still writes the old one), the gathered buffer for member 0's composite
+    const size_t room = sizeof(float4) * L;
+    bool fits = c->g_gathered.bytes >= room * n;
+    for (const auto& mem : c->members) fits = fits && mem.packed.bytes >= room && mem.accum.bytes >= room;
+    if (!fits) {
         for (uint32_t r = 0; r < n; ++r) {
-            vpx_ctx* m = c->members[r];
+            auto& mem = c->members[r];
+            vpx_ctx* m = mem.ctx;
             VPX_HIP(c, hipSetDevice(m->device));
-            VPX_HIP(c, hipStreamSynchronize(m->stream));
-            if (c->g_packed[r]) (void)hipFree(c->g_packed[r]);
-            if (c->g_accum[r]) (void)hipFree(c->g_accum[r]);
-            c->g_packed[r] = nullptr, c->g_accum[r] = nullptr;
-            VPX_HIP(c, hipMalloc(&c->g_packed[r], sizeof(float4) * L));
-            VPX_HIP(c, hipMalloc((void**)&c->g_accum[r], sizeof(float4) * L));
-            VPX_HIP(c, hipMemsetAsync(c->g_accum[r], 0, sizeof(float4) * L, m->stream));
-            if (r == 0) {
-                if (c->g_gathered) (void)hipFree(c->g_gathered);
-                c->g_gathered = nullptr;
-                VPX_HIP(c, hipMalloc(&c->g_gathered, sizeof(float4) * L * n));
-            }
+            if ((rc = mem.packed.grow(m, room, true)) || (rc = mem.accum.grow(m, room, true)) ||
+                (r == 0 && (rc = c->g_gathered.grow(m, room * n, true))))
+                return fail(c, rc, "device " + std::to_string(m->device) + ": " + m->err);
+            VPX_HIP(c, hipMemsetAsync(mem.accum, 0, room, m->stream));
         }
-        c->g_len = L;
     }
-    vpx_ctx* m0 = c->members[0];
+    vpx_ctx* m0 = c->members[0].ctx;
     if (stats) std::memset(stats, 0, sizeof(*stats));
     // stats: every member's counters are read BEFORE any member launches and after the whole
     // set is done, and each member's render is bracketed by events on its own stream, so
@@ -4287,33 +4246,34 @@ static int group_render(vpx_ctx* c, const vpx_frame_params* p, float* accum, uin
     std::vector<std::array<unsigned long long, kCtrWords>> before(stats ? n : 0);
     if (stats)
         for (uint32_t r = 0; r < n; ++r) {
-            VPX_HIP(c, hipSetDevice(c->members[r]->device));
-            if ((rc = snapshot_counters(c->members[r], before[r].data()))) return fail(c, rc, c->members[r]->err);
+            vpx_ctx* m = c->members[r].ctx;
+            VPX_HIP(c, hipSetDevice(m->device));
+            if ((rc = snapshot_counters(m, before[r].data()))) return fail(c, rc, m->err);
         }
     // 1. every member renders its tiles (launches are asynchronous: the devices overlap)
     for (uint32_t r = 0; r < n; ++r) {
-        vpx_ctx* m = c->members[r];
+        auto& mem = c->members[r];
+        vpx_ctx* m = mem.ctx;
         VPX_HIP(c, hipSetDevice(m->device));
         if (c->comms.empty())  // copy path: the previous frame's copy of this buffer is done
             VPX_HIP(c, hipStreamWaitEvent(m->stream, c->g_copied, 0));
         if (stats) VPX_HIP(c, hipEventRecord(m->ev0, m->stream));
-        rc = samples ? vpx_render_tiles(m, p, kTile, kTile, r, n, (float*)c->g_packed[r], nullptr)
-                     : vpx_render_tiles_accum(m, p, kTile, kTile, r, n, c->g_accum[r], (uint32_t*)c->g_packed[r],
-                                              nullptr);
+        rc = samples ? vpx_render_tiles(m, p, kTile, kTile, r, n, mem.packed.as<float>(), nullptr)
+                     : vpx_render_tiles_accum(m, p, kTile, kTile, r, n, mem.accum, mem.packed.as<uint32_t>(), nullptr);
         if (rc) return fail(c, rc, "device " + std::to_string(m->device) + ": " + m->err);
         if (stats) VPX_HIP(c, hipEventRecord(m->ev1, m->stream));
-        if (c->comms.empty()) VPX_HIP(c, hipEventRecord(c->g_ev[r], m->stream));
+        if (c->comms.empty()) VPX_HIP(c, hipEventRecord(mem.ev, m->stream));
     }
     // 2. gather the packed buffers to member 0
-    char* dst = (char*)c->g_gathered;
+    char* dst = c->g_gathered.as<char>();
     const size_t bytes = elem * L;
     if (!c->comms.empty()) {
         VPX_HIP(c, hipSetDevice(m0->device));
-        VPX_HIP(c, hipMemcpyAsync(dst, c->g_packed[0], bytes, hipMemcpyDeviceToDevice, m0->stream));
+        VPX_HIP(c, hipMemcpyAsync(dst, c->members[0].packed, bytes, hipMemcpyDeviceToDevice, m0->stream));
         if (ncclGroupStart() != ncclSuccess) return fail(c, VPX_E_DEVICE, "ncclGroupStart");
         for (uint32_t r = 1; r < n; ++r) {
             if (ncclRecv(dst + bytes * r, bytes, ncclChar, (int)r, c->comms[0], m0->stream) != ncclSuccess ||
-                ncclSend(c->g_packed[r], bytes, ncclChar, 0, c->comms[r], c->members[r]->stream) != ncclSuccess) {
+                ncclSend(c->members[r].packed, bytes, ncclChar, 0, c->comms[r], c->members[r].ctx->stream) != ncclSuccess) {
                 (void)ncclGroupEnd();
                 return fail(c, VPX_E_DEVICE, "RCCL gather");
             }
@@ -4322,9 +4282,9 @@ static int group_render(vpx_ctx* c, const vpx_frame_params* p, float* accum, uin
     } else {
         VPX_HIP(c, hipSetDevice(m0->device));
         for (uint32_t r = 0; r < n; ++r) {
-            vpx_ctx* m = c->members[r];
-            VPX_HIP(c, hipStreamWaitEvent(m0->stream, c->g_ev[r], 0));
-            VPX_HIP(c, hipMemcpyPeerAsync(dst + bytes * r, m0->device, c->g_packed[r], m->device, bytes, m0->stream));
+            const auto& mem = c->members[r];
+            VPX_HIP(c, hipStreamWaitEvent(m0->stream, mem.ev, 0));
+            VPX_HIP(c, hipMemcpyPeerAsync(dst + bytes * r, m0->device, mem.packed, mem.ctx->device, bytes, m0->stream));
         }
         VPX_HIP(c, hipEventRecord(c->g_copied, m0->stream));
     }
@@ -4336,7 +4296,7 @@ static int group_render(vpx_ctx* c, const vpx_frame_params* p, float* accum, uin
         VPX_HIP(c, hipSetDevice(m0->device));
         VPX_HIP(c, hipEventRecord(m0->ev2, m0->stream));
         for (uint32_t r = 0; r < n; ++r) {
-            vpx_ctx* m = c->members[r];
+            vpx_ctx* m = c->members[r].ctx;
             VPX_HIP(c, hipSetDevice(m->device));
             unsigned long long after[kCtrWords];
             if ((rc = snapshot_counters(m, after))) return fail(c, rc, m->err);  // synchronises m's stream
@@ -4374,11 +4334,9 @@ int vpx_create_multi(const int* devices, int ndev, vpx_ctx** out) {
             vpx_destroy(c);
             return rc;
         }
-        c->members.push_back(m);
-        c->g_packed.push_back(nullptr);
-        c->g_accum.push_back(nullptr);
-        c->g_ev.push_back(nullptr);
-        if (hipEventCreateWithFlags(&c->g_ev.back(), hipEventDisableTiming) != hipSuccess) {
+        c->members.emplace_back();
+        c->members.back().ctx = m;
+        if (hipEventCreateWithFlags(&c->members.back().ev, hipEventDisableTiming) != hipSuccess) {
             vpx_destroy(c);
             return VPX_E_DEVICE;
         }
@@ -4489,6 +4447,8 @@ int vpx_debug_last_frame_kernel(vpx_ctx* c) {
     VPX_GROUP_FIRST(c, vpx_debug_last_frame_kernel(m_));
     return c ? c->last_frame_kernel : VPX_E_INVALID;
 }
+
+uint64_t vpx_debug_live_buffers(void) { return g_live_buffers.load(); }
 
 #ifdef VPX_PHASE_PROF
 // out: 48 words: g_phase, then the frame kernel's phases (g_frame_phase summed over its stripes)
