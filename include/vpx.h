@@ -35,6 +35,9 @@
  *   vpx_reproject_ids / vpx_reproject_ids_host   no reference counterpart; temporal accumulation
  *                              under camera motion, its rejection test the vpx_render_ids record
  *                              (Camera::PointToUV template/camera.h:34-49, TransformPosition tmpl8math.cpp:345-353)
+ *   vpx_reproject_moments / vpx_denoise_var (+ _host)   no reference counterpart; the luminance's first
+ *                              two moments through the reprojection, and the a-trous filter with a
+ *                              per-pixel tolerance from their variance
  *   vpx_get_player_light  Renderer::inLight           renderer.h:231; set renderer.cpp:1228-1240,
  *                                                     1438-1450; read :2112-2118, cleared :2206
  *   vpx_trace_probe       Trace's smoke-branch probe  renderer.cpp:1228-1240 (per ray)
@@ -880,6 +883,79 @@ int vpx_reproject_ids(vpx_ctx* ctx, const vpx_frame_params* p /* only width, hei
 int vpx_reproject_ids_host(uint32_t width, uint32_t height, const uint32_t* ids_cur, const uint32_t* ids_prev,
                            const float* cur, const float* hist_in, float* hist_out, uint32_t* rgb8 /* may be NULL */,
                            const vpx_reproject* r, const vpx_volume* cur_volumes, const vpx_volume* prev_volumes);
+/* Variance-guided denoise: vpx_reproject_ids carrying the first two moments of the luminance, and
+   vpx_denoise_ids with a per-pixel luminance tolerance derived from them (SVGF's structure; no
+   reference counterpart).  The edge test stays the integer plane key; only the one soft weight
+   becomes local: a shadow edge on a floor whose history says "this pixel does not vary" is kept,
+   where a global sigma_l would either leave the noise in or smear it.  lum and Key are
+   vpx_denoise_ids'; every operation rounds once to float32, products before sums, nothing
+   contracted, / and sqrtf correctly rounded; the results are defined bit for bit (NaN payloads apart).
+
+   vpx_reproject_moments: hist_out and rgb8 are vpx_reproject_ids' for the same arguments, bit for
+   bit.  In addition, per pixel q with l = lum(cur.rgb), l2 = l * l:
+     no history (every case in which vpx_reproject_ids gives (cur.rgb, 1)): mom_out = (l, l2);
+     history: over the same usable taps, in the same order, with the same weights,
+       s1 = s1 + w * mom_in[r].x, s2 = s2 + w * mom_in[r].y; h1 = s1 / ws, h2 = s2 / ws; with the
+       blend's a = 1.0f / n: mom_out = (h1 + (l - h1) * a, h2 + (l2 - h2) * a).
+   mom_in[r] is read only under a usable tap.  Stream order, counters, device sets and the scratch
+   (shared) are vpx_reproject_ids'.  VPX_E_INVALID: vpx_reproject_ids' refusals; a null mom_out;
+   exactly one of mom_in / hist_in null; mom_out equal to any input or to hist_out; hist_out equal
+   to mom_in.  Feed mom_out back as the next mom_in, beside hist_out.
+
+   vpx_denoise_var: `in` is a float4 image; with mom != NULL its .w is the history length
+   (vpx_reproject_moments' hist_out), else .w is only carried through.
+   Step V, the variance estimate.  A pixel q with an invalid key: var0 = 0.  Else the moments of a
+   pixel r are (m1, m2)(r) = mom[r], or (lum(in[r]), lum(in[r]) * lum(in[r])) when mom == NULL, and
+     temporal arm (mom != NULL and in[q].w >= min_history; a NaN fails): v = m2(q) - m1(q) * m1(q);
+     spatial arm (otherwise): over the taps (x + i, y + j), j = -2..2 outer, i = -2..2 inner, inside
+       the image and carrying q's key: s1 = s1 + m1(r), s2 = s2 + m2(r), cnt = cnt + 1.0f; then
+       mean = s1 / cnt, v = s2 / cnt - mean * mean;
+     var0(q) = v > 0.0f ? v : 0.0f (a NaN gives 0).
+   Pass p (step s = 1 << p) reads image S and variance var, writes D and var'.  An invalid key keeps
+   S(q) and var(q).  Otherwise:
+     prefilter (sets the weight only): over the 3x3 taps at distance 1 (never dilated), j outer, i
+       inner, inside the image and carrying q's key: g = G[|j|] * G[|i|], G = {0.5, 0.25};
+       gs = gs + g * var(r), gw = gw + g; gv = gs / gw; tol = sigma_v * sqrtf(gv) + epsilon;
+       inv = 1.0f / tol;
+     taps: vpx_denoise_ids' 25 taps, same order, matching, same base weight h:
+       dd = (lum(S(r)) - lum(S(q))) * inv; w = h / (1.0f + dd * dd); acc = acc + w * S(r) per
+       channel; wsum = wsum + w; vacc = vacc + (w * w) * var(r);
+     D(q).rgb = acc / wsum, var'(q) = vacc / (wsum * wsum).
+   The last pass writes out = (D.rgb, in.w) and, when rgb8 is not NULL, its tonemap in the same
+   launch.  A tap that does not match is never read into the arithmetic, colour and variance alike.
+   Order, counters, device sets as vpx_denoise_ids; the scratch (keys and two float4 images whose
+   .w is the variance) belongs to the context and grows with the size: VPX_E_NOMEM when that
+   fails.  VPX_E_INVALID: vpx_denoise_ids' size and pointer refusals; passes outside 1..5; sigma_v
+   or epsilon not finite and positive; min_history not integer-valued in 1..65536; nonzero flags or
+   reserved; out == in, out == ids or out == mom.
+   Limits: vpx_denoise_ids'; and a lighting change that the history has not seen yet reads as
+   variance for max_history frames, which widens the tolerance there: the safe side. */
+typedef struct vpx_denoise_var_params {  /* 32 bytes */
+    uint32_t passes;              /* 1..5: steps 1, 2, 4, 8, 16 */
+    float    sigma_v;             /* finite, > 0: the tolerance in standard deviations */
+    float    epsilon;             /* finite, > 0: added to the tolerance (keeps dd finite at zero variance) */
+    float    min_history;         /* integer-valued, 1..65536: in.w >= this takes the temporal variance */
+    uint32_t flags;               /* 0 */
+    uint32_t reserved[3];         /* 0 */
+} vpx_denoise_var_params;
+int vpx_reproject_moments(vpx_ctx* ctx, const vpx_frame_params* p /* only width, height */,
+                          const uint32_t* ids_cur, const uint32_t* ids_prev, const float* cur, const float* hist_in,
+                          const float* mom_in /* float2[W*H], DEVICE; NULL with hist_in */,
+                          float* hist_out, float* mom_out /* float2[W*H], DEVICE */, uint32_t* rgb8 /* may be NULL */,
+                          const vpx_reproject* r, const vpx_volume* cur_volumes, const vpx_volume* prev_volumes);
+int vpx_reproject_moments_host(uint32_t width, uint32_t height, const uint32_t* ids_cur, const uint32_t* ids_prev,
+                               const float* cur, const float* hist_in, const float* mom_in, float* hist_out,
+                               float* mom_out, uint32_t* rgb8 /* may be NULL */, const vpx_reproject* r,
+                               const vpx_volume* cur_volumes, const vpx_volume* prev_volumes);
+int vpx_denoise_var(vpx_ctx* ctx, const vpx_frame_params* p /* only width, height */,
+                    const uint32_t* ids /* uint4[W*H], DEVICE */,
+                    const float* in /* float4[W*H], DEVICE; .w = history length when mom != NULL */,
+                    const float* mom /* float2[W*H], DEVICE, may be NULL */, float* out /* float4[W*H], DEVICE */,
+                    uint32_t* rgb8 /* uint32[W*H], DEVICE, may be NULL */, const vpx_denoise_var_params* d);
+/* The same two on host memory (no device, no context): the CPU paths of the same code
+   (csrc/vpx_denoise_var.hpp, csrc/vpx_reproject.hpp).  VPX_E_NOMEM when the scratch cannot be allocated. */
+int vpx_denoise_var_host(uint32_t width, uint32_t height, const uint32_t* ids, const float* in, const float* mom,
+                         float* out, uint32_t* rgb8 /* may be NULL */, const vpx_denoise_var_params* d);
 /* Focus ray of Renderer::Tick (world-space ray against every Scene::FindNearest). */
 int vpx_focus_distance(vpx_ctx* ctx, uint32_t width, uint32_t height, float* focal_distance);
 

@@ -129,6 +129,16 @@ class Denoise(C.Structure):  # vpx_denoise: passes 1..5 (steps 1..16), sigma_l (
     _fields_ = [("passes", C.c_uint32), ("sigma_l", C.c_float), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class DenoiseVar(C.Structure):  # vpx_denoise_var: passes 1..5, the tolerance in standard deviations, its floor, the arm's threshold
+    _fields_ = [("passes", C.c_uint32), ("sigma_v", C.c_float), ("epsilon", C.c_float), ("min_history", C.c_float),
+                ("flags", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
+def denoise_var(passes=5, sigma_v=4.0, epsilon=2.0**-10, min_history=4):
+    """abi.DenoiseVar with Renderer's defaults."""
+    return DenoiseVar(int(passes), float(sigma_v), float(epsilon), float(min_history), 0, (C.c_uint32 * 3)(0, 0, 0))
+
+
 LOAD_FULL, LOAD_PARTIAL, LOAD_RANDOM = 0, 1, 2  # VPX_LOAD_*: Scene::LoadModel / LoadModelPartial / LoadModelRandomMaterials
 
 
@@ -210,7 +220,8 @@ STAGES = ("primary", "shade", "shadow", "resolve", "bounce", "finish", "frame", 
 STRUCT_SIZES = {PrevCamera: 64, Profile: 160, Volume: 160, Material: 32, PointLight: 24, SpotLight: 40, AreaLight: 32, DirLight: 24,
                 Sphere: 32, Triangle: 64, Camera: 80, FrameParams: 48, Ray: 32, Hit: 32, Stats: 40,
                 BvhTri: 36, BvhNode: 32, PlayerLight: 24, RayProbe: 16, RayFilter: 16, HitCell: 32, ModelLoad: 40, ModelResult: 16,
-                NoiseGen: 16, NoiseResult: 16, Brush: 48, BrushResult: 16, Denoise: 16, Cast: 16, Reproject: 168}
+                NoiseGen: 16, NoiseResult: 16, Brush: 48, BrushResult: 16, Denoise: 16, Cast: 16, Reproject: 168,
+                DenoiseVar: 32}
 
 
 def np_dtype(struct):
@@ -303,6 +314,12 @@ SIGNATURES = {
                           [C.POINTER(Reproject), C.POINTER(Volume), C.POINTER(Volume)]),
     "vpx_reproject_ids_host": (C.c_int, [C.c_uint32, C.c_uint32] + [C.c_void_p] * 6 +
                                [C.POINTER(Reproject), C.POINTER(Volume), C.POINTER(Volume)]),
+    "vpx_reproject_moments": (C.c_int, [C.c_void_p, C.POINTER(FrameParams)] + [C.c_void_p] * 8 +
+                              [C.POINTER(Reproject), C.POINTER(Volume), C.POINTER(Volume)]),
+    "vpx_reproject_moments_host": (C.c_int, [C.c_uint32, C.c_uint32] + [C.c_void_p] * 8 +
+                                   [C.POINTER(Reproject), C.POINTER(Volume), C.POINTER(Volume)]),
+    "vpx_denoise_var": (C.c_int, [C.c_void_p, C.POINTER(FrameParams)] + [C.c_void_p] * 5 + [C.POINTER(DenoiseVar)]),
+    "vpx_denoise_var_host": (C.c_int, [C.c_uint32, C.c_uint32] + [C.c_void_p] * 5 + [C.POINTER(DenoiseVar)]),
     "vpx_focus_distance": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_float)]),
     "vpx_camera_look_at": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_uint32, C.c_uint32,
                                      C.POINTER(Camera)]),

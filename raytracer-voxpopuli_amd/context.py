@@ -476,6 +476,49 @@ class Context:
     def reproject_host(self, width, height, ids_cur, ids_prev, cur, hist_in, camera, prev_camera, **kw):
         return reproject_host(width, height, ids_cur, ids_prev, cur, hist_in, camera, prev_camera, lib=self.lib, **kw)
 
+    def reproject_moments(self, params, ids_cur, ids_prev, cur, hist_in, mom_in, camera, prev_camera, out=None,
+                          mom_out=None, max_history=32, nohist=(1, 0), cur_volumes=None, prev_volumes=None, rgb_ptr=None):
+        """vpx_reproject_moments: reproject() carrying the luminance's first two moments along.
+        mom_in: float32 torch tensor of 2 * W * H (None together with hist_in).  Returns (out, mom_out),
+        allocated when None; never an input."""
+        import torch
+
+        if out is None:
+            out = torch.empty_like(cur)
+        if mom_out is None:
+            mom_out = torch.empty(cur.numel() // 2, dtype=torch.float32, device=cur.device)
+        r, cv, pv = reproject_desc(camera, prev_camera, max_history, nohist, cur_volumes, prev_volumes)
+        ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None else 0)  # noqa: E731
+        self._chk(self.lib.vpx_reproject_moments(self.h, C.byref(params), ptr(ids_cur), ptr(ids_prev), ptr(cur),
+                                                 ptr(hist_in), ptr(mom_in), ptr(out), ptr(mom_out),
+                                                 C.c_void_p(rgb_ptr or 0), C.byref(r), cv, pv), "vpx_reproject_moments")
+        return out, mom_out
+
+    def reproject_moments_host(self, width, height, ids_cur, ids_prev, cur, hist_in, mom_in, camera, prev_camera, **kw):
+        return reproject_moments_host(width, height, ids_cur, ids_prev, cur, hist_in, mom_in, camera, prev_camera,
+                                      lib=self.lib, **kw)
+
+    def denoise_var(self, params, ids, src, mom=None, out=None, passes=5, sigma_v=4.0, epsilon=2.0**-10, min_history=4,
+                    rgb_ptr=None):
+        """vpx_denoise_var: denoise() with a per-pixel luminance tolerance of sigma_v standard
+        deviations (+ epsilon).  mom: reproject_moments' moments tensor (then src.w is the history
+        length and pixels with at least min_history frames take their temporal variance), or None
+        (the variance of the 5x5 neighbourhood on the pixel's plane).  Returns `out` (allocated like
+        src when None; never src itself).  Runs on the context's stream, unsynchronised."""
+        import torch
+
+        if out is None:
+            out = torch.empty_like(src)
+        d = abi.denoise_var(passes, sigma_v, epsilon, min_history)
+        self._chk(self.lib.vpx_denoise_var(self.h, C.byref(params), C.c_void_p(ids.data_ptr()), C.c_void_p(src.data_ptr()),
+                                           C.c_void_p(mom.data_ptr() if mom is not None else 0),
+                                           C.c_void_p(out.data_ptr()), C.c_void_p(rgb_ptr or 0), C.byref(d)),
+                  "vpx_denoise_var")
+        return out
+
+    def denoise_var_host(self, width, height, ids, src, mom=None, **kw):
+        return denoise_var_host(width, height, ids, src, mom, lib=self.lib, **kw)
+
     def trace(self, rays, seeds, depth, sky=abi.SKY_DEFAULT, area_samples=3):
         """Renderer::Trace per ray; sky=None samples the sky texture (activateSky)."""
         n = len(rays)
@@ -616,4 +659,43 @@ def reproject_host(width, height, ids_cur, ids_prev, cur, hist_in, camera, prev_
     abi.check(lib, None, lib.vpx_reproject_ids_host(w, h, abi.as_ptr(ic), abi.as_ptr(ip), abi.as_ptr(c), abi.as_ptr(hi),
                                                     abi.as_ptr(out), abi.as_ptr(rgb8), C.byref(r), cv, pv),
               "vpx_reproject_ids_host")
+    return (out, rgb8) if rgb else out
+
+
+def reproject_moments_host(width, height, ids_cur, ids_prev, cur, hist_in, mom_in, camera, prev_camera, max_history=32,
+                           nohist=(1, 0), cur_volumes=None, prev_volumes=None, rgb=False, lib=None):
+    """vpx_reproject_moments_host: reproject_host carrying the moments (mom_in: float32 [H, W, 2], None
+    together with hist_in).  Returns (hist_out [H, W, 4], mom_out [H, W, 2]), and rgb8 [H, W] with
+    rgb=True."""
+    lib = lib or abi.load_library()
+    w, h = int(width), int(height)
+    ids = lambda a: None if a is None else np.ascontiguousarray(a).view(np.uint32).reshape(h, w, 4)  # noqa: E731
+    img = lambda a, k=4: None if a is None else np.ascontiguousarray(a, np.float32).reshape(h, w, k)  # noqa: E731
+    ic, ip, c, hi, mi = ids(ids_cur), ids(ids_prev), img(cur), img(hist_in), img(mom_in, 2)
+    out = np.empty_like(c)
+    mom_out = np.empty((h, w, 2), np.float32)
+    rgb8 = np.empty((h, w), np.uint32) if rgb else None
+    r, cv, pv = reproject_desc(camera, prev_camera, max_history, nohist, cur_volumes, prev_volumes)
+    abi.check(lib, None, lib.vpx_reproject_moments_host(w, h, abi.as_ptr(ic), abi.as_ptr(ip), abi.as_ptr(c), abi.as_ptr(hi),
+                                                        abi.as_ptr(mi), abi.as_ptr(out), abi.as_ptr(mom_out),
+                                                        abi.as_ptr(rgb8), C.byref(r), cv, pv),
+              "vpx_reproject_moments_host")
+    return (out, mom_out, rgb8) if rgb else (out, mom_out)
+
+
+def denoise_var_host(width, height, ids, src, mom=None, passes=5, sigma_v=4.0, epsilon=2.0**-10, min_history=4, rgb=False,
+                     lib=None):
+    """vpx_denoise_var_host: the variance-guided filter on numpy arrays, no device.  ids: uint32
+    [H, W, 4], src: float32 [H, W, 4], mom: float32 [H, W, 2] or None.  Returns out [H, W, 4], or
+    (out, rgb8 [H, W]) with rgb=True."""
+    lib = lib or abi.load_library()
+    w, h = int(width), int(height)
+    i = np.ascontiguousarray(ids).view(np.uint32).reshape(h, w, 4)
+    s = np.ascontiguousarray(src, np.float32).reshape(h, w, 4)
+    m = None if mom is None else np.ascontiguousarray(mom, np.float32).reshape(h, w, 2)
+    out = np.empty_like(s)
+    rgb8 = np.empty((h, w), np.uint32) if rgb else None
+    d = abi.denoise_var(passes, sigma_v, epsilon, min_history)
+    abi.check(lib, None, lib.vpx_denoise_var_host(w, h, abi.as_ptr(i), abi.as_ptr(s), abi.as_ptr(m), abi.as_ptr(out),
+                                                  abi.as_ptr(rgb8), C.byref(d)), "vpx_denoise_var_host")
     return (out, rgb8) if rgb else out

@@ -16,6 +16,7 @@
 #include "vpx_noise.hpp"
 #include "vpx_brush.hpp"
 #include "vpx_denoise.hpp"
+#include "vpx_denoise_var.hpp"
 #include "vpx_reproject.hpp"
 #include "vpx_skip.hpp"
 
@@ -640,5 +641,43 @@ int vpx_reproject_ids_host(uint32_t width, uint32_t height, const uint32_t* ids_
 }
 
 static_assert(sizeof(vpx_reproject) == 168, "reproject layout");
+
+// vpx_reproject_moments on host memory: the same loop with reproject::pixel's moments payload.
+int vpx_reproject_moments_host(uint32_t width, uint32_t height, const uint32_t* ids_cur, const uint32_t* ids_prev,
+                               const float* cur, const float* hist_in, const float* mom_in, float* hist_out,
+                               float* mom_out, uint32_t* rgb8, const vpx_reproject* r, const vpx_volume* cur_volumes,
+                               const vpx_volume* prev_volumes) {
+    if (vpx::reproject::check_call_moments(width, height, ids_cur, ids_prev, cur, hist_in, mom_in, hist_out, mom_out, r,
+                                           cur_volumes, prev_volumes))
+        return VPX_E_INVALID;
+    try {
+        std::vector<float> tab((size_t)r->n_volumes * vpx::reproject::kTabFloats);
+        std::vector<uint32_t> moved(r->n_volumes);
+        vpx::reproject::build_table(r->n_volumes, cur_volumes, prev_volumes, tab.data(), moved.data());
+        vpx::reproject::run_host_moments(width, height, ids_cur, ids_prev, cur, hist_in, mom_in, hist_out, mom_out, rgb8, *r,
+                                         tab.data(), moved.data());
+    } catch (const std::bad_alloc&) {
+        return VPX_E_NOMEM;
+    }
+    return VPX_OK;
+}
+
+// vpx_denoise_var on host memory: vpx_denoise_var.hpp's host loops, the code the kernels share.
+int vpx_denoise_var_host(uint32_t width, uint32_t height, const uint32_t* ids, const float* in, const float* mom,
+                         float* out, uint32_t* rgb8, const vpx_denoise_var_params* d) {
+    if (vpx::denoise_var::check_call(width, height, ids, in, mom, out, d)) return VPX_E_INVALID;
+    const size_t pixels = (size_t)width * height;
+    try {
+        std::vector<vpx::denoise::Key> keys(pixels);
+        std::vector<float> scratch((d->passes > 1 ? 8 : 4) * pixels);
+        vpx::denoise_var::run_host(width, height, ids, in, mom, out, rgb8, *d, keys.data(), scratch.data(),
+                                   scratch.data() + (d->passes > 1 ? 4 * pixels : 0));
+    } catch (const std::bad_alloc&) {
+        return VPX_E_NOMEM;
+    }
+    return VPX_OK;
+}
+
+static_assert(sizeof(vpx_denoise_var_params) == 32, "denoise_var layout");
 
 }  // extern "C"

@@ -15,6 +15,8 @@
 //   brush_k                       one brush edit (vpx_brush.hpp).
 //   k_plane_key / k_atrous_lds / k_atrous_gather   the plane-keyed denoise (vpx_denoise.hpp).
 //   k_reproject_ids               the plane-keyed temporal reprojection (vpx_reproject.hpp).
+//   k_reproject_moments / k_var_estimate / k_atrous_var_lds / k_atrous_var_gather   the variance-guided
+//                                 denoise: moments through the reprojection (vpx_denoise_var.hpp).
 //   refresh_l1_k / df_mark_k / df_diag_k / df_planes_box_k / axis_box_k / wide_box_k   the
 //                                 region-local level refresh after an edit (refresh_levels).
 #include <hip/hip_runtime.h>
@@ -38,6 +40,7 @@
 #include "vpx_noise.hpp"
 #include "vpx_brush.hpp"
 #include "vpx_denoise.hpp"
+#include "vpx_denoise_var.hpp"
 #include "vpx_reproject.hpp"
 
 using namespace vpx;
@@ -713,6 +716,202 @@ void launch_atrous(hipStream_t st, uint32_t tiles, const DenoiseArgs& a, const u
     hipLaunchKernelGGL((k_atrous_gather<LUM>), dim3(tiles), dim3(kThreads), 0, st, a, keys, src, dst, rgb8);
 }
 
+// ------------------------------------------------------------------ variance-guided denoise
+// vpx_denoise_var (vpx_denoise_var.hpp holds the definition and the arithmetic).  The images of the
+// passes are float4 whose .w is the variance, so a tap is one 16-byte load and the LDS tiles are
+// k_atrous_lds' (keys + float4); the prefilter's 3x3 lies inside the halo (R >= 2).  Only the last
+// pass (restore != NULL) puts in.w back.
+struct DenoiseVarArgs {
+    uint32_t width, height, tiles_x;
+    int32_t step;
+    float sigma_v, epsilon, min_history;
+};
+
+// Step V: V0 = (in.rgb, var0).  The temporal arm reads the pixel's own moments; the spatial arm
+// gathers the 5x5 neighbourhood: the keys first, from clamped addresses, folded into a match
+// mask, then the moments of the matching taps only (mom, or the luminance of `in`).
+template <bool MOM>
+__global__ __launch_bounds__(kThreads) void k_var_estimate(DenoiseVarArgs a, const uint2* __restrict__ keys,
+                                                           const float4* __restrict__ in,
+                                                           const float2* __restrict__ mom, float4* __restrict__ V0) {
+    const int x = (int)(blockIdx.x % a.tiles_x) * kTile + (int)(threadIdx.x & 15);
+    const int y = (int)(blockIdx.x / a.tiles_x) * kTile + (int)(threadIdx.x >> 4);
+    const int W = (int)a.width, H = (int)a.height;
+    if (x >= W || y >= H) return;
+    const uint64_t q = (uint64_t)y * a.width + (uint32_t)x;
+    const uint2 kq = keys[q];
+    const float4 cq = in[q];
+    float var = 0.0f;
+    auto moments = [&](uint64_t r) {
+        if (MOM) {
+            const float2 m = mom[r];
+            return denoise_var::Mom{m.x, m.y};
+        }
+        const float4 c = in[r];
+        return denoise_var::self_moments(c.x, c.y, c.z);
+    };
+    if (kq.y) {
+        if (MOM && cq.w >= a.min_history) {
+            var = denoise_var::temporal_var(moments(q));
+        } else {
+            uint32_t match = 0u;
+#pragma unroll
+            for (int j = -2; j <= 2; ++j)
+#pragma unroll
+                for (int i = -2; i <= 2; ++i) {
+                    const int rx = x + i, ry = y + j;
+                    const bool inside = rx >= 0 && ry >= 0 && rx < W && ry < H;
+                    const int cx = min(max(rx, 0), W - 1), cy = min(max(ry, 0), H - 1);
+                    const uint2 k = keys[(uint64_t)cy * a.width + (uint32_t)cx];
+                    match |= (uint32_t)(inside && k.x == kq.x && k.y == kq.y) << ((j + 2) * 5 + i + 2);
+                }
+            denoise_var::Spatial s;
+#pragma unroll
+            for (int j = -2; j <= 2; ++j)
+#pragma unroll
+                for (int i = -2; i <= 2; ++i)
+                    if (match >> ((j + 2) * 5 + i + 2) & 1u)  // in the image: the mask says so
+                        denoise_var::spatial_tap(s, moments((uint64_t)(y + j) * a.width + (uint32_t)(x + i)));
+            var = denoise_var::spatial_var(s);
+        }
+    }
+    V0[q] = make_float4(cq.x, cq.y, cq.z, var);
+}
+
+__device__ __forceinline__ void denoise_var_store(uint64_t q, float4 o, float4* __restrict__ D,
+                                                  const float4* __restrict__ restore, uint32_t* __restrict__ rgb8) {
+    if (restore) o.w = restore[q].w;  // the last pass only
+    D[q] = o;
+    if (rgb8) rgb8[q] = tonemap_pack(o);
+}
+
+// Steps 1 and 2: k_atrous_lds' staging (tile + halo of 2 * STEP pixels, keys and float4s).
+template <int STEP>
+__global__ __launch_bounds__(kThreads) void k_atrous_var_lds(DenoiseVarArgs a, const uint2* __restrict__ keys,
+                                                             const float4* __restrict__ S, float4* __restrict__ D,
+                                                             const float4* __restrict__ restore,
+                                                             uint32_t* __restrict__ rgb8) {
+    constexpr int R = 2 * STEP, DIM = kTile + 2 * R;
+    __shared__ uint2 lk[DIM * DIM];
+    __shared__ float4 lc[DIM * DIM];
+    const int tx0 = (int)(blockIdx.x % a.tiles_x) * kTile, ty0 = (int)(blockIdx.x / a.tiles_x) * kTile;
+    for (int e = threadIdx.x; e < DIM * DIM; e += kThreads) {
+        const int gx = tx0 - R + e % DIM, gy = ty0 - R + e / DIM;
+        uint2 k = make_uint2(0u, 0u);
+        if (gx >= 0 && gy >= 0 && gx < (int)a.width && gy < (int)a.height) {
+            const uint64_t p = (uint64_t)gy * a.width + (uint32_t)gx;
+            k = keys[p];
+            if (k.y) lc[e] = S[p];
+        }
+        lk[e] = k;
+    }
+    __syncthreads();
+    const int lx = threadIdx.x & 15, ly = threadIdx.x >> 4;
+    const uint32_t x = tx0 + lx, y = ty0 + ly;
+    if (x >= a.width || y >= a.height) return;
+    const uint64_t q = (uint64_t)y * a.width + x;
+    const int eq = (ly + R) * DIM + lx + R;
+    const uint2 kq = lk[eq];
+    if (!kq.y) {
+        denoise_var_store(q, S[q], D, restore, rgb8);
+        return;
+    }
+    denoise_var::Pre pre;
+#pragma unroll
+    for (int j = -1; j <= 1; ++j)
+#pragma unroll
+        for (int i = -1; i <= 1; ++i) {
+            const int e = eq + j * DIM + i;
+            const uint2 k = lk[e];
+            if (k.x == kq.x && k.y == kq.y) denoise_var::pre_tap(pre, denoise_var::pre_weight(j, i), lc[e].w);
+        }
+    const float inv = denoise_var::inv_tolerance(pre, a.sigma_v, a.epsilon);
+    const float4 cq = lc[eq];
+    const float lq = denoise::lum(cq.x, cq.y, cq.z);
+    denoise_var::Sum s;
+#pragma unroll
+    for (int j = -2; j <= 2; ++j)
+#pragma unroll
+        for (int i = -2; i <= 2; ++i) {
+            const int e = eq + j * STEP * DIM + i * STEP;
+            const uint2 k = lk[e];
+            if (k.x == kq.x && k.y == kq.y) {
+                const float4 c = lc[e];
+                denoise_var::tap(s, denoise::base_weight(j, i), c.x, c.y, c.z, c.w, lq, inv);
+            }
+        }
+    denoise_var_store(q, make_float4(s.r / s.w, s.g / s.w, s.b / s.w, denoise_var::out_var(s)), D, restore, rgb8);
+}
+
+// Steps 4 and up: k_atrous_gather's key-mask-then-colour scheme, plus the nine step-1 taps of the
+// prefilter (their keys into a second mask, then 4 bytes of variance under a matching one).
+__global__ __launch_bounds__(kThreads) void k_atrous_var_gather(DenoiseVarArgs a, const uint2* __restrict__ keys,
+                                                                const float4* __restrict__ S, float4* __restrict__ D,
+                                                                const float4* __restrict__ restore,
+                                                                uint32_t* __restrict__ rgb8) {
+    const int x = (int)(blockIdx.x % a.tiles_x) * kTile + (int)(threadIdx.x & 15);
+    const int y = (int)(blockIdx.x / a.tiles_x) * kTile + (int)(threadIdx.x >> 4);
+    const int W = (int)a.width, H = (int)a.height;
+    if (x >= W || y >= H) return;
+    const uint64_t q = (uint64_t)y * a.width + (uint32_t)x;
+    const uint2 kq = keys[q];
+    const float4 cq = S[q];
+    if (!kq.y) {
+        denoise_var_store(q, cq, D, restore, rgb8);
+        return;
+    }
+    uint32_t match = 0u, near = 0u;
+#pragma unroll
+    for (int j = -2; j <= 2; ++j)
+#pragma unroll
+        for (int i = -2; i <= 2; ++i) {
+            const int rx = x + i * a.step, ry = y + j * a.step;
+            const bool inside = rx >= 0 && ry >= 0 && rx < W && ry < H;
+            const int cx = min(max(rx, 0), W - 1), cy = min(max(ry, 0), H - 1);
+            const uint2 k = keys[(uint64_t)cy * a.width + (uint32_t)cx];
+            match |= (uint32_t)(inside && k.x == kq.x && k.y == kq.y) << ((j + 2) * 5 + i + 2);
+        }
+#pragma unroll
+    for (int j = -1; j <= 1; ++j)
+#pragma unroll
+        for (int i = -1; i <= 1; ++i) {
+            const int rx = x + i, ry = y + j;
+            const bool inside = rx >= 0 && ry >= 0 && rx < W && ry < H;
+            const int cx = min(max(rx, 0), W - 1), cy = min(max(ry, 0), H - 1);
+            const uint2 k = keys[(uint64_t)cy * a.width + (uint32_t)cx];
+            near |= (uint32_t)(inside && k.x == kq.x && k.y == kq.y) << ((j + 1) * 3 + i + 1);
+        }
+    denoise_var::Pre pre;
+#pragma unroll
+    for (int j = -1; j <= 1; ++j)
+#pragma unroll
+        for (int i = -1; i <= 1; ++i)
+            if (near >> ((j + 1) * 3 + i + 1) & 1u)
+                denoise_var::pre_tap(pre, denoise_var::pre_weight(j, i), S[(uint64_t)(y + j) * a.width + (uint32_t)(x + i)].w);
+    const float inv = denoise_var::inv_tolerance(pre, a.sigma_v, a.epsilon);
+    const float lq = denoise::lum(cq.x, cq.y, cq.z);
+    denoise_var::Sum s;
+#pragma unroll
+    for (int j = -2; j <= 2; ++j)
+#pragma unroll
+        for (int i = -2; i <= 2; ++i)
+            if (match >> ((j + 2) * 5 + i + 2) & 1u) {  // in the image: the mask says so
+                const float4 c = S[(uint64_t)(y + j * a.step) * a.width + (uint32_t)(x + i * a.step)];
+                denoise_var::tap(s, denoise::base_weight(j, i), c.x, c.y, c.z, c.w, lq, inv);
+            }
+    denoise_var_store(q, make_float4(s.r / s.w, s.g / s.w, s.b / s.w, denoise_var::out_var(s)), D, restore, rgb8);
+}
+
+void launch_atrous_var(hipStream_t st, uint32_t tiles, const DenoiseVarArgs& a, const uint2* keys, const float4* src,
+                       float4* dst, const float4* restore, uint32_t* rgb8) {
+    if (a.step == 1)
+        hipLaunchKernelGGL((k_atrous_var_lds<1>), dim3(tiles), dim3(kThreads), 0, st, a, keys, src, dst, restore, rgb8);
+    else if (a.step == 2)
+        hipLaunchKernelGGL((k_atrous_var_lds<2>), dim3(tiles), dim3(kThreads), 0, st, a, keys, src, dst, restore, rgb8);
+    else
+        hipLaunchKernelGGL(k_atrous_var_gather, dim3(tiles), dim3(kThreads), 0, st, a, keys, src, dst, restore, rgb8);
+}
+
 // ------------------------------------------------------------------ plane-keyed reprojection
 // vpx_reproject_ids (vpx_reproject.hpp holds the definition and the arithmetic: reproject::pixel).
 // One lane per pixel, a 16x16 tile per workgroup, lane t at (t & 15, t >> 4) as the denoise; the
@@ -761,6 +960,64 @@ void launch_reproject(hipStream_t st, uint32_t tiles, const reproject::Args& a, 
                       const float* tab, const uint32_t* moved) {
     hipLaunchKernelGGL((k_reproject_ids<MOVING, RGB8, VPX_REPROJECT_PREKEY != 0>), dim3(tiles), dim3(kThreads), 0, st, a,
                        tiles_x, ids_cur, prev, cur, hist_in, hist_out, rgb8, tab, moved);
+}
+
+// vpx_reproject_moments: k_reproject_ids with reproject::pixel's moments payload, 8 bytes more per
+// usable tap and one 8-byte store more per pixel.
+struct DeviceMoments {
+    static constexpr bool on = true;
+    const float2* m;
+    __device__ __forceinline__ reproject::Mom operator()(uint64_t i) const {
+        const float2 v = m[i];
+        return reproject::Mom{v.x, v.y};
+    }
+};
+template <bool MOVING, bool RGB8, bool PREKEY>
+__global__ __launch_bounds__(kThreads) void k_reproject_moments(reproject::Args a, uint32_t tiles_x,
+                                                                const uint4* __restrict__ ids_cur,
+                                                                const void* __restrict__ prev,
+                                                                const float4* __restrict__ cur,
+                                                                const float4* __restrict__ hist_in,
+                                                                const float2* __restrict__ mom_in,
+                                                                float4* __restrict__ hist_out,
+                                                                float2* __restrict__ mom_out, uint32_t* __restrict__ rgb8,
+                                                                const float* __restrict__ tab,
+                                                                const uint32_t* __restrict__ moved) {
+    const uint32_t x = (blockIdx.x % tiles_x) * kTile + (threadIdx.x & 15u);
+    const uint32_t y = (blockIdx.x / tiles_x) * kTile + (threadIdx.x >> 4);
+    if (x >= a.width || y >= a.height) return;
+    const uint64_t q = (uint64_t)y * a.width + x;
+    const uint4 id = ids_cur[q];
+    const float4 c = cur[q];
+    auto prev_key = [prev](uint64_t i) {
+        if (PREKEY) {
+            const uint2 k = reinterpret_cast<const uint2*>(prev)[i];
+            return denoise::Key{k.x, k.y};
+        }
+        const uint4 r = reinterpret_cast<const uint4*>(prev)[i];
+        return denoise::plane_key(r.y, r.z, r.w);
+    };
+    auto hist = [hist_in](uint64_t i) {
+        const float4 h = hist_in[i];
+        return reproject::Rgbw{h.x, h.y, h.z, h.w};
+    };
+    reproject::Mom mo{0.f, 0.f};
+    const reproject::Rgbw o = reproject::pixel<MOVING>(a, x, y, reproject::Id{id.x, id.y, id.z, id.w},
+                                                       reproject::Rgbw{c.x, c.y, c.z, c.w}, prev_key, hist, tab, moved,
+                                                       DeviceMoments{mom_in}, mo);
+    const float4 out = make_float4(o.r, o.g, o.b, o.w);
+    hist_out[q] = out;
+    mom_out[q] = make_float2(mo.x, mo.y);
+    if (RGB8) rgb8[q] = tonemap_pack(out);
+}
+
+template <bool MOVING, bool RGB8>
+void launch_reproject_moments(hipStream_t st, uint32_t tiles, const reproject::Args& a, uint32_t tiles_x,
+                              const uint4* ids_cur, const void* prev, const float4* cur, const float4* hist_in,
+                              const float2* mom_in, float4* hist_out, float2* mom_out, uint32_t* rgb8, const float* tab,
+                              const uint32_t* moved) {
+    hipLaunchKernelGGL((k_reproject_moments<MOVING, RGB8, VPX_REPROJECT_PREKEY != 0>), dim3(tiles), dim3(kThreads), 0, st,
+                       a, tiles_x, ids_cur, prev, cur, hist_in, mom_in, hist_out, mom_out, rgb8, tab, moved);
 }
 
 // BasicBVH::IntersectBVH (src/BVH/BasicBVH.cpp:19-70), one ray per lane.  The workgroup
@@ -1751,6 +2008,9 @@ struct vpx_ctx {
     // vpx_denoise_ids' scratch: the keys (uint2 per pixel), then two float4 images when a call
     // ran more than one pass; carved per call for the call's size
     Owned<void> dn_buf;
+    // vpx_denoise_var's scratch: the keys, then one float4 image (V0) and a second when a call ran
+    // more than one pass, .w the variance; carved per call for the call's size
+    Owned<void> dv_buf;
     // vpx_reproject_ids' scratch: the volume table (24 floats per volume, then a moved flag per
     // volume) and, in the VPX_REPROJECT_PREKEY form, the previous keys; rj_host: the table's pinned
     // staging copy, rewritten only after rj_ev (its last upload) has passed; rj_last: the table the
@@ -4035,6 +4295,55 @@ static int reproject_table(vpx_ctx* c, uint32_t n, const vpx_volume* cur_volumes
     return VPX_OK;
 }
 
+int vpx_denoise_var(vpx_ctx* c, const vpx_frame_params* p, const uint32_t* ids, const float* in, const float* mom,
+                    float* out, uint32_t* rgb8, const vpx_denoise_var_params* d) {
+    VPX_GROUP_FIRST(c, vpx_denoise_var(m_, p, ids, in, mom, out, rgb8, d));
+    if (!c || !p) return fail(c, VPX_E_INVALID, "null argument");
+    if (const char* why = denoise_var::check_call(p->width, p->height, ids, in, mom, out, d))
+        return fail(c, VPX_E_INVALID, why);
+    VPX_HIP(c, hipSetDevice(c->device));
+    const size_t pixels = (size_t)p->width * p->height;
+    uint2* keys = nullptr;
+    float4* img[2] = {nullptr, nullptr};
+    auto carve = [&](Carve cv) {  // the keys, V0, and the second image of a call with several passes
+        keys = cv.take<uint2>(pixels * sizeof(uint2));
+        img[0] = cv.take<float4>(pixels * sizeof(float4));
+        if (d->passes > 1) img[1] = cv.take<float4>(pixels * sizeof(float4));
+        return cv.used();
+    };
+    // an earlier call may still read the old scratch: wait
+    if (int rc = c->dv_buf.grow(c, carve(Carve(nullptr)), true)) return rc;
+    carve(Carve(c->dv_buf));
+    hipLaunchKernelGGL(k_plane_key, dim3((uint32_t)((pixels + kThreads - 1) / kThreads)), dim3(kThreads), 0, c->stream,
+                       (uint32_t)pixels, reinterpret_cast<const uint4*>(ids), keys);
+    DenoiseVarArgs a;
+    a.width = p->width, a.height = p->height, a.tiles_x = (p->width + kTile - 1) / kTile;
+    a.step = 1;
+    a.sigma_v = d->sigma_v, a.epsilon = d->epsilon, a.min_history = d->min_history;
+    const uint32_t tiles = a.tiles_x * ((p->height + kTile - 1) / kTile);
+    const float4* src = reinterpret_cast<const float4*>(in);
+    if (mom)
+        hipLaunchKernelGGL(k_var_estimate<true>, dim3(tiles), dim3(kThreads), 0, c->stream, a, keys, src,
+                           reinterpret_cast<const float2*>(mom), img[0]);
+    else
+        hipLaunchKernelGGL(k_var_estimate<false>, dim3(tiles), dim3(kThreads), 0, c->stream, a, keys, src,
+                           static_cast<const float2*>(nullptr), img[0]);
+    for (uint32_t k = 0; k < d->passes; ++k) {
+        const bool last = k + 1 == d->passes;
+        a.step = 1 << k;
+        launch_atrous_var(c->stream, tiles, a, keys, img[k & 1u], last ? reinterpret_cast<float4*>(out) : img[(k + 1u) & 1u],
+                          last ? src : nullptr, last ? rgb8 : nullptr);
+    }
+    VPX_HIP(c, hipGetLastError());
+    return VPX_OK;
+}
+
+// vpx_reproject_ids and vpx_reproject_moments (mom_out != NULL): one body, one scratch.
+static int reproject_call(vpx_ctx* c, const vpx_frame_params* p, const uint32_t* ids_cur, const uint32_t* ids_prev,
+                          const float* cur, const float* hist_in, const float* mom_in, float* hist_out, float* mom_out,
+                          uint32_t* rgb8, const vpx_reproject* r, const vpx_volume* cur_volumes,
+                          const vpx_volume* prev_volumes);
+
 int vpx_reproject_ids(vpx_ctx* c, const vpx_frame_params* p, const uint32_t* ids_cur, const uint32_t* ids_prev,
                       const float* cur, const float* hist_in, float* hist_out, uint32_t* rgb8, const vpx_reproject* r,
                       const vpx_volume* cur_volumes, const vpx_volume* prev_volumes) {
@@ -4043,6 +4352,26 @@ int vpx_reproject_ids(vpx_ctx* c, const vpx_frame_params* p, const uint32_t* ids
     if (const char* why = reproject::check_call(p->width, p->height, ids_cur, ids_prev, cur, hist_in, hist_out, r, cur_volumes,
                                                 prev_volumes))
         return fail(c, VPX_E_INVALID, why);
+    return reproject_call(c, p, ids_cur, ids_prev, cur, hist_in, nullptr, hist_out, nullptr, rgb8, r, cur_volumes, prev_volumes);
+}
+
+int vpx_reproject_moments(vpx_ctx* c, const vpx_frame_params* p, const uint32_t* ids_cur, const uint32_t* ids_prev,
+                          const float* cur, const float* hist_in, const float* mom_in, float* hist_out, float* mom_out,
+                          uint32_t* rgb8, const vpx_reproject* r, const vpx_volume* cur_volumes,
+                          const vpx_volume* prev_volumes) {
+    VPX_GROUP_FIRST(c, vpx_reproject_moments(m_, p, ids_cur, ids_prev, cur, hist_in, mom_in, hist_out, mom_out, rgb8, r,
+                                             cur_volumes, prev_volumes));
+    if (!c || !p) return fail(c, VPX_E_INVALID, "null argument");
+    if (const char* why = reproject::check_call_moments(p->width, p->height, ids_cur, ids_prev, cur, hist_in, mom_in, hist_out,
+                                                        mom_out, r, cur_volumes, prev_volumes))
+        return fail(c, VPX_E_INVALID, why);
+    return reproject_call(c, p, ids_cur, ids_prev, cur, hist_in, mom_in, hist_out, mom_out, rgb8, r, cur_volumes, prev_volumes);
+}
+
+static int reproject_call(vpx_ctx* c, const vpx_frame_params* p, const uint32_t* ids_cur, const uint32_t* ids_prev,
+                          const float* cur, const float* hist_in, const float* mom_in, float* hist_out, float* mom_out,
+                          uint32_t* rgb8, const vpx_reproject* r, const vpx_volume* cur_volumes,
+                          const vpx_volume* prev_volumes) {
     VPX_HIP(c, hipSetDevice(c->device));
     const bool have_prev = ids_prev != nullptr;
     const size_t pixels = (size_t)p->width * p->height;
@@ -4076,7 +4405,21 @@ int vpx_reproject_ids(vpx_ctx* c, const vpx_frame_params* p, const uint32_t* ids
     const uint4* ic = reinterpret_cast<const uint4*>(ids_cur);
     const float4 *cu = reinterpret_cast<const float4*>(cur), *hi = reinterpret_cast<const float4*>(hist_in);
     float4* ho = reinterpret_cast<float4*>(hist_out);
-    if (r->n_volumes) {
+    if (mom_out) {
+        const float2* mi = reinterpret_cast<const float2*>(mom_in);
+        float2* mo = reinterpret_cast<float2*>(mom_out);
+        if (r->n_volumes) {
+            if (rgb8)
+                launch_reproject_moments<true, true>(c->stream, tiles, a, tiles_x, ic, prev, cu, hi, mi, ho, mo, rgb8, tab, moved);
+            else
+                launch_reproject_moments<true, false>(c->stream, tiles, a, tiles_x, ic, prev, cu, hi, mi, ho, mo, rgb8, tab, moved);
+        } else {
+            if (rgb8)
+                launch_reproject_moments<false, true>(c->stream, tiles, a, tiles_x, ic, prev, cu, hi, mi, ho, mo, rgb8, tab, moved);
+            else
+                launch_reproject_moments<false, false>(c->stream, tiles, a, tiles_x, ic, prev, cu, hi, mi, ho, mo, rgb8, tab, moved);
+        }
+    } else if (r->n_volumes) {
         if (rgb8)
             launch_reproject<true, true>(c->stream, tiles, a, tiles_x, ic, prev, cu, hi, ho, rgb8, tab, moved);
         else

@@ -126,20 +126,43 @@ VPX_REPROJECT_HD void tap(Sum& s, float w, Rgbw h) {
     s.n = s.any ? (h.w < s.n ? h.w : s.n) : h.w;
     s.any = true;
 }
+VPX_REPROJECT_HD float blend_length(const Sum& s, float cap) { return (s.n < cap ? s.n : cap) + 1.0f; }
 VPX_REPROJECT_HD Rgbw blend(const Sum& s, Rgbw cur, float cap) {
     const float hr = s.r / s.w, hg = s.g / s.w, hb = s.b / s.w;
-    const float n = (s.n < cap ? s.n : cap) + 1.0f;
+    const float n = blend_length(s, cap);
     const float a = 1.0f / n;
     return Rgbw{hr + (cur.r - hr) * a, hg + (cur.g - hg) * a, hb + (cur.b - hb) * a, n};
+}
+
+// The moments payload (vpx_reproject_moments): the first two moments of the luminance ride along
+// the colour, over the same usable taps with the same weights and the same blend factor.
+struct Mom {  // one float2 of a moments image
+    float x, y;
+};
+struct NoMoments {  // vpx_reproject_ids: no payload, nothing of it is compiled in
+    static constexpr bool on = false;
+    VPX_REPROJECT_HD Mom operator()(uint64_t) const { return Mom{0.f, 0.f}; }
+};
+VPX_REPROJECT_HD Mom blend_moments(Mom s, const Sum& sum, float l, float l2, float cap) {
+    const float h1 = s.x / sum.w, h2 = s.y / sum.w;
+    const float a = 1.0f / blend_length(sum, cap);
+    return Mom{h1 + (l - h1) * a, h2 + (l2 - h2) * a};
 }
 
 // One pixel.  prev_key(i) -> denoise::Key of previous pixel i; hist(i) -> Rgbw of hist_in[i]; both
 // are called with in-image indices only, prev_key for all four taps (clamped into the image, so
 // that the loads need no branch and go out together) before any hist; hist only under a tap that
 // is in the image, has a positive weight and q's key.  tab / moved: the volume table (MOVING).
-template <bool MOVING, class PrevKey, class Hist>
+// mom_in(i) -> Mom of mom_in[i], under a usable tap only; mo: the pixel's moments (MomIn::on).
+template <bool MOVING, class PrevKey, class Hist, class MomIn>
 VPX_REPROJECT_HD Rgbw pixel(const Args& a, uint32_t x, uint32_t y, Id id, Rgbw cur, PrevKey prev_key, Hist hist,
-                            const float* tab, const uint32_t* moved) {
+                            const float* tab, const uint32_t* moved, MomIn mom_in, Mom& mo) {
+    float l = 0.f, l2 = 0.f;
+    if (MomIn::on) {
+        l = denoise::lum(cur.r, cur.g, cur.b);
+        l2 = l * l;
+        mo = Mom{l, l2};  // the no-history arm's
+    }
     const Rgbw none{cur.r, cur.g, cur.b, 1.0f};
     const denoise::Key kq = denoise::plane_key(id.y, id.z, id.w);
     if (!a.have_prev || !denoise::valid(kq) || !(a.cap >= 1.0f)) return none;
@@ -170,15 +193,31 @@ VPX_REPROJECT_HD Rgbw pixel(const Args& a, uint32_t x, uint32_t y, Id id, Rgbw c
         use[k] = in && w[k] > 0.0f && denoise::same(kr, kq);
     }
     Sum s;
+    Mom ms{0.f, 0.f};
 #if defined(__HIPCC__)
 #pragma unroll
 #endif
     for (int k = 0; k < 4; ++k)
         if (use[k]) {
             const Rgbw h = hist(at[k]);
-            if (h.w >= 1.0f) tap(s, w[k], h);  // a NaN length fails
+            if (h.w >= 1.0f) {  // a NaN length fails
+                tap(s, w[k], h);
+                if (MomIn::on) {
+                    const Mom m = mom_in(at[k]);
+                    ms.x = ms.x + w[k] * m.x;
+                    ms.y = ms.y + w[k] * m.y;
+                }
+            }
         }
-    return s.any ? blend(s, cur, a.cap) : none;
+    if (!s.any) return none;
+    if (MomIn::on) mo = blend_moments(ms, s, l, l2, a.cap);
+    return blend(s, cur, a.cap);
+}
+template <bool MOVING, class PrevKey, class Hist>
+VPX_REPROJECT_HD Rgbw pixel(const Args& a, uint32_t x, uint32_t y, Id id, Rgbw cur, PrevKey prev_key, Hist hist,
+                            const float* tab, const uint32_t* moved) {
+    Mom mo{0.f, 0.f};
+    return pixel<MOVING>(a, x, y, id, cur, prev_key, hist, tab, moved, NoMoments{}, mo);
 }
 
 // NULL, or why the call is refused (vpx.h: VPX_E_INVALID).
@@ -198,6 +237,21 @@ inline const char* check_call(uint32_t width, uint32_t height, const void* ids_c
     if (r->n_volumes > 0u && (!cur_volumes || !prev_volumes)) return "n_volumes without the volume arrays";
     if (hist_out == ids_cur || hist_out == ids_prev || hist_out == cur || hist_out == hist_in)
         return "hist_out must not be an input";
+    return nullptr;
+}
+// vpx_reproject_moments: vpx_reproject_ids' refusals, then the moments buffers'.
+inline const char* check_call_moments(uint32_t width, uint32_t height, const void* ids_cur, const void* ids_prev,
+                                      const void* cur, const void* hist_in, const void* mom_in, const void* hist_out,
+                                      const void* mom_out, const vpx_reproject* r, const void* cur_volumes,
+                                      const void* prev_volumes) {
+    if (const char* why = check_call(width, height, ids_cur, ids_prev, cur, hist_in, hist_out, r, cur_volumes, prev_volumes))
+        return why;
+    if (!mom_out) return "null argument";
+    if (!mom_in != !hist_in) return "mom_in and hist_in come together or not at all";
+    if (mom_in && hist_out == mom_in) return "hist_out must not be an input";
+    if (mom_out == ids_cur || mom_out == ids_prev || mom_out == cur || mom_out == hist_in || mom_out == mom_in ||
+        mom_out == hist_out)
+        return "mom_out must not be an input or hist_out";
     return nullptr;
 }
 
@@ -241,6 +295,33 @@ inline void run_host(uint32_t W, uint32_t H, const uint32_t* ids_cur, const uint
             const Rgbw o = r.n_volumes ? pixel<true>(a, x, y, id, c, prev_key, hist, tab, moved)
                                        : pixel<false>(a, x, y, id, c, prev_key, hist, tab, moved);
             hist_out[4 * q] = o.r, hist_out[4 * q + 1] = o.g, hist_out[4 * q + 2] = o.b, hist_out[4 * q + 3] = o.w;
+            if (rgb8) rgb8[q] = denoise::tonemap_pack_host(hist_out + 4 * q);
+        }
+}
+
+// vpx_reproject_moments on host memory: the same pixel function with the moments payload.
+struct HostMoments {
+    static constexpr bool on = true;
+    const float* m;
+    Mom operator()(uint64_t i) const { return Mom{m[2 * i], m[2 * i + 1]}; }
+};
+inline void run_host_moments(uint32_t W, uint32_t H, const uint32_t* ids_cur, const uint32_t* ids_prev, const float* cur,
+                             const float* hist_in, const float* mom_in, float* hist_out, float* mom_out, uint32_t* rgb8,
+                             const vpx_reproject& r, const float* tab, const uint32_t* moved) {
+    const Args a = make_args(W, H, r, ids_prev && hist_in);
+    auto prev_key = [=](uint64_t i) { return denoise::plane_key(ids_prev[4 * i + 1], ids_prev[4 * i + 2], ids_prev[4 * i + 3]); };
+    auto hist = [=](uint64_t i) { return Rgbw{hist_in[4 * i], hist_in[4 * i + 1], hist_in[4 * i + 2], hist_in[4 * i + 3]}; };
+    const HostMoments mi{mom_in};
+    for (uint32_t y = 0; y < H; ++y)
+        for (uint32_t x = 0; x < W; ++x) {
+            const uint64_t q = (uint64_t)y * W + x;
+            const Id id{ids_cur[4 * q], ids_cur[4 * q + 1], ids_cur[4 * q + 2], ids_cur[4 * q + 3]};
+            const Rgbw c{cur[4 * q], cur[4 * q + 1], cur[4 * q + 2], cur[4 * q + 3]};
+            Mom mo{0.f, 0.f};
+            const Rgbw o = r.n_volumes ? pixel<true>(a, x, y, id, c, prev_key, hist, tab, moved, mi, mo)
+                                       : pixel<false>(a, x, y, id, c, prev_key, hist, tab, moved, mi, mo);
+            hist_out[4 * q] = o.r, hist_out[4 * q + 1] = o.g, hist_out[4 * q + 2] = o.b, hist_out[4 * q + 3] = o.w;
+            mom_out[2 * q] = mo.x, mom_out[2 * q + 1] = mo.y;
             if (rgb8) rgb8[q] = denoise::tonemap_pack_host(hist_out + 4 * q);
         }
 }

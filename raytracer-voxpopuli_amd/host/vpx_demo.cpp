@@ -9,7 +9,8 @@
 //
 // usage: vpx_demo [n] [width] [height] [frames] [max_bounces] [out.rgb8] [mode] [devices]
 //   mode: letters — 's' staticCamera (the reprojection branch of Tick), 't' a moving camera with
-//   temporal accumulation (Renderer::temporal: every tick a step along a path), 'k' activateSky
+//   temporal accumulation (Renderer::temporal: every tick a step along a path), 'v' with 't': the
+//   variance-guided filter on the history (Renderer::temporalVariance, its defaults), 'k' activateSky
 //   with the demo sky texture (demo_sky below; tests rebuild it with numpy); 'p' puts a block
 //   of player smoke (SMOKE_PLAYER, cells x in [3n/4, 7n/8), y in [2, 2 + n/4), z in [n/4, 3n/8),
 //   albedo (0.8, 0.75, 0.7)) into the world under a point light of colour 8, tracks the player
@@ -281,9 +282,9 @@ int main(int argc, char** argv) {
     const char* out = argc > 6 && argv[6][0] != '-' ? argv[6] : nullptr;
     const char* mode = argc > 7 ? argv[7] : "";
     bool is_static = false, sky = false, player_light = false, player_cast = false, prop_edit = false,
-         generate = false, temporal = false;
+         generate = false, temporal = false, variance = false;
     for (const char* m = mode; *m; ++m)
-        temporal |= *m == 't', is_static |= *m == 's', sky |= *m == 'k', player_light |= *m == 'p', player_cast |= *m == 'w', prop_edit |= *m == 'm',
+        temporal |= *m == 't', variance |= *m == 'v', is_static |= *m == 's', sky |= *m == 'k', player_light |= *m == 'p', player_cast |= *m == 'w', prop_edit |= *m == 'm',
             generate |= *m == 'g';
     std::vector<int> devices;
     if (argc > 8)
@@ -341,7 +342,7 @@ int main(int argc, char** argv) {
     }
     r.staticCamera = is_static;
     if (temporal)  // a moving camera with temporal accumulation: every tick a step along a path, no material left out
-        r.temporal = true, r.temporalNohistLo = 1u, r.temporalNohistHi = 0u;
+        r.temporal = true, r.temporalNohistLo = 1u, r.temporalNohistHi = 0u, r.temporalVariance = variance;
     r.trackPlayerLight = player_light;
     vpx_player_light run{};  // the Ticks' records, summed
     uint32_t ticks_in_light = 0;

@@ -19,7 +19,7 @@ Renderer::~Renderer() {
     if (history_) (void)hipFree(history_);
     if (denoised_) (void)hipFree(denoised_);
     if (ids_) (void)hipFree(ids_);
-    for (void* b : {(void*)tIds_[0], (void*)tIds_[1], (void*)tHist_[0], (void*)tHist_[1]})
+    for (void* b : {(void*)tIds_[0], (void*)tIds_[1], (void*)tHist_[0], (void*)tHist_[1], (void*)tMom_[0], (void*)tMom_[1]})
         if (b) (void)hipFree(b);
     if (ctx_) vpx_destroy(ctx_);
 }
@@ -45,9 +45,9 @@ int Renderer::Init(uint32_t width, uint32_t height) {
         return VPX_E_NOMEM;
     }
     if (width != width_ || height != height_) {  // a resize drops the temporal history and its buffers
-        for (void* b : {(void*)tIds_[0], (void*)tIds_[1], (void*)tHist_[0], (void*)tHist_[1]})
+        for (void* b : {(void*)tIds_[0], (void*)tIds_[1], (void*)tHist_[0], (void*)tHist_[1], (void*)tMom_[0], (void*)tMom_[1]})
             if (b) (void)hipFree(b);
-        tIds_[0] = tIds_[1] = nullptr, tHist_[0] = tHist_[1] = nullptr;
+        tIds_[0] = tIds_[1] = nullptr, tHist_[0] = tHist_[1] = nullptr, tMom_[0] = tMom_[1] = nullptr;
         tValid_ = false;
     }
     width_ = width, height_ = height;
@@ -297,9 +297,17 @@ int Renderer::UpdateTemporal(vpx_stats* stats) {
         }
         tValid_ = false;
     }
-    if (temporalDenoisePasses && !denoised_ && hipMalloc(&denoised_, 16 * pixels) != hipSuccess) {
+    const bool filter = temporalVariance || temporalDenoisePasses;
+    if (filter && !denoised_ && hipMalloc(&denoised_, 16 * pixels) != hipSuccess) {
         err_ = "denoise buffer allocation failed";
         return VPX_E_NOMEM;
+    }
+    if (temporalVariance && !tMom_[0]) {  // switched on after the first tick: the history has no moments yet
+        if (hipMalloc(&tMom_[0], 8 * pixels) != hipSuccess || hipMalloc(&tMom_[1], 8 * pixels) != hipSuccess) {
+            err_ = "moments buffer allocation failed";
+            return VPX_E_NOMEM;
+        }
+        tValid_ = false;
     }
     vpx_frame_params p{};
     p.width = width_, p.height = height_;
@@ -330,10 +338,18 @@ int Renderer::UpdateTemporal(vpx_stats* stats) {
     r.n_volumes = moved ? (uint32_t)volumes_.size() : 0u;
     uint32_t* target = nullptr;
     if ((rc = MapScreen(&target))) return rc;
-    rc = vpx_reproject_ids(ctx_, &p, tIds_[cur], tValid_ ? tIds_[prev] : nullptr, accumulator_,
-                           tValid_ ? tHist_[prev] : nullptr, tHist_[cur], temporalDenoisePasses ? nullptr : target, &r,
-                           moved ? volumes_.data() : nullptr, moved ? tPrevVolumes_.data() : nullptr);
-    if (rc == VPX_OK && temporalDenoisePasses) {
+    if (temporalVariance) {
+        rc = vpx_reproject_moments(ctx_, &p, tIds_[cur], tValid_ ? tIds_[prev] : nullptr, accumulator_,
+                                   tValid_ ? tHist_[prev] : nullptr, tValid_ ? tMom_[prev] : nullptr, tHist_[cur], tMom_[cur],
+                                   nullptr, &r, moved ? volumes_.data() : nullptr, moved ? tPrevVolumes_.data() : nullptr);
+        if (rc == VPX_OK)
+            rc = vpx_denoise_var(ctx_, &p, tIds_[cur], tHist_[cur], tMom_[cur], denoised_, target, &temporalVarianceParams);
+    } else {
+        rc = vpx_reproject_ids(ctx_, &p, tIds_[cur], tValid_ ? tIds_[prev] : nullptr, accumulator_,
+                               tValid_ ? tHist_[prev] : nullptr, tHist_[cur], temporalDenoisePasses ? nullptr : target, &r,
+                               moved ? volumes_.data() : nullptr, moved ? tPrevVolumes_.data() : nullptr);
+    }
+    if (rc == VPX_OK && temporalDenoisePasses && !temporalVariance) {
         const vpx_denoise d{temporalDenoisePasses, temporalSigmaL, 0u, 0u};
         rc = vpx_denoise_ids(ctx_, &p, tIds_[cur], tHist_[cur], denoised_, target, &d);
     }
@@ -425,6 +441,26 @@ int Renderer::Denoise(uint32_t passes, float sigma_l) {
     uint32_t* target = nullptr;
     if ((rc = MapScreen(&target))) return rc;
     return UnmapScreen(vpx_denoise_ids(ctx_, &p, ids_, accumulator_, denoised_, target, &d));
+}
+
+int Renderer::DenoiseVariance(const vpx_denoise_var_params* d) {
+    if (status_) return status_;
+    if (!accumulator_) return VPX_E_STATE;
+    const size_t pixels = (size_t)width_ * height_;
+    if (hipSetDevice(device_) != hipSuccess ||
+        (!denoised_ && hipMalloc(&denoised_, sizeof(float) * 4 * pixels) != hipSuccess) ||
+        (!ids_ && hipMalloc(&ids_, sizeof(uint32_t) * 4 * pixels) != hipSuccess)) {
+        err_ = "denoise buffer allocation failed";
+        return VPX_E_NOMEM;
+    }
+    vpx_frame_params p{};
+    p.width = width_, p.height = height_;
+    int rc = vpx_render_ids(ctx_, &p, nullptr, ids_);
+    if (rc) return rc;
+    const vpx_denoise_var_params defaults{5u, 4.0f, 0.0009765625f, 1.0f, 0u, {0u, 0u, 0u}};
+    uint32_t* target = nullptr;
+    if ((rc = MapScreen(&target))) return rc;
+    return UnmapScreen(vpx_denoise_var(ctx_, &p, ids_, accumulator_, nullptr, denoised_, target, d ? d : &defaults));
 }
 
 int Renderer::CastRays(const vpx_ray* rays, uint32_t n, const vpx_ray_filter* filter, const vpx_cast* opt, vpx_hit* hits,

@@ -123,6 +123,9 @@ public:
     // it is): `passes` passes (1..5), sigma_l 0 = plane key only, the result in the denoised
     // image (CopyDenoised) and tonemapped into the screen.  Queued on the context's stream.
     int Denoise(uint32_t passes = 5, float sigma_l = 0.0f);
+    // The same with a per-pixel luminance tolerance (vpx_denoise_var without moments: the variance
+    // of each pixel's 5x5 neighbourhood on its plane); d NULL: 5 passes, sigma_v 4, epsilon 2^-10.
+    int DenoiseVariance(const vpx_denoise_var_params* d = nullptr);
     int CopyDenoised(float* host_rgba) const;
     // Temporal accumulation under camera motion (vpx_reproject_ids; no reference counterpart: the
     // reference resets its accumulator when the camera moves).  With `temporal` set, Tick's
@@ -136,7 +139,14 @@ public:
     uint32_t temporalNohistLo = 5, temporalNohistHi = 14;  // metal, glass, smoke: view-dependent
     uint32_t temporalDenoisePasses = 0;
     float temporalSigmaL = 0.0f;
-    void DropHistory() { tValid_ = false; }
+    // temporalVariance: the luminance's first two moments ride along the history
+    // (vpx_reproject_moments) and the filter on the result is vpx_denoise_var with these
+    // parameters (in place of temporalDenoisePasses / temporalSigmaL): pixels whose history is at
+    // least min_history frames long take their temporal variance, the others their neighbourhood's.
+    bool temporalVariance = false;
+    vpx_denoise_var_params temporalVarianceParams{5u, 4.0f, 0.0009765625f, 4.0f, 0u, {0u, 0u, 0u}};
+    void DropHistory() { tValid_ = false; }  // the moments go with the history
+    void ResetTemporal() { DropHistory(); }
     int CopyTemporalHistory(float* host_rgba) const;
     // Ray batches that already live on the device (vpx_cast_nearest / vpx_cast_occluded; no reference
     // counterpart: per ray the records of Renderer::FindNearest / IsOccluded): rays, hits, cells and
@@ -203,6 +213,7 @@ private:
     uint32_t* ids_ = nullptr;       // ... and its ID buffer, uint4[W*H]
     uint32_t* tIds_[2] = {nullptr, nullptr};  // UpdateTemporal(): this tick's and the previous tick's ids ...
     float* tHist_[2] = {nullptr, nullptr};    // ... and history images, swapped per tick
+    float* tMom_[2] = {nullptr, nullptr};     // ... and, with temporalVariance, moments images (float2[W*H])
     float* temporalHistory_ = nullptr;        // the one the last tick wrote
     int tCur_ = 0;
     bool tValid_ = false;

@@ -58,14 +58,21 @@ class Renderer:
         # None / False: Tick's moving-camera branch as the reference has it.  True or a dict of
         # max_history (32), nohist (the (lo, hi) first-hit materials without history: metal, glass
         # and smoke, 5..14), denoise (None, or a dict of passes / sigma_l for Denoise's filter on
-        # the result): see _tick_temporal.
+        # the result), variance (None, or a dict of sigma_v / epsilon / min_history / passes: the
+        # luminance's moments ride along the history (vpx_reproject_moments) and the filter on the
+        # result is vpx_denoise_var; takes the place of denoise): see _tick_temporal.
         self.temporal = None
         if temporal:
             self.temporal = dict(max_history=32, nohist=(5, 14), denoise=None)
             if isinstance(temporal, dict):
                 self.temporal.update(temporal)
+            if self.temporal.get("variance"):  # the key is there only when asked for
+                given = self.temporal["variance"] if isinstance(self.temporal["variance"], dict) else {}
+                self.temporal["variance"] = dict(dict(sigma_v=4.0, epsilon=2.0 ** -10, min_history=4, passes=5), **given)
         self.history = None           # the temporal mode's current history image, float4[W*H], .w its length
         self._t_ids, self._t_hist = None, None   # two ID buffers and two history images, swapped per tick
+        self._t_mom = None            # ... and, with temporal variance, two moments images (float2[W*H])
+        self.moments = None           # the current one
         self._t_cur, self._t_valid, self._t_ticks = 0, False, 0
         self._t_prev_camera, self._t_prev_volumes = None, None
         self.device = torch.device("cuda", device)
@@ -172,8 +179,11 @@ class Renderer:
         self.ctx.set_camera(self.scene.camera)
 
     def DropHistory(self):
-        """Forget the temporal mode's history: the next Tick starts from its own samples."""
+        """Forget the temporal mode's history, and the moments that ride along it: the next Tick
+        starts from its own samples."""
         self._t_valid = False
+
+    ResetTemporal = DropHistory
 
     def _tick_temporal(self, stats=False):
         """One Tick of a moving camera with temporal accumulation, queued on the renderer's stream
@@ -184,7 +194,10 @@ class Renderer:
         on self.history into self.denoised; the screen shows the last of them.  The history, not
         the denoised image, is what the next tick reads.  A change of the frame's size drops the
         history; so does DropHistory().  Volumes whose matrices changed since the previous tick are
-        followed (vpx_reproject's moving volumes)."""
+        followed (vpx_reproject's moving volumes).  With temporal["variance"] the reprojection is
+        vpx_reproject_moments, a moments image ping-pongs beside the history, and the filter is
+        vpx_denoise_var on (history, moments): pixels whose history is at least min_history frames
+        long take their temporal variance, the others their neighbourhood's."""
         from .scene import prev_camera
         t = self.temporal
         w, h = self.scene.width, self.scene.height
@@ -192,6 +205,8 @@ class Renderer:
             with torch.cuda.stream(self.stream):
                 self._t_ids = [torch.empty(w * h * 4, dtype=torch.int32, device=self.device) for _ in range(2)]
                 self._t_hist = [torch.empty(w * h * 4, dtype=torch.float32, device=self.device) for _ in range(2)]
+                if t.get("variance"):
+                    self._t_mom = [torch.empty(w * h * 2, dtype=torch.float32, device=self.device) for _ in range(2)]
             self._t_valid = False
         p = self._frame_params()
         p.frame_index = 0
@@ -208,15 +223,25 @@ class Renderer:
         moved = (self._t_valid and self._t_prev_volumes is not None and len(self._t_prev_volumes) == len(volumes) and
                  any(bytes(a) != bytes(b) for a, b in zip(volumes, self._t_prev_volumes)))
         with torch.cuda.stream(self.stream):
-            if t["denoise"] and self.denoised is None:
+            if (t["denoise"] or t.get("variance")) and self.denoised is None:
                 self.denoised = torch.empty_like(self.accumulator)
-        self.ctx.reproject(p, ids[cur], ids[prev] if self._t_valid else None, self.accumulator,
-                           hist[prev] if self._t_valid else None, self.scene.camera,
-                           self._t_prev_camera if self._t_valid else here, out=hist[cur], max_history=t["max_history"],
-                           nohist=t["nohist"], cur_volumes=volumes if moved else None,
-                           prev_volumes=self._t_prev_volumes if moved else None,
-                           rgb_ptr=None if t["denoise"] else self.screen.data_ptr())
-        if t["denoise"]:
+        common = dict(max_history=t["max_history"], nohist=t["nohist"], cur_volumes=volumes if moved else None,
+                      prev_volumes=self._t_prev_volumes if moved else None)
+        if t.get("variance"):
+            v, mom = t.get("variance"), self._t_mom
+            self.ctx.reproject_moments(p, ids[cur], ids[prev] if self._t_valid else None, self.accumulator,
+                                       hist[prev] if self._t_valid else None, mom[prev] if self._t_valid else None,
+                                       self.scene.camera, self._t_prev_camera if self._t_valid else here, out=hist[cur],
+                                       mom_out=mom[cur], **common)
+            self.ctx.denoise_var(p, ids[cur], hist[cur], mom[cur], self.denoised, v["passes"], v["sigma_v"], v["epsilon"],
+                                 v["min_history"], self.screen.data_ptr())
+            self.moments = mom[cur]
+        else:
+            self.ctx.reproject(p, ids[cur], ids[prev] if self._t_valid else None, self.accumulator,
+                               hist[prev] if self._t_valid else None, self.scene.camera,
+                               self._t_prev_camera if self._t_valid else here, out=hist[cur],
+                               rgb_ptr=None if t["denoise"] else self.screen.data_ptr(), **common)
+        if t["denoise"] and not t.get("variance"):
             self.ctx.denoise(p, ids[cur], hist[cur], self.denoised, t["denoise"].get("passes", 5),
                              t["denoise"].get("sigma_l", 0.0), self.screen.data_ptr())
         self.history, self.ids = hist[cur], ids[cur]
@@ -227,6 +252,10 @@ class Renderer:
     def temporal_history_host(self):
         self.synchronize()
         return self.history.cpu().numpy().reshape(self.scene.height, self.scene.width, 4)
+
+    def temporal_moments_host(self):
+        self.synchronize()
+        return self.moments.cpu().numpy().reshape(self.scene.height, self.scene.width, 2)
 
     def _read_player_light(self):
         """The frame's flag, read and cleared after the render on both branches: the reference's
@@ -266,19 +295,26 @@ class Renderer:
 
     pick_pixel = PickPixel
 
-    def Denoise(self, passes=5, sigma_l=0.0):
+    def Denoise(self, passes=5, sigma_l=0.0, variance=None):
         """The plane-keyed a-trous filter of the current accumulator (no reference counterpart: the
         reference shows a moving camera's frame as it is): the ids of the current camera
         (vpx_render_ids), then vpx_denoise_ids from self.accumulator into self.denoised, tonemapped
         into self.screen.  Three launches or more on the renderer's stream, no synchronisation.
         The ids are those of the un-jittered pixel-centre ray; paths through glass, smoke or a
-        mirror are keyed by their first hit."""
+        mirror are keyed by their first hit.  variance: True or a dict of sigma_v / epsilon (and
+        passes): vpx_denoise_var without moments instead, the luminance tolerance from the variance
+        of each pixel's 5x5 neighbourhood on its plane (sigma_l is not used)."""
         p = self._frame_params()
         with torch.cuda.stream(self.stream):  # the tensors belong to the stream their kernels run on
             self.ids = self.ctx.render_ids(p)
             if self.denoised is None:
                 self.denoised = torch.empty_like(self.accumulator)
-        self.ctx.denoise(p, self.ids, self.accumulator, self.denoised, passes, sigma_l, self.screen.data_ptr())
+        if variance:
+            v = dict(dict(sigma_v=4.0, epsilon=2.0 ** -10, passes=passes), **(variance if isinstance(variance, dict) else {}))
+            self.ctx.denoise_var(p, self.ids, self.accumulator, None, self.denoised, v["passes"], v["sigma_v"], v["epsilon"],
+                                 1, self.screen.data_ptr())
+        else:
+            self.ctx.denoise(p, self.ids, self.accumulator, self.denoised, passes, sigma_l, self.screen.data_ptr())
         return self.denoised
 
     def CastRays(self, rays, filter=None, cells=True, form=None, max_waves=0):
