@@ -281,7 +281,8 @@ __device__ __forceinline__ uint32_t wave_sum(uint32_t v) { return __reduce_add_s
 // Work counters: [0] shadow rays, [1] FindNearest calls, [2] DDA cells, [3] primary rays,
 // [8 + s] DDA cells of stage s (VPX_STAGE_*), striped over kCtrStripes copies of
 // kCtrWords words (one 64-bit atomic per counter per wave, spread over addresses by
-// workgroup so that waves do not serialise on one word); summed on readout.
+// workgroup so that waves do not serialise on one word); summed on readout.  k_frame0 goes
+// through a record in its LDS and flushes once per workgroup (WgCounters, below).
 constexpr uint32_t kCtrStripes = 64;
 constexpr uint32_t kCtrWords = 16;
 __device__ __forceinline__ void flush_counters(const Counters& k, uint32_t primary, unsigned long long* ctr,
@@ -297,6 +298,75 @@ __device__ __forceinline__ void flush_counters(const Counters& k, uint32_t prima
             atomicAdd(&c[8 + stage], (unsigned long long)ce);
         }
         if (pr) atomicAdd(&c[3], (unsigned long long)pr);
+    }
+}
+
+// Round 15: k_frame0 flushes once per workgroup instead of three times per wave.  Its waves add
+// their sums to a record in the workgroup's LDS where they flushed (after the primary walks,
+// the level-0 shade and the shadow walks: nothing is carried across a walk loop, the reason the
+// flush was per phase), and after the barrier that follows the shadow walks one lane per
+// non-zero word issues one global atomic into the workgroup's stripe.  The kernel's bench instance:
+// three groups of up to five 64-bit atomics per wave (up to 60 per workgroup, all on the
+// stripe's one cache line) become one group of at most seven per workgroup, and the twelve DPP
+// reductions per wave become at most one (cells) per phase, none in a wave that counted nothing
+// (its listing: 15 global atomic instructions -> 1, 84 DPP instructions -> 36, 7571 -> 7479 in all).
+// C1 0.3887-0.3985 ms per step against the parent's 0.3992-0.4041 (eight interleaved runs);
+// the record with DPP sums throughout (-DVPX_COUNT_BALLOTS=0) 0.3951-0.3996, 256 stripes instead
+// of 64 0.3891-0.3983: no better than 64, which stays (profiles/r15_counter_flush_ab.txt).
+// The guaranteed-form instances (VIEW 1) pay for it with a second reload inside the primary walk
+// loop and reloads in the shade's light loops (profiles/r15_loop_scratch.txt) and are still
+// faster than the parent's (sky frame 0.3866-0.3884 against 0.3923-0.3942 ms, six runs each).
+// 32-bit words suffice: a tile has 256 paths, a path casts one primary and (in this kernel) one
+// shadow ray, and its cells per frame are far below 2^24 (a walk visits a few times the grid's
+// edge in cells at the most), so a word stays below 2^32; the global words stay 64-bit.
+struct WgCounters {
+    uint32_t w[8];  // [0] shadow rays, [1] FindNearest calls, [2] primary rays, [3 + s] DDA cells of stage s < 3
+};
+static_assert(VPX_STAGE_PRIMARY == 0 && VPX_STAGE_SHADE == 1 && VPX_STAGE_SHADOW == 2, "WgCounters::w[3 + stage]");
+__device__ __forceinline__ void wg_zero(WgCounters* wc) {  // published by the caller's next barrier
+    if (threadIdx.x < 8u) wc->w[threadIdx.x] = 0u;
+}
+// Exact wave reductions that cost less than the DPP sum: the number of lanes whose flag is set
+// (a count that is 0 or 1 per lane), and a sum that is skipped when every lane holds 0.
+// (-DVPX_COUNT_BALLOTS=0: the DPP sum for both, the A/B baseline of the record alone.)
+#ifndef VPX_COUNT_BALLOTS
+#define VPX_COUNT_BALLOTS 1
+#endif
+__device__ __forceinline__ uint32_t wave_count(bool b) {
+    return VPX_COUNT_BALLOTS ? (uint32_t)__popcll(__ballot(b)) : wave_sum(b ? 1u : 0u);
+}
+__device__ __forceinline__ uint32_t wave_sum_nz(uint32_t v) {
+    return !VPX_COUNT_BALLOTS || __ballot(v != 0u) ? wave_sum(v) : 0u;
+}
+// A wave's sums (wave-uniform) of one stage into the record: one lane, LDS adds, non-zero sums only.
+__device__ __forceinline__ void wg_add_sums(WgCounters* wc, uint32_t sh, uint32_t ne, uint32_t ce, uint32_t pr,
+                                            uint32_t stage) {
+    if (!(sh | ne | ce | pr)) return;  // wave-uniform: an idle wave falls through
+    // the lane test from a copy the compiler takes for a new value: shared between the three
+    // phases' adds, its mask was kept in scalar registers across the walk loops
+    uint32_t t = threadIdx.x;
+    asm volatile("" : "+v"(t));
+    if ((t & 63u) == 0u) {
+        if (sh) atomicAdd(&wc->w[0], sh);
+        if (ne) atomicAdd(&wc->w[1], ne);
+        if (pr) atomicAdd(&wc->w[2], pr);
+        if (ce) atomicAdd(&wc->w[3 + stage], ce);
+    }
+}
+// A wave's Counters of one stage (any per-lane values).
+__device__ __forceinline__ void wg_add(WgCounters* wc, const Counters& k, uint32_t stage) {
+    if (!__ballot((k.shadow | k.nearest | k.cells) != 0u)) return;  // nothing counted: no reduction
+    wg_add_sums(wc, wave_sum_nz(k.shadow), wave_sum_nz(k.nearest), wave_sum_nz(k.cells), 0u, stage);
+}
+// The workgroup's one flush, after a barrier that follows the last add: flush_counters' words
+// ([2] the stages' sum, [8 + s] each stage's own) into the workgroup's stripe.
+__device__ __forceinline__ void wg_flush(const WgCounters* wc, unsigned long long* ctr) {
+    const uint32_t t = threadIdx.x;
+    if (t < 7u) {
+        const uint32_t v = t < 6u ? wc->w[t] : wc->w[3] + wc->w[4] + wc->w[5];
+        // record word -> counter word: 0 -> 0, 1 -> 1, 2 -> 3, 3 + s -> 8 + s, the cells' sum -> 2
+        const uint32_t to = t < 2u ? t : t == 2u ? 3u : t < 6u ? t + 5u : 2u;
+        if (v) atomicAdd(&ctr[kCtrWords * (blockIdx.x & (kCtrStripes - 1u)) + to], (unsigned long long)v);
     }
 }
 
@@ -1002,11 +1072,16 @@ __device__ __forceinline__ bool meets_later_volume(const SceneView& sv, f3 o, f3
 // rays reach the instance lattice's box.
 // STASH (k_frame0; ONE && SHADE): the pixel threads hand their walk state to the walkers
 // through *st (WalkStash) instead of the walkers setting the walk up again.
-template <bool ONE, bool SHADE, class KIND = NearestWalk, bool DEFER = false, bool STASH = false>
+// wc (k_frame0): the workgroup's counter record, which takes the two stages' sums instead of the
+// global counters (the kernel flushes it once, wg_flush); without WG each wave flushes its own.
+// (A template flag beside the pointer: an LDS address is not a compile-time constant, and a test
+// of the pointer kept both forms in the kernel.)
+template <bool ONE, bool SHADE, class KIND = NearestWalk, bool DEFER = false, bool STASH = false, bool WG = false>
 __device__ __forceinline__ void primary_tile(const SceneView& sv, const FrameArgs& f, const WaveBufs& w,
                                              HeadLds<SHADE>& L, unsigned long long* __restrict__ ctr,
-                                             const WalkStash* st = nullptr) {
+                                             const WalkStash* st = nullptr, WgCounters* wc = nullptr) {
     static_assert(!STASH || (ONE && SHADE), "the walk stash is the fused single-volume head's");
+    static_assert(!WG || STASH, "the counter record is k_frame0's, whose head stashes");
     uint32_t* sh = L.sh;
     uint32_t* lst = L.lst;
     const uint32_t tb = tile_block() * 256u;
@@ -1061,9 +1136,10 @@ __device__ __forceinline__ void primary_tile(const SceneView& sv, const FrameArg
         }
     }
     // STASH: what the pixel thread carries across the walks in one register (its two one-bit
-    // counts) or not at all (its path, re-derived below): the walk loops have no register to spare
+    // counts; with WG not even those) or not at all (its path, re-derived below): the walk loops
+    // have no register to spare
     uint32_t carried = 0u;
-    if (STASH) {
+    if (STASH && !WG) {
         carried = prim | k.nearest << 1;
         asm volatile("" : "+v"(carried));
         prim = k.nearest = 0u;
@@ -1071,6 +1147,14 @@ __device__ __forceinline__ void primary_tile(const SceneView& sv, const FrameArg
     uint32_t total;
     const uint32_t at = block_scan(walk ? 1u : 0u, total, sh);  // (its barrier orders the LDS writes)
     if (walk) lst[at] = p;
+    if (WG) {
+        // with the record the two counts (one bit per lane: ballots) are added here, after the
+        // barrier that published its zeroes, and nothing is carried across the walks
+        // (the two counts packed into one register across block_scan measured worse: the bench's
+        // instance got its reload inside the primary walk loop back)
+        wg_add_sums(wc, 0u, wave_count(k.nearest != 0u), 0u, wave_count(prim != 0u), VPX_STAGE_PRIMARY);
+        prim = k.nearest = 0u;
+    }
     __syncthreads();
     VPX_FRAME_PHASE(1);
     if (threadIdx.x < total) {
@@ -1091,12 +1175,21 @@ __device__ __forceinline__ void primary_tile(const SceneView& sv, const FrameArg
     VPX_FRAME_PHASE(2);
     uint32_t ps = p;  // the thread's own path for the shade
     if (STASH) {
-        prim = carried & 1u;
-        k.nearest += carried >> 1;
         ps = tb + threadIdx.x;
         asm volatile("" : "+v"(ps));
     }
-    flush_counters(k, prim, ctr, VPX_STAGE_PRIMARY);
+    VPX_MARK("frame counters");
+    if (WG) {
+        // a walker lane's FindNearest count is its one call (nearest_record_stashed): a ballot;
+        // only the cells need a sum (FindNearest casts no shadow ray)
+        wg_add_sums(wc, 0u, wave_count(k.nearest != 0u), wave_sum_nz(k.cells), 0u, VPX_STAGE_PRIMARY);
+    } else {
+        if (STASH) {
+            prim = carried & 1u;
+            k.nearest += carried >> 1;
+        }
+        flush_counters(k, prim, ctr, VPX_STAGE_PRIMARY);
+    }
     if (SHADE) {  // level 0's material switch for this thread's own path (k_primary_shade)
         // the tile's hit records, written by the compacted walkers; with STASH it also orders
         // the walkers' reads of the stash before the shade's writes to the records that held it
@@ -1120,7 +1213,11 @@ __device__ __forceinline__ void primary_tile(const SceneView& sv, const FrameArg
         if (DEFER) put_amask(w, ps, defer);
         const bool cont = defer ? false : shade_path<true>(sv, f, w, pr, ps, 0, ks);
         if (!DEFER && f.max_bounces > 0) put_amask(w, ps, cont);
-        flush_counters(ks, 0u, ctr, VPX_STAGE_SHADE);
+        VPX_MARK("frame counters");
+        if (WG)
+            wg_add(wc, ks, VPX_STAGE_SHADE);
+        else
+            flush_counters(ks, 0u, ctr, VPX_STAGE_SHADE);
     }
 }
 
@@ -1417,10 +1514,11 @@ __device__ __forceinline__ void mark_occluded(const WaveBufs& w, uint64_t slot, 
 // entry i in the .w word of lw[i], instead of 32-bit entries in the dynamic LDS.  k_frame0
 // passes the tile's SL records: put_slot writes 0 there and nobody reads it (resolve_path takes
 // x, y, z), so the list costs no LDS of its own.
+// WG, wc (k_frame0): the workgroup's counter record instead of the per-wave flush (primary_tile).
 constexpr uint32_t kShadowTileLds = sizeof(uint32_t) * (4u + kLightKeys);  // shadow_tile's own statics: sh, hist
-template <bool ONE, class KIND = ShadowWalk>
+template <bool ONE, class KIND = ShadowWalk, bool WG = false>
 __device__ __forceinline__ void shadow_tile(const SceneView& sv, const WaveBufs& w, unsigned long long* __restrict__ ctr,
-                                            uint32_t* occ, uint32_t p, float4* lw = nullptr) {
+                                            uint32_t* occ, uint32_t p, float4* lw = nullptr, WgCounters* wc = nullptr) {
     __shared__ uint32_t sh[4];
     if (occ)
         for (uint32_t i = threadIdx.x; i < w.S * 8u; i += 256u) occ[i] = 0u;  // published by the barriers below
@@ -1491,7 +1589,13 @@ __device__ __forceinline__ void shadow_tile(const SceneView& sv, const WaveBufs&
         if (shadow(sv, r, k)) mark_occluded(w, slot, e, occ);
     }
     VPX_FRAME_PHASE(6);
-    flush_counters(k, 0u, ctr, VPX_STAGE_SHADOW);
+    VPX_MARK("frame counters");
+    if (WG && lw && ONE)  // at most 256 entries (one slot per path): a lane walked one or none
+        wg_add_sums(wc, wave_count(k.shadow != 0u), wave_sum_nz(k.nearest), wave_sum_nz(k.cells), 0u, VPX_STAGE_SHADOW);
+    else if (WG)
+        wg_add(wc, k, VPX_STAGE_SHADOW);
+    else
+        flush_counters(k, 0u, ctr, VPX_STAGE_SHADOW);
 }
 
 template <bool ONE>
@@ -2052,6 +2156,11 @@ constexpr uint32_t kFuseFrameTiles = VPX_FUSE_FRAME_TILES;
 #ifndef VPX_FRAME_HANDOFF
 #define VPX_FRAME_HANDOFF 1
 #endif
+// The work counters go through a workgroup record in LDS and one flush (WgCounters); 0: every
+// wave flushes after each of the three phases (the A/B baseline).
+#ifndef VPX_FRAME_WG_COUNTERS
+#define VPX_FRAME_WG_COUNTERS 1
+#endif
 // The depth-0 frame's path state never leaves the workgroup: a path is shaded, its light
 // resolved and its pixel finished by the same thread, and its shadow slots are walked by the
 // same tile, so the shade's records (LA / leaf, SM, forms, smask) and — one slot per path: the
@@ -2123,15 +2232,17 @@ __device__ __forceinline__ FrameArgs frame0_args(const FrameArgs& f) {
 // Seven workgroups must share a CU's 163840 bytes whatever the allocation granule: a workgroup
 // may take 23040 bytes = 18 x 1280 = 45 x 512 = 90 x 256 (7 x 23040 = 161280); 23168, the
 // round-5 size, rounds to 23552 at 512 (7 x = 164864) and to 24320 at 1280 (7 x = 170240).
+// Round 15: the workgroup's counter record (wc, 32 bytes) joins it: 22608 + 80 = 22688.
 struct Frame0Lds {
     HeadLds<true> L;     // 14352: sh, the walker list (then forms), O / D / H (then SO / SD / SL), HM (then smask)
     float4 s_val[256];   // 4096: the walk stash, then LA (a) or leaf of the path's one level
     float4 s_sm[256];    // 4096: the walk stash, then SM: the pending light
     uint32_t occ[8];     // 32: one slot per path (S == 1, checked at launch)
+    WgCounters wc;       // 32: the workgroup's work counters (round 15), flushed once after the shadow walks
 };
 constexpr uint32_t kFrame0LdsBudget = 23040;
 static_assert(sizeof(Frame0Lds) + kShadowTileLds <= kFrame0LdsBudget,
-              "k_frame0: seven workgroups no longer fit a CU's LDS (22576 + 80 = 22656 today)");
+              "k_frame0: seven workgroups no longer fit a CU's LDS (22608 + 80 = 22688 today)");
 
 template <bool ONE, int MODE, bool X86 = false, int VIEW = kFrameAsGiven>
 __global__ __launch_bounds__(256) VPX_WPE(ONE ? VPX_WPE_FRAME : VPX_WPE_MULTI_NEAREST) void k_frame0(
@@ -2161,18 +2272,27 @@ __global__ __launch_bounds__(256) VPX_WPE(ONE ? VPX_WPE_FRAME : VPX_WPE_MULTI_NE
     // the walkers' barrier) and its H record (written by its walker, after the walk)
     constexpr bool kStash = ONE && VPX_FRAME_HANDOFF;
     const WalkStash st{L.ray + 512, s_val, s_sm};
-    primary_tile<ONE, true, FrameNearestWalk, false, kStash>(sv, f, wl, L, ctr, &st);
+    // the workgroup's counter record: zeroed before the head's first barrier, added to where the
+    // waves flushed (primary_tile, shadow_tile), flushed once below
+    constexpr bool kWg = kStash && VPX_FRAME_WG_COUNTERS;  // (the adds count a walker lane's one stashed walk)
+    WgCounters* const wc = &F.wc;
+    if (kWg) wg_zero(wc);
+    primary_tile<ONE, true, FrameNearestWalk, false, kStash, kWg>(sv, f, wl, L, ctr, &st, wc);
     __syncthreads();
     VPX_FRAME_PHASE(4);
     float4* const lw = L.ray + 512;  // the shadow list in the SL records' .w (shadow_tile)
 #ifdef VPX_FRAME_P_TILE
-    shadow_tile<ONE, FrameShadowWalk>(sv, wl, ctr, occ, tile_block() * 256u + threadIdx.x, lw);
+    shadow_tile<ONE, FrameShadowWalk, kWg>(sv, wl, ctr, occ, tile_block() * 256u + threadIdx.x, lw, wc);
 #else
     uint32_t ps = p;  // re-derived, not kept live across the head (as pt below)
     asm volatile("" : "+v"(ps));
-    shadow_tile<ONE, FrameShadowWalk>(sv, wl, ctr, occ, ps, lw);
+    shadow_tile<ONE, FrameShadowWalk, kWg>(sv, wl, ctr, occ, ps, lw, wc);
 #endif
     __syncthreads();
+    if (kWg) {
+        VPX_MARK("frame counters");
+        wg_flush(wc, ctr);
+    }
     VPX_FRAME_PHASE(7);
     // the tail's own copy of p: the shade's per-lane LDS addresses are re-derived here
     // instead of being kept live (spilled) across the shadow walks

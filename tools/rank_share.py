@@ -1,7 +1,7 @@
 """One rank's GPU time in the N-GPU strong-scaling run, measured on one GPU: rank 0's share
 of a config's frame (vpx_render_tiles_accum, rank 0 of R) for R = 1, 2, 4, 8 — the render
 part of bench.py --gpus R without the gather.  CFG (default C1), K frames per R, PIPE frames
-in flight (vpx_set_pipeline lanes, default 0); WINDOW=1 (default) renders an spp > 1 step as
+in flight (vpx_set_pipeline lanes, default 0); SKY=1 turns the sky texture on; WINDOW=1 (default) renders an spp > 1 step as
 one accumulation window (vpx_render_tiles_accum_window, as bench.py does), WINDOW=0 frame by
 frame.
 """
@@ -17,6 +17,8 @@ import __graft_entry__ as entry  # noqa: E402
 pkg = entry.load_package()
 cfg = os.environ.get("CFG", "C1")
 desc = pkg.scene.CONFIGS[cfg]()
+if os.environ.get("SKY") == "1":  # the sky texture on: k_frame0's guaranteed form instead of the lean one
+    desc = pkg.scene.with_sky(desc)
 K = int(os.environ.get("K", "20"))
 s = torch.cuda.Stream()
 torch.cuda.set_stream(s)
