@@ -523,8 +523,10 @@ int vpx_render_tiles_accum(vpx_ctx* ctx, const vpx_frame_params* params, uint32_
    (a rank's 1/n_ranks of the tiles), several frames render in ONE chain of launches — frame b
    in tile blocks [b*T, (b+1)*T) with its own seeds — and a single blend folds their samples
    into the accumulator in frame order; large frames render one chain each.  Lanes
-   (vpx_set_pipeline) carry the chains as they carry frames.  VPX_FLAG_NO_TONEMAP frames and
-   device sets (vpx_create_multi) render frame by frame. */
+   (vpx_set_pipeline) carry the chains as they carry frames.  VPX_FLAG_NO_TONEMAP frames
+   render frame by frame.  On a device set (vpx_create_multi) vpx_render_window is n_frames
+   calls of vpx_render on the set and takes what that takes (accum may be NULL with rgb8
+   given: the members' sharded accumulators). */
 int vpx_render_window(vpx_ctx* ctx, const vpx_frame_params* params, uint32_t n_frames, float* accum,
                       uint32_t* rgb8);
 int vpx_render_tiles_accum_window(vpx_ctx* ctx, const vpx_frame_params* params, uint32_t n_frames,

@@ -3819,7 +3819,7 @@ static int render_window_impl(vpx_ctx* c, const vpx_frame_params* p, uint32_t n,
         bmax = std::min<uint32_t>(bmax, std::max<uint32_t>(1u, (n + (uint32_t)c->lanes.size() - 1) / (uint32_t)c->lanes.size()));
     // the shadow lists pack a path index into 27 bits (validate_frame's bound per chain)
     while (bmax > 1 && (uint64_t)bmax * T * kTilePix > (1ull << 27)) --bmax;
-    const bool per_frame = bmax == 1 || n == 1 || (p->flags & VPX_FLAG_NO_TONEMAP) || !c->members.empty();
+    const bool per_frame = bmax == 1 || n == 1 || (p->flags & VPX_FLAG_NO_TONEMAP);  // (a device set never gets here)
     for (uint32_t i = 0; i < n;) {
         vpx_frame_params q = *p;
         q.frame_index = p->frame_index + i;
@@ -3887,6 +3887,17 @@ static int render_window_impl(vpx_ctx* c, const vpx_frame_params* p, uint32_t n,
 }
 
 int vpx_render_window(vpx_ctx* c, const vpx_frame_params* p, uint32_t n_frames, float* accum, uint32_t* rgb8) {
+    if (c && !c->members.empty()) {
+        // a device set keeps its camera and world in its members: frame by frame through
+        // vpx_render (group_render validates, and takes accum == NULL with rgb8 given)
+        if (!p) return fail(c, VPX_E_INVALID, "null params");
+        for (uint32_t i = 0; i < n_frames; ++i) {
+            vpx_frame_params q = *p;
+            q.frame_index = p->frame_index + i;
+            if (int rc = vpx_render(c, &q, accum, rgb8, nullptr)) return rc;
+        }
+        return VPX_OK;
+    }
     return render_window_impl(c, p, n_frames, 0, 1, true, accum, rgb8);
 }
 

@@ -635,10 +635,54 @@ def test_trace_depth1_every_branch(pkg, orc, name, wall, ray):
     assert (st.shadow_rays, st.dda_cells) == (shadows, cells_n)
 
 
+DEPTHS = (2, 3, 5)
+# In the room no glass march can leave the grid (the block stands clear of the cube's faces), so the
+# deeper tests add a case whose glass reaches the x = 0 face and a ray inside it that heads there.
+DEEP_CASES = CASES + [("glass_to_the_edge", 8, ((0.27, 0.22, 0.45), (-1.0, 0.05, 0.1), True))]
+
+
+def case_scene(name):
+    wall_mat = {"default": 20, "non_metal": 0, "metal": 6, "emissive": 15}.get(name, 0)
+    cells, mats, points, d = kat_scene(wall_mat)
+    if name == "glass_to_the_edge":
+        for x in range(3):
+            for y in range(2, 5):
+                for z in range(6, 9):
+                    cells[x + y * N + z * N * N] = 8
+    return cells, mats, points, d
+
+
+@pytest.mark.parametrize("name,wall,ray", DEEP_CASES, ids=[c[0] for c in DEEP_CASES])
+def test_trace_deeper_every_branch(pkg, orc, name, wall, ray):
+    """Trace(ray, 2 / 3 / 5) over SEEDS[:8] per case: the recursion past the first bounce (the
+    stream handed from one level to the next, inside_glass carried along, the products folded on
+    the way back) equals the numpy restatement bit for bit, and so do the shadow-ray and DDA-cell
+    counts."""
+    cells, mats, points, d = case_scene(name)
+    vols = [Vol(cells, N)]
+    o = orc.Oracle(pkg.abi, to_oracle(pkg, orc, cells, mats, points, d, vols))
+    org, dirn, inside = ray
+    seeds = SEEDS[:8]
+    rays = api_rays(pkg.abi, [(org, dirn, 1e34, inside)] * len(seeds))
+    h = o.find_nearest(rays)[0]
+    assert h.material == wall, (name, h.material)
+    for depth in DEPTHS:
+        got, st = o.trace(rays, np.array(seeds, np.uint32), depth, (0.392, 0.584, 0.829), 3)
+        shadows = cells_n = 0
+        for i, seed in enumerate(seeds):
+            exp, s = _expected(cells, mats, points, d, vols, org, dirn, inside, seed, depth)
+            assert np.array_equal(fbits(got[i]), fbits(exp)), (name, depth, hex(seed), got[i], exp)
+            shadows += s.shadows
+            cells_n += s.cells
+        assert (st.shadow_rays, st.dda_cells) == (shadows, cells_n), (name, depth)
+
+
 def test_branch_arms_are_covered():
     """The seeds above take both arms of the random decisions the KATs exist for: the
     non-metal Schlick draw (diffuse / specular), glass reflect and refract from outside and
-    from inside after FindMaterialExit, and the smoke scatter draw after FindSmokeExit."""
+    from inside after FindMaterialExit, and the smoke scatter draw after FindSmokeExit.  Deeper
+    than one bounce (DEPTHS over SEEDS[:8]) the glass march that leaves the grid and a smoke
+    scatter followed by a further hit occur as well."""
     arms = set()
     for name, wall, (org, dirn, inside) in CASES:
         wall_mat = {"default": 20, "non_metal": 0, "metal": 6, "emissive": 15}.get(name, 0)
@@ -652,6 +696,42 @@ def test_branch_arms_are_covered():
             ("glass", "inside", "refract", "exit"), ("glass", "inside", "reflect", "exit"),
             ("smoke", "inside", "scatter"), ("smoke", "inside", "pass"), ("smoke", "outside", "pass")}
     assert need <= arms, sorted(need - arms)
+    deep, scatter_then_hit = set(), False
+    for name, wall, (org, dirn, inside) in DEEP_CASES:
+        cells, mats, points, d = case_scene(name)
+        for seed in SEEDS[:8]:
+            for depth in DEPTHS:
+                s = Scene([Vol(cells, N)], mats, points, d)
+                hits = []
+                find = s.find_nearest
+                s.find_nearest = lambda ray, find=find, hits=hits: hits.append((len(s.arms_log), find(ray), ray.mat)) or hits[-1][1]
+                s.arms_log = _ArmLog(s)
+                s.trace(Ray(v3(*org), v3(*dirn), inside=inside), depth, Rng(seed))
+                deep |= s.arms
+                # a smoke scatter, and a later FindNearest of the same path that hits something
+                for at, arm in s.arms_log.order:
+                    if arm[0] == "smoke" and arm[-1] == "scatter":
+                        scatter_then_hit |= any(n > at and m != NONE for n, _, m in hits)
+    assert any(a[0] == "glass" and a[-1] == "left grid" for a in deep), sorted(deep)
+    assert scatter_then_hit
+
+
+class _ArmLog:
+    """Scene.arms with the order of the additions kept: (arms added before, arm)."""
+
+    def __init__(self, scene):
+        self.order = []
+        log, inner = self, scene.arms
+
+        class Arms(set):
+            def add(self, arm):
+                log.order.append((len(log.order), arm))
+                set.add(self, arm)
+
+        scene.arms = Arms(inner)
+
+    def __len__(self):
+        return len(self.order)
 
 
 def _messy_volume(cells):
@@ -727,22 +807,26 @@ def test_setup3ddda_general_and_sse_sum_order(pkg, orc):
 
 @pytest.mark.gpu
 def test_kat_paths_on_device(pkg):
-    """The same depth-1 KATs through the library's vpx_trace on the GPU: bit for bit equal
+    """The same KATs through the library's vpx_trace on the GPU — depth 1 over every seed, depths
+    2, 3 and 5 over SEEDS[:8], the glass march that leaves the grid included: bit for bit equal
     to the numpy restatement (no oracle in between)."""
     torch = pytest.importorskip("torch")
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
-    for name, wall, (org, dirn, inside) in CASES:
-        wall_mat = {"default": 20, "non_metal": 0, "metal": 6, "emissive": 15}.get(name, 0)
-        cells, mats, points, d = kat_scene(wall_mat)
+    for name, wall, (org, dirn, inside) in DEEP_CASES:
+        cells, mats, points, d = case_scene(name)
         vols = [Vol(cells, N)]
         desc = to_oracle(pkg, None, cells, mats, points, d, vols)
         ctx = pkg.context.Context(0)
         ctx.load_scene(desc)
-        rays = api_rays(pkg.abi, [(org, dirn, 1e34, inside)] * len(SEEDS))
-        got = ctx.trace(rays, np.array(SEEDS, np.uint32), 1, (0.392, 0.584, 0.829), 3)
-        got = got[0] if isinstance(got, tuple) else got
+        got = {}
+        for depth in (1,) + DEPTHS:
+            seeds = SEEDS if depth == 1 else SEEDS[:8]
+            rays = api_rays(pkg.abi, [(org, dirn, 1e34, inside)] * len(seeds))
+            g = ctx.trace(rays, np.array(seeds, np.uint32), depth, (0.392, 0.584, 0.829), 3)
+            got[depth] = (seeds, g[0] if isinstance(g, tuple) else g)
         ctx.close()
-        for i, seed in enumerate(SEEDS):
-            exp, _ = _expected(cells, mats, points, d, vols, org, dirn, inside, seed, 1)
-            assert np.array_equal(fbits(np.asarray(got[i], np.float32)), fbits(exp)), (name, hex(seed))
+        for depth, (seeds, g) in got.items():
+            for i, seed in enumerate(seeds):
+                exp, _ = _expected(cells, mats, points, d, vols, org, dirn, inside, seed, depth)
+                assert np.array_equal(fbits(np.asarray(g[i], np.float32)), fbits(exp)), (name, depth, hex(seed))
