@@ -344,6 +344,32 @@ VPX_HD uint32_t load_u8(const uint8_t* p, uint32_t i) {
     return p[i];
 #endif
 }
+// The bit of cell (X, Y, Z) in its brick's l1 word, lx + 4 ly + 16 lz, as a 64-bit shift reads it:
+// the coordinates are shifted into place whole and only the amount's six bits are kept (four
+// operations where masking each coordinate first takes six).
+// (Through lshl2_or the device keeps that form: left to itself the compiler masks each coordinate
+// again.  An asm statement inside the run loop kept the pool kernels' loop from unrolling, so only
+// the walk kinds with `packed` take these forms.)
+VPX_HD uint32_t lshl2_or(uint32_t a, uint32_t b) {  // a << 2 | b
+#if defined(__HIP_DEVICE_COMPILE__)
+    uint32_t r;
+    asm("v_lshl_or_b32 %0, %1, 2, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+#else
+    return a << 2 | b;
+#endif
+}
+VPX_HD uint32_t cell_bit(uint32_t X, uint32_t Y, uint32_t Z) { return lshl2_or(lshl2_or(Z, Y & 3u), X & 3u) & 63u; }
+// (a ^ b) + c in one operation.
+VPX_HD uint32_t xor_add(uint32_t a, uint32_t b, uint32_t c) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    uint32_t r;
+    asm("v_xad_u32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
+    return r;
+#else
+    return (a ^ b) + c;
+#endif
+}
 // (k: the brick's plane byte, already loaded)
 template <uint32_t MINC = kMinCube>
 VPX_HD int classify_dfp_byte(Walk& w, const GridView& g, uint32_t k) {
@@ -380,7 +406,8 @@ VPX_HD uint32_t sec_axis(const Walk& w) { return sec_axis(dom_axis(w), w.dx, w.d
 // classify_dfp on the axis planes: apar = (octant * 3 + axis) * nb2^3 (plane_parent of the
 // plane's index), one load per step: the 32-bit word of dfw, or on the host dfa's 16 bits.  An empty brick skips (class 2) when its cube
 // reaches MINC or its box's length MINL; m1 gets the word (cube_dfp / len_dfa read it back).
-template <uint32_t MINC = kMinCube, uint32_t MINL = 2>
+// BIT6: the cell's bit through cell_bit (the walk kinds with `packed`).
+template <uint32_t MINC = kMinCube, uint32_t MINL = 2, bool BIT6 = false>
 VPX_HD int classify_axis_o(Walk& w, const GridView& g, uint32_t apar) {
     const uint32_t bx = w.X >> 2, by = w.Y >> 2, bz = w.Z >> 2, np = g.nb2;
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -396,7 +423,7 @@ VPX_HD int classify_axis_o(Walk& w, const GridView& g, uint32_t apar) {
 #endif
     if (kl == 0u) {
         w.m1 = load_mask(g.l1, blk_index(bx, by, bz, np));
-        const uint32_t cb = (w.X & 3u) | ((w.Y & 3u) << 2) | ((w.Z & 3u) << 4);
+        const uint32_t cb = BIT6 ? cell_bit(w.X, w.Y, w.Z) : (w.X & 3u) | ((w.Y & 3u) << 2) | ((w.Z & 3u) << 4);
         return ((w.m1 >> cb) & 1ull) ? 0 : 1;
     }
     w.m1 = kl;
@@ -441,6 +468,44 @@ VPX_HD void df_box_axis(const Walk& w, uint32_t n, uint32_t k, uint32_t L, uint3
     }
 }
 
+// The packed selectors of a walk: which byte of a dfw word holds each axis's extent is fixed per
+// ray (dom_axis / sec_axis / wid_dfw's shift), so it is worked out once per walk and kept as
+// three shifts, axis q's in bits 8q .. 8q + 4: 8 (L) for `axis`, 16 or 24 (wid_dfw's M) for `sec`
+// and 0 (k) for the third.  df_box_sel reads them back with two bit-field extracts per axis
+// where df_box_axis selects on q == axis and q == sec three times over, behind dom_axis' and
+// sec_axis' five float compares.  The axes come from dom_axis / sec_axis as before (ties,
+// infinities and NaNs fall where those compares put them) and the signs are still the walk's own.
+VPX_HD uint32_t box_sel(uint32_t axis, uint32_t sec) {
+    const uint32_t third = 3u - axis - sec;
+    return (8u << (8u * axis)) | ((sec < third ? 16u : 24u) << (8u * sec));
+}
+VPX_HD uint32_t box_sel(const Walk& w) {
+    const uint32_t axis = dom_axis(w);
+    return box_sel(axis, sec_axis(axis, w.dx, w.dy, w.dz));
+}
+// The byte of kl at the shift in s's low five bits.
+VPX_HD uint32_t sel_byte(uint32_t kl, uint32_t s) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    uint32_t r;
+    asm("v_bfe_u32 %0, %1, %2, 8" : "=v"(r) : "v"(kl), "v"(s));  // the offset operand reads five bits
+    return r;
+#else
+    return (kl >> (s & 31u)) & 255u;
+#endif
+}
+// df_box_axis for a dfw word `kl` from the walk's packed selectors: the same box.
+VPX_HD void df_box_sel(const Walk& w, uint32_t n, uint32_t kl, uint32_t sel, uint32_t lo[3], uint32_t hi[3]) {
+    const uint32_t c[3] = {w.X, w.Y, w.Z};
+    const int32_t sg[3] = {w.sx, w.sy, w.sz};
+    for (uint32_t q = 0; q < 3; ++q) {
+        const uint32_t e4 = sel_byte(kl, sel >> (8u * q)) * 4u;
+        const uint32_t b = c[q] & ~3u;
+        const uint32_t up = b + e4 - 1u, dn = b + 4u > e4 ? b + 4u - e4 : 0u;
+        lo[q] = sg[q] > 0 ? c[q] : dn;
+        hi[q] = sg[q] > 0 ? (up < n - 1u ? up : n - 1u) : c[q];
+    }
+}
+
 // The chosen axis' cell and head advance (shared by both forms of step1).
 VPX_HD bool step1_commit(Walk& w, uint32_t n, bool ax, bool ay, bool az) {
     w.X += ax ? (uint32_t)w.sx : 0u;
@@ -466,8 +531,8 @@ VPX_HD bool step1(Walk& w, uint32_t n) {
     const bool xy = w.tx < w.ty;
     const float a = xy ? w.tx : w.ty;
     const bool nz = a < w.tz;
-    const bool ax = xy && nz;
-    const bool ay = !xy && nz;
+    const bool ax = xy & nz;
+    const bool ay = nz & !ax;  // (!xy && nz, from the masks at hand: no second compare of the heads)
     const bool az = !nz;
     w.t = nz ? a : w.tz;
     return step1_commit(w, n, ax, ay, az);
@@ -600,7 +665,7 @@ VPX_HD bool seg_params_nb(float a, float d, uint32_t& b, uint32_t& c, uint32_t& 
     const uint32_t ab = fbits(a), db = fbits(d);
     const uint32_t ea = ab >> 23, ed = db >> 23;
     const uint32_t sh = ea - ed;  // meaningful when ok
-    const uint32_t shc = sh > 24u ? 24u : (sh < 1u ? 1u : sh);
+    const uint32_t sh1 = sh > 1u ? sh : 1u, shc = sh1 < 24u ? sh1 : 24u;  // sh clamped to [1, 24]: one med3
     const uint32_t md = (db & 0x7fffffu) | 0x800000u;
     const uint32_t rem = md & ((1u << shc) - 1u), half = 1u << (shc - 1u);
     const uint32_t c0 = md >> shc;
@@ -609,7 +674,8 @@ VPX_HD bool seg_params_nb(float a, float d, uint32_t& b, uint32_t& c, uint32_t& 
     c = tie ? c0 + (c0 & 1u) : c0 + (rem > half ? 1u : 0u);
     b = tie ? b0 + ((b0 + c0) & 1u) - (c0 & 1u) : b0;
     e = ea;
-    return (ea - 1u < 254u) & (ed - 1u < 254u) & (ed < ea) & (sh <= 24u) & (c != 0u);
+    // (sh - 1 < 24: ed < ea and sh <= 24 in one compare; ed >= ea wraps far above)
+    return (ea - 1u < 254u) & (ed - 1u < 254u) & (sh - 1u < 24u) & (c != 0u);
 }
 
 // ceil(p / c) clamped to 1025 (p <= 2^24 + 1, 1 <= c < 2^24).  q's error is far below 1
@@ -914,8 +980,10 @@ VPX_HD bool gate_open(const Walk& w, uint32_t gate) {
 // with g.dfw widened along its second.  `gate` (gate_word, 0: none): a class-2 brick is stepped
 // through while the maturity gate is shut, as the walkers do for the kinds with `gate`;
 // bits 5-7 of it: the further segments its skips may take (skip_box_lean's MORE, up to 4); bit 8
-// (kGatePre): its skips take the plain-step prefix (skip_box_lean's PRE).
+// (kGatePre): its skips take the plain-step prefix (skip_box_lean's PRE); bit 9 (kGatePacked): its
+// boxes come through the packed selectors (box_sel / df_box_sel), as in the walk kinds with `packed`.
 constexpr uint32_t kGatePre = 1u << 8;
+constexpr uint32_t kGatePacked = 1u << 9;
 template <bool PRE>
 VPX_HD int skip_box_lean_more(Walk& w, uint32_t lo[3], uint32_t hi[3], float bound, uint32_t& cells, uint32_t more) {
     return more == 0u   ? skip_box_lean<true, 0, PRE>(w, lo, hi, bound, cells)
@@ -928,6 +996,8 @@ VPX_HD bool walk_skip(const GridView& g, Walk& w, float bound, uint32_t& cells, 
     const bool wide = g.dfw != nullptr, axes = wide || g.dfa != nullptr;
     const uint32_t axis = dom_axis(w), sec = wide ? sec_axis(w) : 3u;
     const uint32_t apar = plane_parent(g, (w.osh >> 3) * 3u + axis);
+    const bool packed = wide && (gate & kGatePacked);
+    const uint32_t sel = packed ? box_sel(axis, sec) : 0u;
     for (;;) {
         if (!(w.t < bound)) return false;
         const int cls = axes ? classify_axis_o(w, g, apar) : classify(w, g);
@@ -937,7 +1007,8 @@ VPX_HD bool walk_skip(const GridView& g, Walk& w, float bound, uint32_t& cells, 
         }
         if (cls == 2 && gate_open(w, gate)) {
             uint32_t lo[3], hi[3];
-            if (axes) df_box_axis(w, g.n, cube_dfp(w), len_dfa(w), axis, lo, hi, sec, wide ? wid_dfw(w, axis, sec) : 0u);
+            if (packed) df_box_sel(w, g.n, (uint32_t)w.m1, sel, lo, hi);
+            else if (axes) df_box_axis(w, g.n, cube_dfp(w), len_dfa(w), axis, lo, hi, sec, wide ? wid_dfw(w, axis, sec) : 0u);
             else df_box(w, g.n, cube_l1(w), lo, hi);
             const int sr = (gate & kGatePre) ? skip_box_lean_more<true>(w, lo, hi, bound, cells, (gate >> 5) & 7u)
                                              : skip_box_lean_more<false>(w, lo, hi, bound, cells, (gate >> 5) & 7u);

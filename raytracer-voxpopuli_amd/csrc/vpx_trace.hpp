@@ -532,6 +532,8 @@ __device__ __forceinline__ bool walk_wave(const skip::GridView& g, skip::Walk& w
                   "walk_wave: the gate's exponent margin and event count (skip::gate_word's ranges)");
     // the ray's plane: its (octant, dominant axis)'s
     const uint32_t opar = skip::plane_parent(g, (w.osh >> 3) * 3u + skip::dom_axis(w));
+    // the packed selectors of its boxes, once per walk (KIND::packed)
+    const uint32_t sel = KIND::packed ? skip::box_sel(w) : 0u;
     int mode = POOL ? *pmode : kStep;
     int last = REC ? *plast : -1;
     VPX_PH(uint64_t cs = 0, ck = 0, ns = 0, nk = 0, ls = 0, lk = 0, fb = 0, cf = 0;)
@@ -558,7 +560,7 @@ __device__ __forceinline__ bool walk_wave(const skip::GridView& g, skip::Walk& w
                     if (!(w.t < bound)) {
                         mode = kMiss;
                     } else {
-                        int cls = skip::classify_axis_o<KIND::minc, KIND::minlen>(w, g, opar);
+                        int cls = skip::classify_axis_o<KIND::minc, KIND::minlen, KIND::packed>(w, g, opar);
                         if (KIND::gate) {  // an immature lane steps through its empty brick
                             float dx = w.dx, dy = w.dy, dz = w.dz;
                             asm volatile("" : "+v"(dx), "+v"(dy), "+v"(dz));  // the tdeltas' compares stay here
@@ -566,10 +568,22 @@ __device__ __forceinline__ bool walk_wave(const skip::GridView& g, skip::Walk& w
                         }
                         // the class's outcome by selects: 0 = the solid cell (visited, hit), 2 =
                         // skip; 1 / 3 visit the cell and run on in the brick
-                        cells += cls != 2 ? 1u : 0u;
-                        mode = cls == 0 ? kHit : (cls == 2 ? kSkip : mode);
+                        if (KIND::packed) {
+                            // (the same from a table, four bits per class: the lane's new mode, which
+                            // is kStep here, and whether the cell is visited; no compare, no select)
+                            static_assert(kStep == 0 && kSkip == 1 && kHit == 3, "walk_wave: the class table's modes");
+                            const uint32_t ent = (0x4147u >> (4u * (uint32_t)cls)) & 7u;
+                            cells += ent >> 2;
+                            mode = (int)(ent & 3u);
+                        } else {
+                            cells += cls != 2 ? 1u : 0u;
+                            mode = cls == 0 ? kHit : (cls == 2 ? kSkip : mode);
+                        }
                         if (cls & 1) {
-                            const uint64_t solid = cls == 1 ? w.m1 : 0ull;
+                            // class 1 reads the brick's cell mask, class 3 (all empty) nothing:
+                            // the mask's bit is kept under c1 = 1 / 0 (no select of the word)
+                            const uint64_t solid = w.m1;
+                            const uint32_t c1 = ((uint32_t)cls ^ 3u) >> 1;
 #pragma unroll
                             for (int r = 0; r < kRun; ++r) {
                                 const uint32_t ox = w.X, oy = w.Y, oz = w.Z;
@@ -579,10 +593,14 @@ __device__ __forceinline__ bool walk_wave(const skip::GridView& g, skip::Walk& w
                                 // cell is visited, a solid one ends the walk
                                 const bool ing = skip::step1<KIND::min2>(w, g.n);
                                 if (REC) last = stepped_axis(w, ox, oy);
-                                const bool inb = r + 1 < kRun && ((w.X ^ ox) | (w.Y ^ oy) | (w.Z ^ oz)) <= 3u;
+                                // (one coordinate moved, so the sum of the three differences is their OR)
+                                const uint32_t moved = KIND::packed ? skip::xor_add(w.Z, oz, skip::xor_add(w.Y, oy, w.X ^ ox))
+                                                                    : (w.X ^ ox) | (w.Y ^ oy) | (w.Z ^ oz);
+                                const bool inb = r + 1 < kRun && moved <= 3u;
                                 const bool inbound = w.t < bound;
-                                const bool sol =
-                                    (solid >> ((w.X & 3u) | ((w.Y & 3u) << 2) | ((w.Z & 3u) << 4))) & 1ull;
+                                const uint32_t cb =
+                                    KIND::packed ? skip::cell_bit(w.X, w.Y, w.Z) : (w.X & 3u) | ((w.Y & 3u) << 2) | ((w.Z & 3u) << 4);
+                                const bool sol = ((uint32_t)(solid >> cb) & c1) != 0u;
                                 const bool visit = ing && inb && inbound;
                                 cells += visit ? 1u : 0u;
                                 mode = !ing || (inb && !inbound) ? kMiss : (visit && sol ? kHit : mode);
@@ -604,10 +622,14 @@ __device__ __forceinline__ bool walk_wave(const skip::GridView& g, skip::Walk& w
         VPX_MARK("skip phase");
         if (mode == kSkip) {
             uint32_t lo[3], hi[3];
-            float dx = w.dx, dy = w.dy, dz = w.dz;
-            if (KIND::local) asm volatile("" : "+v"(dx), "+v"(dy), "+v"(dz));  // the axes' compares are not hoisted
-            const uint32_t axis = skip::dom_axis(dx, dy, dz), sec = skip::sec_axis(axis, dx, dy, dz);
-            skip::df_box_axis(w, g.n, skip::cube_dfp(w), skip::len_dfa(w), axis, lo, hi, sec, skip::wid_dfw(w, axis, sec));
+            if (KIND::packed) {
+                skip::df_box_sel(w, g.n, (uint32_t)w.m1, sel, lo, hi);
+            } else {
+                float dx = w.dx, dy = w.dy, dz = w.dz;
+                if (KIND::local) asm volatile("" : "+v"(dx), "+v"(dy), "+v"(dz));  // the axes' compares are not hoisted
+                const uint32_t axis = skip::dom_axis(dx, dy, dz), sec = skip::sec_axis(axis, dx, dy, dz);
+                skip::df_box_axis(w, g.n, skip::cube_dfp(w), skip::len_dfa(w), axis, lo, hi, sec, skip::wid_dfw(w, axis, sec));
+            }
             const int sr = skip::skip_box_lean<KIND::seg2, 0, KIND::pre>(w, lo, hi, bound, cells);  // 2 (refused): a plain step
             VPX_MARK("skip end");
             VPX_PH(fb += __popcll(__ballot(sr == 2));)

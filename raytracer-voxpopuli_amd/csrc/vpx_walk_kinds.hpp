@@ -37,6 +37,14 @@ struct NearestWalk {
     // The skip phase works its axes out behind a barrier, so the compares' results are not kept
     // in scratch all walk long.  Without it anywhere C1 gained 3.3 % from round 8 instead of 5.9 %.
     static constexpr bool local = true;
+    // The instruction forms of round 16: the boxes' byte selectors packed once per walk (skip::box_sel,
+    // read back by skip::df_box_sel) instead of dom_axis / sec_axis and the select chains in every
+    // skip phase; the class outcomes from a table; the cell's bit and the moved test in one-instruction
+    // asm forms (skip::cell_bit, skip::xor_add).  The word is live through the walk loops and an asm
+    // statement kept the pool kernels' run loop from unrolling, so only k_frame0's kinds take them:
+    // C1 0.3790-0.3834 against the parent's 0.3867-0.3922 (eight interleaved runs); the selectors
+    // alone 0.3836-0.3887 against 0.3876-0.3930, not enough by themselves.
+    static constexpr bool packed = false;
     // The maturity gate (skip::gate_open): a class-2 lane whose skip would be clipped at an
     // immature axis's next event (exponent of tmax below exponent of tdelta + gate_g, that event
     // within gate_n events of the dominant axis) steps instead.  For the shadow walks of the
@@ -51,6 +59,7 @@ struct NearestWalk {
 struct FrameNearestWalk : NearestWalk {
     static constexpr uint32_t passes = 4;
     static constexpr bool pre = true;
+    static constexpr bool packed = true;
 };
 // The bounce walks (k_tail, k_nearest_tile, k_nearest_pool): rays leaving surfaces.
 struct BounceWalk : NearestWalk {
@@ -90,6 +99,7 @@ struct ShadowWalk : NearestWalk {
 struct FrameShadowWalk : ShadowWalk {
     static constexpr uint32_t passes = 3;
     static constexpr bool min2 = true;
+    static constexpr bool packed = true;
 };
 // k_shadow_pool (96 VGPRs, 5 waves/SIMD).  It takes the two-compare step without spilling: C3
 // 3.684-3.719 vs 3.724-3.756 (round 3).  Its lanes start at different times, so a gated lane

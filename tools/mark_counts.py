@@ -5,7 +5,8 @@
 
 Counts follow the listing's order (the compiler's block layout), so code the compiler moved across
 a mark is counted where it landed.  A mark inside a loop the compiler unrolled appears once per copy:
-sections of the same name are summed.
+sections of the same name are summed.  cmp / cnd / mov: v_cmp*, v_cndmask* and v_mov* (all VALU);
+carry: v_addc* / v_subb*; nop: s_nop instructions, wait: the wait states they idle (s_nop N: N + 1).
 """
 import collections
 import re
@@ -50,6 +51,13 @@ def count(body):
         r["div"] += op.startswith("v_div_fixup")
         r["f64"] += op.endswith("_f64")
         r["scratch"] += op.startswith("scratch_")
+        r["cmp"] += op.startswith("v_cmp")
+        r["cnd"] += op.startswith("v_cndmask")
+        r["mov"] += op.startswith("v_mov")
+        r["carry"] += op.startswith(("v_addc", "v_subb"))
+        if op == "s_nop":  # s_nop N idles N + 1 wait states
+            r["nop"] += 1
+            r["wait"] += int(t.split()[1], 0) + 1
     return rows
 
 
@@ -59,12 +67,15 @@ def main():
         body = ks[want]
         rows = count(body)
         print(f"== {want}")
-        print(f"{'all':>6} {'VALU':>6} {'SALU':>6} {'lane':>5} {'div':>4} {'f64':>4} {'scr':>4}  section")
+        cols = [("all", 6, "all"), ("VALU", 6, "valu"), ("SALU", 6, "salu"), ("lane", 5, "lane"), ("div", 4, "div"),
+                ("f64", 4, "f64"), ("scr", 4, "scratch"), ("cmp", 5, "cmp"), ("cnd", 5, "cnd"), ("mov", 5, "mov"),
+                ("carry", 6, "carry"), ("nop", 4, "nop"), ("wait", 5, "wait")]
+        print(" ".join(f"{h:>{w}}" for h, w, _ in cols) + "  section")
         tot = collections.Counter()
-        for sec, r in rows.items():
-            tot.update(r)
-            print(f"{r['all']:>6} {r['valu']:>6} {r['salu']:>6} {r['lane']:>5} {r['div']:>4} {r['f64']:>4} {r['scratch']:>4}  {sec}")
-        print(f"{tot['all']:>6} {tot['valu']:>6} {tot['salu']:>6} {tot['lane']:>5} {tot['div']:>4} {tot['f64']:>4} {tot['scratch']:>4}  total")
+        for sec, r in list(rows.items()) + [("total", tot)]:
+            if r is not tot:
+                tot.update(r)
+            print(" ".join(f"{r[k]:>{w}}" for _, w, k in cols) + f"  {sec}")
 
 
 if __name__ == "__main__":
