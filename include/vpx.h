@@ -51,6 +51,9 @@
  *   vpx_grid_generate_noise  Scene::GenerateSomeNoise    template/scene.cpp:226-282 (renderer.cpp:2883-2898)
  *                            Scene::GenerateSomeSmoke    template/scene.cpp:285-356 (renderer.cpp:626, 2174)
  *   vpx_grid_brush        Scene::Set over a sphere / box   template/scene.h (Set), edits of a few voxels
+ *   vpx_grid_stamp        Scene::Set over an oriented model  template/scene.h (Set); a prop put into, dug
+ *                                                          out of or moved within a world that holds content
+ *   vpx_model_capture / vpx_model_read   no reference counterpart; a box of a grid as a resident model
  *   vpx_grid_read_box     Scene::grid read back (debug)  template/scene.h:258
  *   vpx_set_volumes       Renderer::voxelVolumes      renderer.h:211
  *   vpx_set_materials     Renderer::materials         renderer.h:190, MaterialSetUp renderer.cpp:357-443
@@ -74,6 +77,7 @@
  *   vpx_noise_generate_host  the two generators' loops          template/scene.cpp:226-356
  *   vpx_perlin3              the noise field (this project's definition, DESIGN parity decision 9)
  *   vpx_brush_apply_host     vpx_grid_brush's cells on a host grid
+ *   vpx_stamp_apply_host     vpx_grid_stamp's cells on a host grid
  */
 #ifndef VPX_H_
 #define VPX_H_
@@ -414,6 +418,73 @@ int vpx_grid_brush(vpx_ctx* ctx, uint32_t grid_id, const vpx_brush* brushes, uin
    cells == NULL or n outside vpx_upload_grid's range. */
 int vpx_brush_apply_host(uint8_t* cells, uint32_t n, const vpx_brush* brushes, uint32_t count,
                          vpx_brush_result* out /* may be NULL */);
+
+#define VPX_STAMP_GRID_BYTES 0x1u  /* model bytes are grid bytes: 255 is empty, 0 is a material
+                                      (what vpx_model_capture stores).  Default: 0 is empty and
+                                      byte k writes k, vpx_grid_load_model's convention */
+#define VPX_STAMP_CONSTANT   0x2u  /* non-empty voxels write `value` instead of their own byte;
+                                      value 255 digs the model's shape out */
+/* orient: which model axis feeds each grid axis, and mirrored or not.
+   bits 0-1 / 2-3 / 4-5: model axis (0 = x, 1 = y, 2 = z) of grid x / y / z, a permutation;
+   bits 8 / 9 / 10: grid x / y / z runs against that model axis.  All other bits 0. */
+#define VPX_ORIENT_IDENTITY   0x24u /* x<-x, y<-y, z<-z */
+#define VPX_ORIENT_LOAD_MODEL 0x18u /* x<-x, y<-z, z<-y: Scene::LoadModel's swap at scale 1 */
+typedef struct vpx_stamp {           /* 32 bytes */
+    uint32_t model_id;               /* a resident model (vpx_model_upload, vpx_model_capture) */
+    int32_t  origin[3];              /* grid cell of the box's low corner; may lie outside the grid */
+    uint32_t orient;                 /* VPX_ORIENT_*, or any of the 48 */
+    uint32_t flags;                  /* VPX_STAMP_* */
+    uint8_t  value;                  /* CONSTANT: the byte written */
+    uint8_t  match_lo, match_hi;     /* the filter on the cell's current byte, as vpx_brush */
+    uint8_t  reserved;               /* 0 */
+    uint32_t reserved2;              /* 0 */
+} vpx_stamp;
+/* Device-side edit: `count` (1..256) resident models gathered into an existing grid, in order,
+   one launch each, so a later stamp's filter sees the bytes an earlier one left; all arithmetic
+   is integer.  With s = (sx, sy, sz) the model's size, a_q the model axis of grid axis q and
+   e_q = s[a_q]:
+     - the stamp's box is origin[q] .. origin[q] + e_q - 1 per axis, clipped to [0, n) in int64;
+       a box that holds no cell is skipped;
+     - a cell g of the clipped box has d_q = g[q] - origin[q], m[a_q] = (flip_q ? e_q - 1 - d_q : d_q)
+       and reads v = voxels[m0 + m1*sx + m2*sx*sy];
+     - the voxel is empty when v == 0, or when v == 255 under GRID_BYTES; an empty voxel leaves
+       the cell alone;
+     - otherwise w = (CONSTANT ? value : v), and a cell holding c with match_lo <= c <= match_hi
+       and c != w becomes w and counts as changed.  Under the default convention a voxel byte
+       255 therefore writes NONE.
+   A cell reads one voxel and is written by its own thread only, so the result does not depend
+   on the order the device works in.  Then ONE region-local refresh over the stamps' clipped
+   boxes, as vpx_grid_brush ends (DESIGN §4 "Stamps"); `out` is filled as for brushes.  The call
+   allocates nothing beyond the refresh's record, which comes with the context's first edit.
+   VPX_E_INVALID: stamps == NULL, count outside 1..256, unknown grid, unknown model, an orient
+   whose axes are not a permutation or that has other bits set, unknown flags, reserved or
+   reserved2 != 0, match_lo > match_hi.  Like every world edit the call waits for the frames in
+   flight; a device set applies it to every member. */
+int vpx_grid_stamp(vpx_ctx* ctx, uint32_t grid_id, const vpx_stamp* stamps, uint32_t count,
+                   vpx_brush_result* out /* may be NULL */);
+/* Make (or replace) resident model `model_id` from the cells of a box of a grid, on the device:
+   raw grid bytes, model index x + y*dx + z*dx*dy = cell (x0 + x, y0 + y, z0 + z), so a stamp with
+   VPX_ORIENT_IDENTITY | VPX_STAMP_GRID_BYTES at (x0, y0, z0) puts it back.  Allocates like
+   vpx_model_upload; a failure leaves the id empty.  VPX_E_INVALID: unknown grid, model_id above
+   vpx_model_upload's cap, a dimension outside 1..256, a box not inside the grid.  Waits for the
+   frames in flight; a device set captures on every member. */
+int vpx_model_capture(vpx_ctx* ctx, uint32_t model_id, uint32_t grid_id, uint32_t x0, uint32_t y0, uint32_t z0,
+                      uint32_t dx, uint32_t dy, uint32_t dz);
+/* Debug read-back of a resident model: its size into size_out, and, when dst != NULL, its
+   sx*sy*sz bytes (a device set reads its first member).  VPX_E_INVALID: unknown model,
+   size_out == NULL, dst != NULL with cap < sx*sy*sz. */
+int vpx_model_read(vpx_ctx* ctx, uint32_t model_id, uint8_t* dst /* may be NULL: size only */, uint64_t cap,
+                   uint32_t size_out[3]);
+typedef struct vpx_stamp_source {    /* 24 bytes */
+    const uint8_t* voxels;           /* sx*sy*sz bytes, index x + y*sx + z*sx*sy */
+    uint32_t sx, sy, sz, reserved;   /* each dimension 1..256; reserved 0 */
+} vpx_stamp_source;
+/* The same stamps on a host grid of n^3 bytes (host only, the code the device runs); model_id
+   indexes `models`; `flipped` from the host level builder before and after.  VPX_E_INVALID as
+   above (an unknown model: model_id >= n_models, NULL voxels, a dimension outside 1..256, reserved
+   != 0), and for cells == NULL, models == NULL or n outside vpx_upload_grid's range. */
+int vpx_stamp_apply_host(uint8_t* cells, uint32_t n, const vpx_stamp_source* models, uint32_t n_models,
+                         const vpx_stamp* stamps, uint32_t count, vpx_brush_result* out /* may be NULL */);
 /* Debug read-back of a box of cells, host bytes x fastest: the inverse of vpx_grid_write_box
    (a device set reads its first member). */
 int vpx_grid_read_box(vpx_ctx* ctx, uint32_t grid_id, uint8_t* dst, uint32_t x0, uint32_t y0, uint32_t z0,

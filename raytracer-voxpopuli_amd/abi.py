@@ -188,6 +188,21 @@ class BrushResult(C.Structure):  # vpx_brush_result: cells changed, bricks whose
     _fields_ = [("changed", C.c_uint64), ("flipped", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+STAMP_GRID_BYTES, STAMP_CONSTANT = 1, 2  # VPX_STAMP_*
+ORIENT_IDENTITY, ORIENT_LOAD_MODEL = 0x24, 0x18  # VPX_ORIENT_*
+
+
+class Stamp(C.Structure):  # vpx_stamp: one resident model, where and how turned, the filter (vpx_grid_stamp)
+    _fields_ = [("model_id", C.c_uint32), ("origin", C.c_int32 * 3), ("orient", C.c_uint32), ("flags", C.c_uint32),
+                ("value", C.c_uint8), ("match_lo", C.c_uint8), ("match_hi", C.c_uint8), ("reserved", C.c_uint8),
+                ("reserved2", C.c_uint32)]
+
+
+class StampSource(C.Structure):  # vpx_stamp_source: a model in host memory (vpx_stamp_apply_host)
+    _fields_ = [("voxels", C.c_void_p), ("sx", C.c_uint32), ("sy", C.c_uint32), ("sz", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
 class PrevCamera(C.Structure):
     _fields_ = [("cam_pos", f3), ("left_normal", f3), ("right_normal", f3), ("top_normal", f3),
                 ("bottom_normal", f3), ("pad", C.c_float)]
@@ -221,7 +236,7 @@ STRUCT_SIZES = {PrevCamera: 64, Profile: 160, Volume: 160, Material: 32, PointLi
                 Sphere: 32, Triangle: 64, Camera: 80, FrameParams: 48, Ray: 32, Hit: 32, Stats: 40,
                 BvhTri: 36, BvhNode: 32, PlayerLight: 24, RayProbe: 16, RayFilter: 16, HitCell: 32, ModelLoad: 40, ModelResult: 16,
                 NoiseGen: 16, NoiseResult: 16, Brush: 48, BrushResult: 16, Denoise: 16, Cast: 16, Reproject: 168,
-                DenoiseVar: 32}
+                DenoiseVar: 32, Stamp: 32, StampSource: 24}
 
 
 def np_dtype(struct):
@@ -352,6 +367,11 @@ SIGNATURES = {
     "vpx_grid_brush": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(Brush), C.c_uint32, C.POINTER(BrushResult)]),
     "vpx_brush_apply_host": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(Brush), C.c_uint32, C.POINTER(BrushResult)]),
     "vpx_grid_level_words": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64]),
+    "vpx_grid_stamp": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(Stamp), C.c_uint32, C.POINTER(BrushResult)]),
+    "vpx_stamp_apply_host": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(StampSource), C.c_uint32, C.POINTER(Stamp), C.c_uint32,
+                                       C.POINTER(BrushResult)]),
+    "vpx_model_capture": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32] + [C.c_uint32] * 6),
+    "vpx_model_read": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint32)]),
 }
 
 _LIB = None

@@ -131,6 +131,32 @@ class Context:
         self._chk(self.lib.vpx_grid_brush(self.h, grid_id, arr, len(brushes), C.byref(res)), "vpx_grid_brush")
         return res
 
+    def grid_stamp(self, grid_id, stamps):
+        """Device-side edit (vpx_grid_stamp): a list of abi.Stamp (scene.stamp) gathered into the
+        grid in order, then one region-local refresh of the levels.  Returns the abi.BrushResult:
+        cells changed, bricks whose emptiness flipped."""
+        arr = (abi.Stamp * max(1, len(stamps)))(*stamps)
+        res = abi.BrushResult()
+        self._chk(self.lib.vpx_grid_stamp(self.h, grid_id, arr, len(stamps), C.byref(res)), "vpx_grid_stamp")
+        return res
+
+    def model_capture(self, model_id, grid_id, origin, shape):
+        """Resident model model_id made from the cells of the box at origin (x0, y0, z0) of shape
+        (dz, dy, dx), on the device (vpx_model_capture): raw grid bytes, so a stamp with
+        abi.STAMP_GRID_BYTES puts them back."""
+        dz, dy, dx = (int(s) for s in shape)
+        x0, y0, z0 = (int(s) for s in origin)
+        self._chk(self.lib.vpx_model_capture(self.h, model_id, grid_id, x0, y0, z0, dx, dy, dz), "vpx_model_capture")
+
+    def model_read(self, model_id):
+        """Debug read-back of a resident model (vpx_model_read): uint8 array of shape (sz, sy, sx)."""
+        size = (C.c_uint32 * 3)()
+        self._chk(self.lib.vpx_model_read(self.h, model_id, None, 0, size), "vpx_model_read")
+        sx, sy, sz = (int(s) for s in size)
+        out = np.empty((sz, sy, sx), np.uint8)
+        self._chk(self.lib.vpx_model_read(self.h, model_id, out.ctypes.data_as(C.c_void_p), out.size, size), "vpx_model_read")
+        return out
+
     def model_upload(self, model_id, size, voxels):
         """A resident model (vpx_model_upload): ogt_vox's voxel_data as scene.load_model returns
         it, size = (sx, sy, sz); voxels None removes it."""

@@ -15,6 +15,7 @@
 #include "vpx_model.hpp"
 #include "vpx_noise.hpp"
 #include "vpx_brush.hpp"
+#include "vpx_stamp.hpp"
 #include "vpx_denoise.hpp"
 #include "vpx_denoise_var.hpp"
 #include "vpx_reproject.hpp"
@@ -266,6 +267,9 @@ static_assert(sizeof(vpx_cast) == 16 && offsetof(vpx_cast, max_waves) == 4 && of
 static_assert(sizeof(vpx_model_load) == 40 && sizeof(vpx_model_result) == 16, "model load layout");
 static_assert(sizeof(vpx_noise_gen) == 16 && sizeof(vpx_noise_result) == 16, "noise generator layout");
 static_assert(sizeof(vpx_brush) == 48 && sizeof(vpx_brush_result) == 16, "brush layout");
+static_assert(sizeof(vpx_stamp) == 32 && offsetof(vpx_stamp, orient) == 16 && offsetof(vpx_stamp, value) == 24 &&
+                  offsetof(vpx_stamp, reserved2) == 28 && sizeof(vpx_stamp_source) == 24 && offsetof(vpx_stamp_source, sx) == 8,
+              "stamp layout");
 static_assert(sizeof(vpx_area_light) == 32 && sizeof(vpx_dir_light) == 24, "light layout");
 static_assert(sizeof(vpx_sphere) == 32 && sizeof(vpx_triangle) == 64, "shape layout");
 static_assert(sizeof(vpx_camera) == 80 && sizeof(vpx_frame_params) == 48, "camera/frame layout");
@@ -596,6 +600,37 @@ int vpx_brush_apply_host(uint8_t* cells, uint32_t n, const vpx_brush* brushes, u
     if (out) vpx::skip::build_masks_host(cells, n, l1.data(), before.data());
     vpx_brush_result res{};
     for (uint32_t i = 0; i < count; ++i) res.changed += vpx::brush::apply_host(cells, n, brushes[i]);
+    if (out) {
+        vpx::skip::build_masks_host(cells, n, l1.data(), after.data());
+        for (size_t i = 0; i < after.size(); ++i) res.flipped += (uint32_t)__builtin_popcountll(before[i] ^ after[i]);
+        *out = res;
+    }
+#endif
+    return VPX_OK;
+}
+
+// vpx_grid_stamp's cells on the host, through the plan and the per-cell rule the device runs
+// (vpx_stamp.hpp); `flipped` as above.
+int vpx_stamp_apply_host(uint8_t* cells, uint32_t n, const vpx_stamp_source* models, uint32_t n_models, const vpx_stamp* stamps,
+                         uint32_t count, vpx_brush_result* out) {
+    if (!cells || !models || n == 0 || n > 4096 || vpx::stamp::check_stamps(stamps, count)) return VPX_E_INVALID;
+    for (uint32_t i = 0; i < count; ++i) {
+        if (stamps[i].model_id >= n_models) return VPX_E_INVALID;
+        const vpx_stamp_source& m = models[stamps[i].model_id];
+        if (!m.voxels || m.reserved != 0 || !m.sx || !m.sy || !m.sz || m.sx > vpx::stamp::kMaxDim || m.sy > vpx::stamp::kMaxDim ||
+            m.sz > vpx::stamp::kMaxDim)
+            return VPX_E_INVALID;
+    }
+#if !defined(__HIP_DEVICE_COMPILE__)  // the host builders exist in the host pass only
+    const uint32_t nb1 = (n + 3) / 4, nb2 = (nb1 + 3) / 4, nb3 = (nb2 + 3) / 4;
+    std::vector<uint64_t> l1(64ull * nb2 * nb2 * nb2), before(64ull * nb3 * nb3 * nb3), after(before.size());
+    if (out) vpx::skip::build_masks_host(cells, n, l1.data(), before.data());
+    vpx_brush_result res{};
+    for (uint32_t i = 0; i < count; ++i) {
+        const vpx_stamp_source& m = models[stamps[i].model_id];
+        vpx::stamp::Plan p;
+        if (vpx::stamp::plan(stamps[i], m.sx, m.sy, m.sz, n, p)) res.changed += vpx::stamp::apply_host(cells, n, p, m.voxels);
+    }
     if (out) {
         vpx::skip::build_masks_host(cells, n, l1.data(), after.data());
         for (size_t i = 0; i < after.size(); ++i) res.flipped += (uint32_t)__builtin_popcountll(before[i] ^ after[i]);

@@ -13,6 +13,7 @@
 //   model_gather_k / model_random_k   the model loaders' placement (vpx_model.hpp).
 //   smoke_gen_k / noise_mark_k / noise_scan_k / noise_draw_k   the noise generators (vpx_noise.hpp).
 //   brush_k                       one brush edit (vpx_brush.hpp).
+//   stamp_k / capture_k           one model stamp (vpx_stamp.hpp); a box of a grid into a model.
 //   k_plane_key / k_atrous_lds / k_atrous_gather   the plane-keyed denoise (vpx_denoise.hpp).
 //   k_reproject_ids               the plane-keyed temporal reprojection (vpx_reproject.hpp).
 //   k_reproject_moments / k_var_estimate / k_atrous_var_lds / k_atrous_var_gather   the variance-guided
@@ -39,6 +40,7 @@
 #include "vpx_model.hpp"
 #include "vpx_noise.hpp"
 #include "vpx_brush.hpp"
+#include "vpx_stamp.hpp"
 #include "vpx_denoise.hpp"
 #include "vpx_denoise_var.hpp"
 #include "vpx_reproject.hpp"
@@ -1576,6 +1578,88 @@ __global__ __launch_bounds__(256) void brush_k(uint8_t* __restrict__ grid, uint3
     }
 }
 
+// One stamp over its clipped box (vpx_stamp.hpp's plan and per-cell rule): a gather, every cell
+// reads one voxel and is written by its own thread.  kWide (n % 16 == 0): a thread owns one
+// 16-byte-aligned span of a row that meets the box (spans [s0, s0 + spans) of the row), loads it
+// with one vector load, merges the cells inside the box and stores it once if a byte changed;
+// no model index is formed for a cell outside the box.  Otherwise one thread per cell.  The
+// changed cells are counted per wave, the ballots of the count's five bits, summed over the
+// wave's strides; one atomic per workgroup ends the kernel (16384 atomics on one address, one
+// per wave and stride, were the whole time of a 256^3 stamp: DESIGN §4 "Stamps").
+template <bool kWide>
+__global__ __launch_bounds__(256) void stamp_k(uint8_t* __restrict__ grid, uint32_t n, const uint8_t* __restrict__ vox,
+                                               stamp::Plan p, uint32_t s0, uint32_t spans, RefreshDev* rd) {
+    const uint32_t cy = p.hi[1] - p.lo[1] + 1, cz = p.hi[2] - p.lo[2] + 1;
+    const uint32_t per_row = kWide ? spans : p.hi[0] - p.lo[0] + 1;
+    const uint64_t total = (uint64_t)per_row * cy * cz, n64 = n;
+    unsigned long long wave = 0;  // cells this wave changed
+    for (uint64_t base = (uint64_t)blockIdx.x * blockDim.x; base < total; base += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t i = base + threadIdx.x;
+        uint32_t ch = 0;  // cells this thread changed, 0..16
+        if (i < total) {
+            const uint32_t k = (uint32_t)(i % per_row);
+            const uint32_t y = p.lo[1] + (uint32_t)((i / per_row) % cy), z = p.lo[2] + (uint32_t)(i / ((uint64_t)per_row * cy));
+            const int32_t row = stamp::row_base(p, y, z);
+            uint8_t* cells = grid + (y * n64 + z * n64 * n64);
+            if (kWide) {
+                const uint32_t x0 = (s0 + k) * 16u;
+                uint4* span = reinterpret_cast<uint4*>(cells + x0);
+                const uint4 in = *span;
+                uint32_t w[4] = {in.x, in.y, in.z, in.w};
+                const uint32_t first = x0 < p.lo[0] ? p.lo[0] - x0 : 0u, last = min(p.hi[0] - x0, 15u);
+                const int32_t m0 = row + p.step[0] * ((int32_t)(x0 + first) - p.origin[0]);
+                // the 16 voxel loads first, none waiting for a merge; a cell outside the box has no
+                // voxel of its own (its coordinate is out of range): its load repeats the nearest
+                // inside cell's and is not used
+                uint8_t v[16];
+#pragma unroll
+                for (uint32_t j = 0; j < 16; ++j) v[j] = vox[m0 + p.step[0] * (int32_t)(min(max(j, first), last) - first)];
+#pragma unroll
+                for (uint32_t j = 0; j < 16; ++j) {
+                    const uint32_t sh = 8 * (j & 3u);
+                    uint8_t out;
+                    if (stamp::writes(p, v[j], (uint8_t)(w[j >> 2] >> sh), out) && j >= first && j <= last) {
+                        w[j >> 2] = (w[j >> 2] & ~(255u << sh)) | (uint32_t)out << sh;
+                        ++ch;
+                    }
+                }
+                if (ch) *span = make_uint4(w[0], w[1], w[2], w[3]);
+            } else {
+                const uint32_t x = p.lo[0] + k;
+                uint8_t out;
+                if (stamp::writes(p, vox[row + p.step[0] * ((int32_t)x - p.origin[0])], cells[x], out)) cells[x] = out, ch = 1;
+            }
+        }
+#pragma unroll
+        for (uint32_t b = 0; b < (kWide ? 5u : 1u); ++b) wave += (unsigned long long)__popcll(__ballot((ch >> b) & 1u)) << b;
+    }
+    __shared__ unsigned long long waves[4];
+    if ((threadIdx.x & 63) == 0) waves[threadIdx.x >> 6] = wave;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const unsigned long long sum = waves[0] + waves[1] + waves[2] + waves[3];
+        if (sum) atomicAdd(&rd->changed, sum);
+    }
+}
+
+// vpx_model_capture: the cells of a box into a model, index x + y*dx + z*dx*dy.  kWide (the grid's
+// rows, x0 and dx are multiples of 16): 16 bytes per thread, loaded and stored as one vector.
+template <bool kWide>
+__global__ __launch_bounds__(256) void capture_k(const uint8_t* __restrict__ grid, uint32_t n, uint8_t* __restrict__ vox, uint32_t x0,
+                                                 uint32_t y0, uint32_t z0, uint32_t dx, uint32_t dy, uint32_t dz) {
+    const uint32_t per_row = kWide ? dx / 16u : dx;
+    const uint64_t total = (uint64_t)per_row * dy * dz, n64 = n;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (uint64_t)gridDim.x * blockDim.x) {
+        const uint32_t x = (uint32_t)(i % per_row) * (kWide ? 16u : 1u), y = (uint32_t)((i / per_row) % dy), z = (uint32_t)(i / ((uint64_t)per_row * dy));
+        const uint8_t* src = grid + ((x0 + x) + (y0 + y) * n64 + (z0 + z) * n64 * n64);
+        uint8_t* dst = vox + (x + (uint64_t)y * dx + (uint64_t)z * dx * dy);
+        if (kWide)
+            *reinterpret_cast<uint4*>(dst) = *reinterpret_cast<const uint4*>(src);
+        else
+            *dst = *src;
+    }
+}
+
 // Stage 0: the cell masks of the bricks [b0, b0 + c) from the edited cells, and l2's bits.  The
 // l1 word of an empty brick holds its distance-field bytes: a brick that stays empty keeps them,
 // one that empties gets 0 until stage 1 (it lies in E).  Flips are counted and boxed in rd.
@@ -3072,6 +3156,40 @@ int vpx_grid_brush(vpx_ctx* c, uint32_t id, const vpx_brush* brushes, uint32_t c
     return VPX_OK;
 }
 
+int vpx_grid_stamp(vpx_ctx* c, uint32_t id, const vpx_stamp* stamps, uint32_t count, vpx_brush_result* out) {
+    VPX_GROUP_ALL(c, vpx_grid_stamp(m_, id, stamps, count, out));
+    if (!c) return VPX_E_INVALID;
+    if (const char* why = stamp::check_stamps(stamps, count)) return fail(c, VPX_E_INVALID, why);
+    if (id >= c->grids.size() || !c->grids[id].ptr) return fail(c, VPX_E_INVALID, "unknown grid");
+    for (uint32_t i = 0; i < count; ++i)
+        if (stamps[i].model_id >= c->models.size() || !c->models[stamps[i].model_id].vox) return fail(c, VPX_E_INVALID, "unknown model");
+    auto& g = c->grids[id];
+    VPX_HIP(c, hipSetDevice(c->device));
+    VPX_HIP(c, sync_all(c));  // frames in flight still read the grid
+    if (int r = refresh_begin(c)) return r;
+    skip::Box3 boxes[stamp::kMaxStamps];
+    uint32_t n_boxes = 0;
+    const bool wide = (g.n % 16u) == 0;
+    for (uint32_t i = 0; i < count; ++i) {
+        const auto& m = c->models[stamps[i].model_id];
+        stamp::Plan p;
+        if (!stamp::plan(stamps[i], m.sx, m.sy, m.sz, g.n, p)) continue;
+        const uint32_t s0 = p.lo[0] >> 4, spans = (p.hi[0] >> 4) - s0 + 1;
+        const uint64_t threads = (uint64_t)(wide ? spans : p.hi[0] - p.lo[0] + 1) * (p.hi[1] - p.lo[1] + 1) * (p.hi[2] - p.lo[2] + 1);
+        const dim3 blocks((unsigned)std::min<uint64_t>(2048, (threads + 255) / 256));
+        if (wide)
+            hipLaunchKernelGGL(stamp_k<true>, blocks, dim3(256), 0, c->stream, g.ptr, g.n, (const uint8_t*)m.vox, p, s0, spans, c->d_refresh);
+        else
+            hipLaunchKernelGGL(stamp_k<false>, blocks, dim3(256), 0, c->stream, g.ptr, g.n, (const uint8_t*)m.vox, p, s0, spans, c->d_refresh);
+        VPX_HIP(c, hipGetLastError());
+        boxes[n_boxes++] = skip::Box3{{(int32_t)p.lo[0], (int32_t)p.lo[1], (int32_t)p.lo[2]}, {(int32_t)p.hi[0], (int32_t)p.hi[1], (int32_t)p.hi[2]}};
+    }
+    vpx_brush_result res{};
+    if (int r = refresh_levels(c, g, boxes, n_boxes, &res)) return r;
+    if (out) *out = res;
+    return VPX_OK;
+}
+
 int vpx_grid_fill(vpx_ctx* c, uint32_t id, uint8_t value) {
     VPX_GROUP_ALL(c, vpx_grid_fill(m_, id, value));
     if (!c) return VPX_E_INVALID;
@@ -3170,25 +3288,73 @@ static int ensure_model_aux(vpx_ctx* c) {
     return VPX_OK;
 }
 
-int vpx_model_upload(vpx_ctx* c, uint32_t id, const uint8_t* voxels, uint32_t sx, uint32_t sy, uint32_t sz) {
-    VPX_GROUP_ALL(c, vpx_model_upload(m_, id, voxels, sx, sy, sz));
-    if (!c) return VPX_E_INVALID;
+// Resident model `id` replaced by an empty one of sx * sy * sz voxels in `m` (vpx_model_upload,
+// vpx_model_capture): the checks, the wait for the frames in flight, the old model released,
+// the aux buffers, the voxels and the `mat` scratch.  Without `fill` the id is only emptied.
+// The caller fills m.vox and moves m into c->models[id]: a failure leaves the id empty.
+static int model_replace(vpx_ctx* c, uint32_t id, bool fill, uint32_t sx, uint32_t sy, uint32_t sz, vpx_ctx::ModelBuf& m) {
     if (id > 4096) return fail(c, VPX_E_INVALID, "model_id too large");
-    if (voxels && (!sx || !sy || !sz || sx > model::kMaxDim || sy > model::kMaxDim || sz > model::kMaxDim))
+    if (fill && (!sx || !sy || !sz || sx > model::kMaxDim || sy > model::kMaxDim || sz > model::kMaxDim))
         return fail(c, VPX_E_INVALID, "model dimension outside 1..256");
     VPX_HIP(c, hipSetDevice(c->device));
     VPX_HIP(c, sync_all(c));
     if (id < c->models.size()) c->models[id] = vpx_ctx::ModelBuf{};
-    if (!voxels) return VPX_OK;
+    if (!fill) return VPX_OK;
     if (int rc = ensure_model_aux(c)) return rc;
     if (id >= c->models.size()) c->models.resize(id + 1);
-    vpx_ctx::ModelBuf m;  // the context's only when complete: a failure leaves the id empty
     const size_t count = (size_t)sx * sy * sz;
     VPX_HIP(c, m.vox.alloc(count));
     VPX_HIP(c, m.mat.alloc((count + model::kChunk - 1) / model::kChunk * model::kChunk));
-    VPX_HIP(c, hipMemcpy(m.vox, voxels, count, hipMemcpyHostToDevice));
     m.sx = sx, m.sy = sy, m.sz = sz;
+    return VPX_OK;
+}
+
+int vpx_model_upload(vpx_ctx* c, uint32_t id, const uint8_t* voxels, uint32_t sx, uint32_t sy, uint32_t sz) {
+    VPX_GROUP_ALL(c, vpx_model_upload(m_, id, voxels, sx, sy, sz));
+    if (!c) return VPX_E_INVALID;
+    vpx_ctx::ModelBuf m;  // the context's only when complete: a failure leaves the id empty
+    if (int rc = model_replace(c, id, voxels != nullptr, sx, sy, sz, m)) return rc;
+    if (!voxels) return VPX_OK;
+    VPX_HIP(c, hipMemcpy(m.vox, voxels, (size_t)sx * sy * sz, hipMemcpyHostToDevice));
     c->models[id] = std::move(m);
+    return VPX_OK;
+}
+
+int vpx_model_capture(vpx_ctx* c, uint32_t model_id, uint32_t id, uint32_t x0, uint32_t y0, uint32_t z0, uint32_t dx,
+                      uint32_t dy, uint32_t dz) {
+    VPX_GROUP_ALL(c, vpx_model_capture(m_, model_id, id, x0, y0, z0, dx, dy, dz));
+    if (!c) return VPX_E_INVALID;
+    if (id >= c->grids.size() || !c->grids[id].ptr) return fail(c, VPX_E_INVALID, "unknown grid");
+    const auto& g = c->grids[id];
+    if (dx && dy && dz && ((uint64_t)x0 + dx > g.n || (uint64_t)y0 + dy > g.n || (uint64_t)z0 + dz > g.n))
+        return fail(c, VPX_E_INVALID, "box outside the grid");
+    vpx_ctx::ModelBuf m;  // the context's only when complete: a failure leaves the id empty
+    if (int rc = model_replace(c, model_id, true, dx, dy, dz, m)) return rc;
+    const bool wide = g.n % 16u == 0 && x0 % 16u == 0 && dx % 16u == 0;
+    const uint64_t threads = (uint64_t)(wide ? dx / 16u : dx) * dy * dz;
+    const dim3 blocks((unsigned)std::min<uint64_t>(4096, (threads + 255) / 256));
+    if (wide)
+        hipLaunchKernelGGL(capture_k<true>, blocks, dim3(256), 0, c->stream, (const uint8_t*)g.ptr, g.n, m.vox.get(), x0, y0, z0, dx, dy, dz);
+    else
+        hipLaunchKernelGGL(capture_k<false>, blocks, dim3(256), 0, c->stream, (const uint8_t*)g.ptr, g.n, m.vox.get(), x0, y0, z0, dx, dy, dz);
+    VPX_HIP(c, hipGetLastError());
+    VPX_HIP(c, sync_all(c));
+    c->models[model_id] = std::move(m);
+    return VPX_OK;
+}
+
+int vpx_model_read(vpx_ctx* c, uint32_t model_id, uint8_t* dst, uint64_t cap, uint32_t size_out[3]) {
+    VPX_GROUP_FIRST(c, vpx_model_read(m_, model_id, dst, cap, size_out));
+    if (!c || !size_out) return fail(c, VPX_E_INVALID, "null argument");
+    if (model_id >= c->models.size() || !c->models[model_id].vox) return fail(c, VPX_E_INVALID, "unknown model");
+    const auto& m = c->models[model_id];
+    size_out[0] = m.sx, size_out[1] = m.sy, size_out[2] = m.sz;
+    if (!dst) return VPX_OK;
+    const uint64_t count = (uint64_t)m.sx * m.sy * m.sz;
+    if (cap < count) return fail(c, VPX_E_INVALID, "cap smaller than the model");
+    VPX_HIP(c, hipSetDevice(c->device));
+    VPX_HIP(c, sync_all(c));
+    VPX_HIP(c, hipMemcpy(dst, m.vox, count, hipMemcpyDeviceToHost));
     return VPX_OK;
 }
 

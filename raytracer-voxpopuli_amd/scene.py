@@ -211,6 +211,42 @@ def apply_brushes(cells, n, brushes):
     return res
 
 
+def orient(axes=(0, 1, 2), flips=(False, False, False)):
+    """vpx_stamp.orient: axes[q] is the model axis (0 = x, 1 = y, 2 = z) that feeds grid axis q,
+    flips[q] whether grid axis q runs against it.  orient() is VPX_ORIENT_IDENTITY,
+    orient((0, 2, 1)) VPX_ORIENT_LOAD_MODEL."""
+    a = [int(v) for v in axes]
+    assert sorted(a) == [0, 1, 2], "axes must be a permutation of (0, 1, 2)"
+    return a[0] | a[1] << 2 | a[2] << 4 | sum(1 << (8 + q) for q in range(3) if flips[q])
+
+
+def stamp(model_id, origin, orient=abi.ORIENT_IDENTITY, flags=0, value=0, match=(0, 255)):
+    """abi.Stamp: model `model_id` turned by `orient` (scene.orient), the low corner of its box at the
+    grid cell `origin` (x, y, z; may lie outside the grid).  flags: abi.STAMP_GRID_BYTES (the
+    model holds grid bytes, 255 empty, as model_capture stores them; default 0 empty),
+    abi.STAMP_CONSTANT (non-empty voxels write `value`; 255 digs the shape out).  match filters on
+    the cell's current byte as for sphere_brush."""
+    return abi.Stamp(int(model_id), (C.c_int32 * 3)(*[int(v) for v in origin]), int(orient), int(flags), int(value),
+                     int(match[0]), int(match[1]), 0, 0)
+
+
+def apply_stamps(cells, n, models, stamps):
+    """vpx_stamp_apply_host: the stamps on a host grid of n^3 bytes, in place: abi.BrushResult.
+    models: a list of (size, voxels) as Context.model_upload takes them; model_id indexes it."""
+    lib = abi.load_library()
+    assert cells.dtype == np.uint8 and cells.size == int(n) ** 3 and cells.flags.c_contiguous
+    keep = [np.ascontiguousarray(v, np.uint8).reshape(-1) for _, v in models]
+    for (size, _), v in zip(models, keep):
+        assert v.size == int(size[0]) * int(size[1]) * int(size[2]), "voxels do not match the model size"
+    src = (abi.StampSource * max(1, len(models)))(*[abi.StampSource(v.ctypes.data, int(s[0]), int(s[1]), int(s[2]), 0)
+                                                    for (s, _), v in zip(models, keep)])
+    arr = (abi.Stamp * max(1, len(stamps)))(*stamps)
+    res = abi.BrushResult()
+    abi.check(lib, None, lib.vpx_stamp_apply_host(cells.ctypes.data, int(n), src, len(models), arr, len(stamps), C.byref(res)),
+              "vpx_stamp_apply_host")
+    return res
+
+
 def default_materials():
     lib = abi.load_library()
     mats = (abi.Material * 256)()
