@@ -30,9 +30,10 @@ Not covered, on purpose:
     direction it is given exactly, so head() composed with it cannot carry an rsqrt-normalised D,
     and the numpy Trace has no FastReciprocal;
   - GetPrimaryRayNoDOF paths (the static camera, vpx_render_ids, vpx_pick_pixel): restated in
-    tests/test_kat_reproject.py and tests/reproject_ids_ref.py;
-  - spot and area lights inside the numpy Trace (test_kat_paths.Scene has point and directional
-    lights): the GPU tests compose head() with the device's vpx_trace for those.
+    tests/test_kat_reproject.py and tests/reproject_ids_ref.py.
+Spot and area lights are inside the numpy Trace (test_kat_paths.Scene.illumination; tests/test_kat_lights.py
+pins the oracle to it): whole frames with them are compared with head -> numpy Trace like the others, and
+the GPU tests' composition of head() with the device's vpx_trace remains for depth 8 and as a second check.
 
 The device flushes subnormals and numpy does not: every intermediate is asserted to be zero or
 normal, so that the restatement never silently depends on one.

@@ -14,6 +14,7 @@ import pytest
 
 import epilogue_ref as E
 import frame_head_ref as F
+import test_kat_lights as L
 from test_kat_paths import N, NONE, Rng, Scene, Vol, _messy_volume, api_rays, fbits, kat_scene, to_oracle, v3
 
 pytestmark = pytest.mark.filterwarnings("ignore:divide by zero:RuntimeWarning", "ignore:invalid value:RuntimeWarning")
@@ -42,17 +43,23 @@ def camera(pkg, W, H, focal=1.0, jitter=2.0, cam=CAM):
     return c
 
 
-def frame_params(abi, W, H, frame=0, seed_base=0, flags=0, aa=1.0, depth=0):
+def frame_params(abi, W, H, frame=0, seed_base=0, flags=0, aa=1.0, depth=0, samples=3):
     p = abi.FrameParams()
     p.width, p.height, p.max_bounces, p.frame_index, p.seed_base = W, H, depth, frame, seed_base
-    p.flags, p.aa_strength, p.area_samples, p.sky = flags, aa, 3, abi.vec3(SKY)
+    p.flags, p.aa_strength, p.area_samples, p.sky = flags, aa, samples, abi.vec3(SKY)
     return p
 
 
-def room(pkg, vols_of=lambda cells: [Vol(cells, N)], wall=0):
+def room(pkg, vols_of=lambda cells: [Vol(cells, N)], wall=0, lights=None):
+    """The KAT room as a SceneDesc and as what Scene takes; lights: a test_kat_lights light set in place
+    of the room's point light (the last element then holds the spots and areas for Scene)."""
     cells, mats, points, d = kat_scene(wall)
     vols = vols_of(cells)
-    return to_oracle(pkg, None, cells, mats, points, d, vols), (cells, mats, points, d, vols)
+    if lights is None:
+        return to_oracle(pkg, None, cells, mats, points, d, vols), (cells, mats, points, d, vols)
+    kw = L.lights_of(lights)
+    points = kw.pop("points")
+    return to_oracle(pkg, None, cells, mats, points, d, vols, **kw), (cells, mats, points, d, vols, kw)
 
 
 def two_volumes(cells):
@@ -419,29 +426,43 @@ def test_forced_draws(pkg, orc, abi):
 
 # ------------------------------------------------------------------ whole frames
 FRAME_W, FRAME_H = 19, 13
-FRAME_SCENES = {"room": lambda cells: [Vol(cells, N)], "two volumes": two_volumes}
+FRAME_SCENES = {"room": lambda cells: [Vol(cells, N)], "two volumes": two_volumes,
+                "mixed lights": lambda cells: [Vol(cells, N)]}
+# which -> (light set, area samples): the scenes whose lights are not the room's own point light.  "wide
+# lights" (18 lights and the directional one, 15 samples) is no FRAME_SCENES entry: it has one frame at depth 2.
+# "mixed lights, 1 sample" is the mixed set with one shadow slot per path, which the device's one-launch
+# depth-0 frame kernel requires.
+FRAME_LIGHTS = {"mixed lights": (L.LIGHT_SETS["mixed"], 3), "wide lights": (L.LIGHT_SETS["wide"], 15),
+                "mixed lights, 1 sample": (L.LIGHT_SETS["mixed"], 1)}
 FRAME_LENS = dict(focal=1.3, jitter=2.0)
 _FRAMES = {}
 
 
-def expected_frames(pkg, abi, which, depth):
-    """Frames 0..2 of the 19x13 AA+DOF scene accumulated from a zero accumulator by F.frame (numpy
-    only): (desc, camera, [per frame (accumulator bits, RGB8)], refusals).  Computed once and shared
-    with the GPU tests."""
-    key = (which, depth)
+def frame_samples(which):
+    return FRAME_LIGHTS[which][1] if which in FRAME_LIGHTS else 3
+
+
+def expected_frames(pkg, abi, which, depth, frames=3):
+    """Frames 0..frames-1 of the 19x13 AA+DOF scene accumulated from a zero accumulator by F.frame
+    (numpy only): (desc, camera, [per frame (accumulator bits, RGB8, shadow rays, DDA cells, the
+    picks)], refusals).  Computed once and shared with the GPU tests."""
+    key = (which, depth, frames)
     if key not in _FRAMES:
-        desc, (cells, mats, points, d, vols) = room(pkg, FRAME_SCENES[which])
+        lights, samples = FRAME_LIGHTS.get(which, (None, 3))
+        desc, (cells, mats, points, d, vols, *kw) = room(pkg, FRAME_SCENES.get(which, FRAME_SCENES["room"]), lights=lights)
+        desc.area_samples = samples
         cam = camera(pkg, FRAME_W, FRAME_H, **FRAME_LENS)
         acc = np.zeros((FRAME_W * FRAME_H, 4), np.uint32)
         out, refused = [], []
-        for f in range(3):
-            p = frame_params(abi, FRAME_W, FRAME_H, f, 0, AA | DOF, 1.0, depth)
-            s = Scene(vols, mats, points, d, sky=SKY)
+        for f in range(frames):
+            p = frame_params(abi, FRAME_W, FRAME_H, f, 0, AA | DOF, 1.0, depth, samples)
+            s = Scene(vols, mats, points, d, sky=SKY, **(kw[0] if kw else {}))
+            s.area_samples = samples
             r = refusing(lambda: F.frame(s, cam, p, acc), refused)
             if r is None:
                 break
             acc, rgb = r
-            out.append((acc, rgb))
+            out.append((acc, rgb, s.shadows, s.cells, s.picks))
         _FRAMES[key] = (desc, cam, out, refused)
     return _FRAMES[key]
 
@@ -456,12 +477,52 @@ def test_whole_frames_equal_oracle_render(pkg, orc, abi, which, depth):
     o = orc.Oracle(abi, desc)
     o.set_camera(cam)
     acc = None
-    for f, (want_acc, want_rgb) in enumerate(frames):
-        acc, rgb, _ = o.render(frame_params(abi, FRAME_W, FRAME_H, f, 0, AA | DOF, 1.0, depth), accum=acc, threads=2)
+    for f, (want_acc, want_rgb, shadows, cells, _) in enumerate(frames):
+        acc, rgb, st = o.render(frame_params(abi, FRAME_W, FRAME_H, f, 0, AA | DOF, 1.0, depth, frame_samples(which)),
+                                accum=acc, threads=2)
         bad, left_out = E.compare(fbits(acc), rgb, want_acc, want_rgb)
         assert not bad and left_out == 0, (which, depth, f, len(bad), bad[:8])
+        assert (st.shadow_rays, st.dda_cells) == (shadows, cells), (which, depth, f)
     hit = (frames[0][0][:, :3] != fbits(np.array(SKY, np.float32))[None, :]).any(axis=1)
     assert 40 <= hit.sum() <= FRAME_W * FRAME_H - 20  # both hits and misses, not a constant image
+
+
+def frame_picks(frames):
+    """(kind, index within the kind, randLightIndex, outcome) of every Illumination call of the frames."""
+    return [p for fr in frames for p in fr[4]]
+
+
+def test_light_frames_draw_every_light(pkg, abi):
+    """What the frames with light sets stand on, from the restatement alone: every light of the mixed
+    set is drawn at depth 0 and at depth 2, spots fall outside, lit and occluded, area samples are
+    rejected, occluded and lit; the wide frame draws every one of its 19 lights, picks that share a
+    bucket modulo 16, and an area light with all 15 samples lit (every slot bit)."""
+    for depth in (0, 2):
+        _, _, frames, refused = expected_frames(pkg, abi, "mixed lights", depth)
+        assert not refused and len(frames) == 3
+        picks = frame_picks(frames)
+        assert {p[2] for p in picks} == set(range(7)), depth
+        assert {p[3] for p in picks if p[0] == "spot"} == {"outside", "lit", "occluded"}, depth
+        assert {o for p in picks if p[0] == "area" for o in p[3]} == {"rejected", "occluded", "lit"}, depth
+    _, _, frames, refused = expected_frames(pkg, abi, "wide lights", 2, frames=1)
+    assert not refused and len(frames) == 1
+    picks = frame_picks(frames)
+    idx = {p[2] for p in picks}
+    assert idx == set(range(19)) and {0, 16} <= idx
+    assert any(p[0] == "area" and set(p[3]) == {"lit"} and len(p[3]) == 15 for p in picks)
+    assert any(p[0] == "area" and len(set(p[3])) == 3 for p in picks)  # one pick with all three outcomes
+
+
+def test_wide_light_frame_equals_oracle_render(pkg, orc, abi):
+    """One 19x13 frame at depth 2 with the wide light set and 15 area samples."""
+    desc, cam, frames, refused = expected_frames(pkg, abi, "wide lights", 2, frames=1)
+    assert not refused and len(frames) == 1
+    o = orc.Oracle(abi, desc)
+    o.set_camera(cam)
+    acc, rgb, st = o.render(frame_params(abi, FRAME_W, FRAME_H, 0, 0, AA | DOF, 1.0, 2, 15), threads=2)
+    bad, left_out = E.compare(fbits(acc), rgb, frames[0][0], frames[0][1])
+    assert not bad and left_out == 0, (len(bad), bad[:8])
+    assert (st.shadow_rays, st.dda_cells) == (frames[0][2], frames[0][3])
 
 
 # ------------------------------------------------------------------ focus ray

@@ -8,10 +8,10 @@ The head cases at the parameter ends (K.head_cases, inside the closed lit box) a
 pixel sets (fma against mul + add, (p * jitter) / W against p * (jitter / W)) are compared as raw
 samples (VPX_FLAG_NO_TONEMAP) with head() composed with vpx_trace.
 
-Tier B: the head in every kernel that computes it.  For scenes the numpy Trace does not model (spot
-and area lights, depth 8) the expected sample of a pixel is head() composed with the device's own
-vpx_trace(origin, direction, state) — the entry test_kat_paths_on_device pins to the numpy Trace —
-folded with epilogue_ref.blend_ref.  Forms as tests/test_epilogue_gpu.py's FORMS, each confirmed on
+Tier B: the head in every kernel that computes it.  The expected sample of a pixel is head() composed
+with the device's own vpx_trace(origin, direction, state) — the entry test_kat_paths_on_device and
+test_kat_lights_gpu pin to the numpy Trace — folded with epilogue_ref.blend_ref; for the "spot" and
+"area3" forms the composed samples are held to the numpy Trace as well.  Forms as tests/test_epilogue_gpu.py's FORMS, each confirmed on
 the serial vpx_render with vpx_debug_last_frame_kernel and vpx_profile_read; a 37x21 frame (partial
 right and bottom tiles), frames 0..2 (and 2..4 for the second window), through vpx_render with 0 and
 2 lanes, vpx_render_tiles_accum for every rank of 1, 2 and 3, vpx_render_window, and vpx_render /
@@ -103,10 +103,10 @@ def test_whole_frames_equal_the_restatement(pkg, abi, which, depth):
     desc, cam, frames, refused = K.expected_frames(pkg, abi, which, depth)
     assert len(refused) == 0 and len(frames) == 3, refused
     ctx = open_ctx(pkg, desc, cam)
-    params = [K.frame_params(abi, K.FRAME_W, K.FRAME_H, f, 0, AA | DOF, 1.0, depth) for f in range(3)]
+    params = [K.frame_params(abi, K.FRAME_W, K.FRAME_H, f, 0, AA | DOF, 1.0, depth, K.frame_samples(which)) for f in range(3)]
     got = render_frames(ctx, params, K.FRAME_W * K.FRAME_H)
     ctx.close()
-    for f, ((acc, rgb), (want_acc, want_rgb)) in enumerate(zip(got, frames)):
+    for f, ((acc, rgb), (want_acc, want_rgb, *_)) in enumerate(zip(got, frames)):
         expect(acc, rgb, want_acc, want_rgb, f"{which} depth {depth} frame {f}")
 
 
@@ -286,6 +286,25 @@ def folded(pkg, abi, kind, first, count=3):
             acc, rgb = E.reference(samples(pkg, abi, kind, f), acc, f)
         return acc, rgb
     return cached(("folded", kind, first, count), make)
+
+
+@pytest.mark.parametrize("kind", ["spot", "area3"])
+def test_composed_samples_equal_the_numpy_trace(pkg, abi, kind):
+    """The expected samples of the "spot" and "area3" forms, head() composed with the device's
+    vpx_trace, are also the numpy Trace's (frame 0): the lights of those scenes are ones
+    test_kat_paths.Scene.illumination restates, read back here from the scene the device was given."""
+    _torch()
+    desc = kind_scene(pkg, kind)
+    cells, mats, points, d = kat_scene(0)
+    spots = [(tuple(s.position), tuple(s.direction), tuple(s.color), s.angle) for s in desc.spots]
+    areas = [(tuple(a.position), tuple(a.color), a.color_multiplier, a.radius) for a in desc.areas]
+    assert len(spots) + len(areas) == 1
+    s = K.Scene([Vol(cells, N)], mats, points, d, sky=SKY, spots=spots, areas=areas)
+    want = F.samples(s, tb_camera(pkg), tb_params(abi, kind, 0))
+    got = samples(pkg, abi, kind, 0)
+    bad = np.flatnonzero((got != want).any(axis=1))
+    assert bad.size == 0, (kind, bad[:8], got[bad[0]], want[bad[0]])
+    assert {p[0] for p in s.picks} == {"point", "spot" if spots else "area", "directional"}
 
 
 @pytest.mark.parametrize("lanes", [0, 2])

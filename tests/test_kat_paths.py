@@ -18,6 +18,8 @@ operand order, rounded to float32 after each step (the build's -ffp-contract=off
   Scene::FindNearest / IsOccluded  template/scene.cpp:751-811, 1009-1047
   Scene::FindMaterialExit / FindSmokeExit  template/scene.cpp:875-1006
   PointLightEvaluate / DirectionalLightEvaluate / Illumination  renderer.cpp:102-131, 315-338, 738-764
+  SpotLightEvaluate / AreaLightEvaluation  renderer.cpp:133-207 (tests/test_kat_lights.py holds the
+                                                        oracle to them, test_kat_lights_gpu.py the device)
 """
 import ctypes as C
 import math
@@ -49,6 +51,10 @@ def sub(a, b):
 
 def mul(a, b):  # float3 * float3 or float3 * float (commutative per lane in IEEE)
     return (np.asarray(a, np.float32) * np.asarray(b, np.float32)).astype(np.float32)
+
+
+def div(a, b):  # float3 / float: a lane-wise division (tmpl8math.h:1962-1972)
+    return (np.asarray(a, np.float32) / np.asarray(b, np.float32)).astype(np.float32)
 
 
 def dot(a, b):  # tmpl8math.h: a.x*b.x + a.y*b.y + a.z*b.z, left to right
@@ -314,9 +320,18 @@ class Vol:
 
 
 class Scene:
-    def __init__(self, vols, mats, points=(), dir_light=(v3(1, 0, 0), v3(0, 0, 0)), sky=(0.392, 0.584, 0.829)):
+    """points: [(position, colour)]; spots: [(position, direction, colour, angle)], the angle a cosine;
+    areas: [(position, colour, colorMultiplier, radius)]; area_samples: numCheckShadowsAreaLight."""
+
+    def __init__(self, vols, mats, points=(), dir_light=(v3(1, 0, 0), v3(0, 0, 0)), sky=(0.392, 0.584, 0.829),
+                 spots=(), areas=()):
         self.vols, self.mats = vols, mats
         self.points = list(points)
+        self.spots = [(v3(*p), v3(*d), v3(*c), f32(a)) for p, d, c, a in spots]
+        self.areas = [(v3(*p), v3(*c), f32(m), f32(r)) for p, c, m, r in areas]
+        self.area_samples = 3
+        self.picks = []  # per Illumination call: (kind, index within the kind, randLightIndex, outcome)
+        self.outcome = None
         self.dir = dir_light
         self.sky = v3(*sky)
         self.cells = 0
@@ -391,32 +406,113 @@ class Scene:
         ray.t = s["t"]
         return False
 
-    def illumination(self, ray, g):  # Illumination (renderer.cpp:738-764), point + directional
-        lc = len(self.points) + 1
-        idx = int(f32(g.rf() * f32(lc)))
-        ip, n = ray.point(), ray.N
-        inc = v3(0, 0, 0)
-        if idx < len(self.points):  # PointLightEvaluate (renderer.cpp:102-131)
-            pos, col = self.points[idx]
-            dr = sub(pos, ip)
-            dst = length(dr)
-            dn = mul(dr, f32(f32(1.0) / dst))
-            c = dot(dn, n)
-            if not (c <= f32(0.0)):
-                li = mul(mul(col, std_max(f32(0.0), c)), f32(f32(1.0) / f32(dst * dst)))
-                sh = Ray(offset_ray(ip, n), dn)
-                sh.t = dst
-                if not self.is_occluded(sh):
-                    inc = mul(li, self.albedo(ray.mat))
-        else:  # DirectionalLightEvaluate (renderer.cpp:315-338)
-            dr = -self.dir[0]
-            c = dot(dr, n)
-            if not (c <= f32(0)):
-                li = mul(self.dir[1], std_max(f32(0.0), c))
-                sh = Ray(offset_ray(ip, n), dr)
-                if not self.is_occluded(sh):
-                    inc = mul(li, self.albedo(ray.mat))
+    def illumination(self, ray, g):  # Illumination (renderer.cpp:738-764)
+        np_, na, ns = len(self.points), len(self.areas), len(self.spots)
+        lc = np_ + na + ns + 1  # CalculateLightCount: the one directional light last
+        idx = int(f32(g.rf() * f32(lc)))  # static_cast<size_t>(Rand(lightCount))
+        if idx < np_:
+            pick = ("point", idx)
+            inc = self.point_light(ray, self.points[idx])
+        elif idx < na + np_:  # the areas come before the spots
+            pick = ("area", idx - np_)
+            inc = self.area_light(ray, self.areas[idx - np_], g)
+        elif idx < na + ns + np_:
+            pick = ("spot", idx - na - np_)
+            inc = self.spot_light(ray, self.spots[idx - na - np_])
+        else:
+            pick = ("directional", 0)
+            inc = self.directional_light(ray)
+        self.arms.add(("light",) + pick)
+        self.picks.append(pick + (idx, self.outcome))
         return mul(inc, f32(lc))
+
+    def point_light(self, ray, light):  # PointLightEvaluate (renderer.cpp:102-131)
+        self.outcome = None
+        ip, n = ray.point(), ray.N
+        pos, col = light
+        dr = sub(pos, ip)
+        dst = length(dr)
+        dn = mul(dr, f32(f32(1.0) / dst))
+        c = dot(dn, n)
+        if c <= f32(0.0):
+            return v3(0, 0, 0)
+        li = mul(mul(col, std_max(f32(0.0), c)), f32(f32(1.0) / f32(dst * dst)))
+        sh = Ray(offset_ray(ip, n), dn)
+        sh.t = dst
+        if self.is_occluded(sh):
+            return v3(0, 0, 0)
+        return mul(li, self.albedo(ray.mat))
+
+    def spot_light(self, ray, light):  # SpotLightEvaluate (renderer.cpp:133-159): no N.L test
+        ip = ray.point()
+        pos, direction, col, angle = light
+        dr = sub(pos, ip)
+        dst = length(dr)
+        dn = div(dr, dst)
+        n = ray.N
+        c = dot(dn, direction)
+        if c <= angle:
+            self.outcome = "outside"
+            self.arms.add(("spot", "outside"))
+            return v3(0, 0, 0)
+        alpha = f32(f32(1.0) - f32(f32(f32(f32(1.0) - c) * f32(1.0)) / f32(f32(1.0) - angle)))
+        li = div(mul(col, std_max(f32(0.0), c)), f32(dst * dst))
+        k = self.albedo(ray.mat)
+        sh = Ray(offset_ray(ip, n), dn)
+        sh.t = dst
+        if self.is_occluded(sh):
+            self.outcome = "occluded"
+            self.arms.add(("spot", "occluded"))
+            return v3(0, 0, 0)
+        self.outcome = "lit"
+        self.arms.add(("spot", "lit"))
+        return mul(mul(li, k), alpha)
+
+    def area_light(self, ray, light, g):  # AreaLightEvaluation (renderer.cpp:161-207)
+        ip, n = ray.point(), ray.N
+        center, col, mult, radius = light
+        inc = v3(0, 0, 0)
+        k = self.albedo(ray.mat)
+        point = offset_ray(ip, n)
+        out = []
+        for _ in range(self.area_samples):
+            rp = g.random_direction()
+            rp = mul(rp, radius)
+            rp = add(rp, center)
+            dr = sub(rp, ip)
+            dst = length(dr)
+            dn = mul(dr, f32(f32(1) / dst))
+            c = dot(dn, n)
+            if c <= f32(0):
+                out.append("rejected")
+                continue
+            sh = Ray(point, dn)
+            sh.t = dst
+            if self.is_occluded(sh):
+                out.append("occluded")
+                continue
+            # cosTheta * color * colorMultiplier * (radius * radius) * PI4 / (dst * dst), PI4 the
+            # unparenthesised macro 3.14159265358979323846264f*4.0f (common.h:10)
+            li = mul(mul(mul(mul(mul(col, c), mult), f32(radius * radius)), PI), f32(4.0))
+            inc = add(inc, div(li, f32(dst * dst)))
+            out.append("lit")
+        self.outcome = tuple(out)
+        self.arms |= {("area sample", o) for o in out}
+        inc = div(inc, f32(self.area_samples))  # 0 samples: 0 / 0
+        return mul(inc, k)
+
+    def directional_light(self, ray):  # DirectionalLightEvaluate (renderer.cpp:315-338)
+        self.outcome = None
+        ip, n = ray.point(), ray.N
+        dr = -self.dir[0]
+        c = dot(dr, n)
+        if c <= f32(0):
+            return v3(0, 0, 0)
+        li = mul(self.dir[1], std_max(f32(0.0), c))
+        sh = Ray(offset_ray(ip, n), dr)
+        if self.is_occluded(sh):
+            return v3(0, 0, 0)
+        return mul(li, self.albedo(ray.mat))
 
     def trace(self, ray, depth, g):  # Renderer::Trace (renderer.cpp:1076-1328)
         if depth < 0:
@@ -552,8 +648,8 @@ def kat_scene(wall_mat):
     return c, mats, points, d
 
 
-def to_oracle(pkg, orc, cells, mats, points, d, vols):
-    """The same scene as the oracle's (and the device's) SceneDesc."""
+def to_oracle(pkg, orc, cells, mats, points, d, vols, spots=(), areas=()):
+    """The same scene as the oracle's (and the device's) SceneDesc; spots and areas as Scene takes them."""
     abi, sc = pkg.abi, pkg.scene
     m = (abi.Material * 256)()
     for i in range(256):
@@ -571,8 +667,11 @@ def to_oracle(pkg, orc, cells, mats, points, d, vols):
         vol.b0[:] = [float(x) for x in v.b0]
         vol.b1[:] = [float(x) for x in v.b1]
         vs.append(vol)
+    fl = lambda a: tuple(float(f32(x)) for x in a)  # noqa: E731
     desc = sc._scene("kat", [sc.GridSpec(n=N, dense=cells)], vs, m,
-                     [sc.point_light(tuple(map(float, p)), tuple(map(float, c))) for p, c in points], [], [],
+                     [sc.point_light(tuple(map(float, p)), tuple(map(float, c))) for p, c in points],
+                     [sc.spot_light(fl(p), fl(dr), fl(c), float(f32(a))) for p, dr, c, a in spots],
+                     [sc.area_light(fl(p), fl(c), float(f32(ml)), float(f32(r))) for p, c, ml, r in areas],
                      sc.dir_light(tuple(map(float, d[0])), tuple(map(float, d[1]))), (0.5, 0.5, -1.0), (0.5, 0.5, 0.5),
                      16, 16)
     return desc

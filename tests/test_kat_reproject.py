@@ -271,17 +271,29 @@ def reproject_scene():
 
 
 _PASS1 = {}
+MIXED = "mixed"  # test_kat_lights' mixed light set in place of the room's point light
 
 
-def pass1(w, h, depth, frame_index, cam_pt):
+def scene_lights(lights):
+    """(points, Scene's spots / areas keywords) of reproject_scene() under `lights` (None: its own)."""
+    if lights is None:
+        return reproject_scene()[2], {}
+    from test_kat_lights import LIGHT_SETS, lights_of
+
+    kw = lights_of(LIGHT_SETS[lights])
+    return kw.pop("points"), kw
+
+
+def pass1(w, h, depth, frame_index, cam_pt, lights=None):
     """The first pixel loop (renderer.cpp:2003-2022): albedo, illumination, GetRayInfo's
     intersection point and material per pixel, and the loop's counts."""
-    key = (w, h, depth, frame_index, cam_pt)
+    key = (w, h, depth, frame_index, cam_pt, lights)
     if key in _PASS1:
         return _PASS1[key]
-    cells, mats, points, d = reproject_scene()
+    cells, mats, _, d = reproject_scene()
+    points, kw = scene_lights(lights)
     cam = Camera(cam_pt[0], cam_pt[1], w, h)
-    s = RScene([Vol(cells, N)], mats, points, d, sky=SKY)
+    s = RScene([Vol(cells, N)], mats, points, d, sky=SKY, **kw)
     alb, ill, ip = (np.zeros((w * h, 3), np.float32) for _ in range(3))
     mat = np.zeros(w * h, np.int64)
     for y in range(h):
@@ -293,7 +305,7 @@ def pass1(w, h, depth, frame_index, cam_pt):
             alb[k], ill[k] = a, i
             ip[k], mat[k] = ray.point(), ray.mat  # GetRayInfo on the ray as TraceReproject leaves it
     out = dict(alb=alb, ill=ill, ip=ip, mat=mat, nearest=s.nearest, shadows=s.shadows, cells=s.cells,
-               probes=s.probes)
+               probes=s.probes, picks=s.picks)
     _PASS1[key] = out
     return out
 
@@ -450,7 +462,10 @@ CASES = {
     # a live camera beside the KAT position, so that no pixel centre lies on a cell boundary: the
     # 3 x 3 metal pixels all reflect the sky, a uniform neighbourhood whose variance term is < 0
     "f_uniform_metal": (20, 12, 1, OFF_CAM, 1, OFF_CAM),
+    # TraceReproject's Illumination calls with spot and area lights (3 samples), two frames
+    "g_mixed_lights": (20, 12, 1, _cam((0.004, -0.003, 0.002), (0.3 * PX, -0.3 * PX, 0)), 2),
 }
+LIGHTS = {"g_mixed_lights": MIXED}
 
 
 def crafted_history(w, h):
@@ -489,7 +504,7 @@ def expected_case(name):
     hist = crafted_history(w, h)
     out, arms = [], set()
     for f in range(frames):
-        p1 = pass1(w, h, depth, f, live)
+        p1 = pass1(w, h, depth, f, live, LIGHTS.get(name))
         new, rgb, (sh2, cells2), a = pass2(p1, w, h, prev, hist)
         arms |= a
         bounce = p1["nearest"] - (w * h if depth >= 0 else 0)  # vpx_stats: FindNearest calls past the primary
@@ -505,9 +520,10 @@ def expected():
     return {name: expected_case(name) for name in CASES}
 
 
-def scene_desc(pkg, w, h, depth, live=KAT_CAM):
-    cells, mats, points, d = reproject_scene()
-    desc = to_oracle(pkg, None, cells, mats, points, d, [Vol(cells, N)])
+def scene_desc(pkg, w, h, depth, live=KAT_CAM, lights=None):
+    cells, mats, _, d = reproject_scene()
+    points, kw = scene_lights(lights)
+    desc = to_oracle(pkg, None, cells, mats, points, d, [Vol(cells, N)], **kw)
     desc = desc.with_size(w, h)
     desc._cam_pos, desc._cam_target = live
     desc.camera = pkg.scene.look_at(live[0], live[1], w, h)
@@ -560,7 +576,7 @@ def test_oracle_equals_restatement(pkg, orc, expected, name):
     """oracle_render_reproject: the same history bits, RGB8 words and shadow / bounce / cell
     counts as the restatement, frame after frame with the history fed back."""
     w, h, depth, _, frames = CASES[name][:5]
-    desc = scene_desc(pkg, w, h, depth, live_of(name))
+    desc = scene_desc(pkg, w, h, depth, live_of(name), LIGHTS.get(name))
     o = orc.Oracle(pkg.abi, desc)
     prev = _prev_struct(pkg, name)
     out, _ = expected[name]
@@ -602,6 +618,12 @@ def test_reprojection_arms_are_covered(expected):
     mats = set(int(m) for m in pass1(20, 12, 1, 0, KAT_CAM)["mat"])
     assert {0, 4, 6, 8, 11, 15, 20, NONE} <= mats, mats
     assert expected["a_depth1"][0][0]["probes"] > 0
+    # the mixed set: every light drawn in pass 1, by the smoke probe too, with every area outcome
+    picks = [p for f in range(2) for p in pass1(20, 12, 1, f, KAT_CAM, MIXED)["picks"]]
+    assert {p[2] for p in picks} == set(range(7)), sorted({p[2] for p in picks})
+    assert {o for p in picks if p[0] == "area" for o in p[3]} == {"rejected", "occluded", "lit"}
+    assert {p[3] for p in picks if p[0] == "spot"} == {"outside", "lit", "occluded"}
+    assert expected["g_mixed_lights"][0][0]["probes"] > 0
 
 
 GPU_PIPELINED = "b_subpixel"
@@ -618,7 +640,7 @@ def test_device_equals_restatement(pkg, expected, name):
         pytest.skip("no GPU")
     name, _, pipe = name.partition("+")
     w, h, depth, _, frames = CASES[name][:5]
-    desc = scene_desc(pkg, w, h, depth, live_of(name))
+    desc = scene_desc(pkg, w, h, depth, live_of(name), LIGHTS.get(name))
     prev = _prev_struct(pkg, name)
     out, _ = expected[name]
     ctx = pkg.context.Context(0)

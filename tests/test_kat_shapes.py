@@ -540,6 +540,72 @@ def test_path_arms_are_covered():
     assert carried and c["guards"] == 0
 
 
+# -------------------------------------------------------- 4b. a shape between an area light and the floor
+# From FLOOR_RAY's hit point, about (0.35, 0.125, 0.35), the sphere covers most of the mixed set's first
+# area light (samples in (0.3, 0.8, -0.6) + 0.3 * [0, 1]^3) and leaves the rest of it in view.
+LIGHT_SPHERE = sphere((0.42, 0.5, 0.05), 0.08, 15)
+LIGHT_SAMPLES = 15
+
+
+def _mixed_lights():
+    from test_kat_lights import LIGHT_SETS, lights_of
+
+    kw = lights_of(LIGHT_SETS["mixed"])
+    return kw.pop("points"), kw
+
+
+def light_path_scene(spheres):
+    mats, _, d = lights()
+    points, kw = _mixed_lights()
+    s = ShapeScene([Vol(world("R0"), N)], mats, points, spheres=spheres, dir_light=d, **kw)
+    s.area_samples = LIGHT_SAMPLES
+    return s
+
+
+def light_path_desc(pkg):
+    mats, _, d = lights()
+    points, kw = _mixed_lights()
+    desc = to_oracle(pkg, None, world("R0"), mats, points, d, [Vol(world("R0"), N)], **kw)
+    c, r, m = LIGHT_SPHERE
+    desc.spheres = [pkg.abi.Sphere(pkg.abi.vec3(tuple(float(x) for x in c)), float(r), m)]
+    return desc
+
+
+@functools.lru_cache(maxsize=None)
+def light_path_expect(depth):
+    """FLOOR_RAY over SEEDS with the mixed light set, 15 area samples and LIGHT_SPHERE: radiance,
+    counts, and per seed the floor's pick with and without the sphere."""
+    o, d, inside = FLOOR_RAY
+    rad, shadows, cells, picks, arms = [], 0, 0, [], set()
+    for seed in SEEDS:
+        s, bare = light_path_scene([LIGHT_SPHERE]), light_path_scene([])
+        rad.append(s.trace(make_ray(v3(*o), v3(*d), BIG, inside), depth, Rng(seed)))
+        bare.trace(make_ray(v3(*o), v3(*d), BIG, inside), depth, Rng(seed))
+        shadows, cells, arms = shadows + s.shadows, cells + s.cells, arms | s.shape_arms
+        picks.append((s.picks[0], bare.picks[0]))
+    return dict(rad=np.array(rad, np.float32), shadows=shadows, cells=cells, picks=picks, arms=arms)
+
+
+@pytest.mark.parametrize("depth", DEPTHS)
+def test_sphere_between_an_area_light_and_the_floor(pkg, orc, depth):
+    """The shape stage of IsOccluded under AreaLightEvaluation: of one pick's 15 samples the sphere
+    blocks some and not others (the same samples are all lit without it), and oracle_trace equals
+    the restatement: radiance, shadow rays (a rejected sample sends none), cells."""
+    e = light_path_expect(depth)
+    area = [(p, q) for p, q in e["picks"] if p[0] == "area" and p[1] == 0]
+    assert len(area) >= 2
+    assert all(p[:3] == q[:3] for p, q in e["picks"])  # the sphere changes no draw before the pick
+    assert any({"occluded", "lit"} <= set(p[3]) and set(q[3]) == {"lit"} for p, q in area), area
+    assert ("sphere_is_hit", "len <= t", "nearer") in e["arms"]
+    o, d, inside = FLOOR_RAY
+    orac = orc.Oracle(pkg.abi, light_path_desc(pkg))
+    got, st = orac.trace(api_rays(pkg.abi, [(o, d, 1e34, inside)] * len(SEEDS)), np.array(SEEDS, np.uint32), depth, SKY,
+                         LIGHT_SAMPLES)
+    bad = [hex(s) for k, s in enumerate(SEEDS) if not np.array_equal(fbits(got[k]), fbits(e["rad"][k]))]
+    assert not bad, (depth, bad)
+    assert (st.shadow_rays, st.dda_cells) == (e["shadows"], e["cells"])
+
+
 # ---------------------------------------------------------------------------------- 5. BVH
 def chain(abi, sign):
     """test_gpu_parity.chain_tris(abi, 64) (sign = 1: centroids at x = 2^i, a chain 63 deep) or

@@ -100,6 +100,20 @@ def probe_scene(c):
     return cells, mats, points, d
 
 
+MIXED = "mixed"  # in place of a colour: test_kat_lights' mixed set (2 point + 2 area + 2 spot + directional)
+
+
+def probe_lights(c):
+    """(cells, mats, points, directional light, Scene's spots / areas keywords) of a reference scene."""
+    if c != MIXED:
+        return probe_scene(c) + ({},)
+    from test_kat_lights import LIGHT_SETS, lights_of
+
+    cells, mats, _, d = kat_scene(0)
+    kw = lights_of(LIGHT_SETS[MIXED])
+    return cells, mats, kw.pop("points"), d, kw
+
+
 def probe_rays():
     """(origin, direction, inside, seed) of the 48 reference rays: the two smoke rays x SEEDS."""
     return [(o, dd, inside, seed) for (o, dd, inside) in SMOKE_RAYS for seed in SEEDS]
@@ -111,16 +125,28 @@ _REF = {}
 def reference(c, depth):
     """Per ray (probes, lit, bits of max_sqr) from the numpy restatement; computed once."""
     if (c, depth) not in _REF:
-        cells, mats, points, d = probe_scene(c)
-        rows = []
+        cells, mats, points, d, kw = probe_lights(c)
+        rows, rad, picks = [], [], []
         for o, dd, inside, seed in probe_rays():
-            s = ProbeScene([Vol(cells, N)], mats, points, d)
-            s.trace(Ray(v3(*o), v3(*dd), inside=inside), depth, Rng(seed))
+            s = ProbeScene([Vol(cells, N)], mats, points, d, **kw)
+            rad.append(s.trace(Ray(v3(*o), v3(*dd), inside=inside), depth, Rng(seed)))
+            picks.append(s.picks[0])  # the first Illumination of either smoke ray is the probe's
             ok = [v for v in s.sqr if v == v]
             mx = max(ok) if ok else f32(0)
             rows.append((len(s.sqr), sum(1 for v in s.sqr if v > THRESHOLD), int(np.float32(mx).view(np.uint32))))
         _REF[(c, depth)] = np.array(rows, np.uint64)
+        _RAD[(c, depth)] = (np.array(rad, np.float32), picks)
     return _REF[(c, depth)]
+
+
+_RAD = {}
+
+
+def reference_paths(c, depth):
+    """Per ray the radiance of the same paths (what the stream gives after the probe's draws) and
+    the probe's pick (kind, index, randLightIndex, outcome)."""
+    reference(c, depth)
+    return _RAD[(c, depth)]
 
 
 def test_reference_is_not_empty():
@@ -135,6 +161,35 @@ def test_reference_is_not_empty():
         assert abs(got - mx) < 1e-4, (c, depth, got)
     assert int((reference(4.5, 3)[:, 0] > 1).sum()) == 37
     assert int((reference(4.0, 3)[:, 0] > 1).sum()) == 37
+
+
+@pytest.mark.filterwarnings("ignore:divide by zero:RuntimeWarning")  # 1 / 0 = inf, as the reference
+def test_probe_draws_area_lights(pkg, orc):
+    """The probe with test_kat_lights' mixed set: a third of the probes or so draw an area light, whose
+    rejection loops advance the stream that the smoke branch draws its threshold, its scatter and
+    its direction from afterwards.  oracle_trace at depth 0, 1 and 3 equals the restatement on the
+    same 48 rays bit for bit; the probes' own values are what the GPU test compares."""
+    from test_kat_paths import api_rays, fbits, to_oracle
+
+    cells, mats, points, d, kw = probe_lights(MIXED)
+    o = orc.Oracle(pkg.abi, to_oracle(pkg, None, cells, mats, points, d, [Vol(cells, N)], **kw))
+    rr = probe_rays()
+    rays = api_rays(pkg.abi, [(org, dd, 1e34, inside) for org, dd, inside, _ in rr])
+    seeds = np.array([s for *_, s in rr], np.uint32)
+    for depth in DEPTHS:
+        rows = reference(MIXED, depth)
+        rad, picks = reference_paths(MIXED, depth)
+        area = [p for p in picks if p[0] == "area"]
+        assert len(area) >= 8 and {p[1] for p in area} == {0, 1}, picks
+        assert any("lit" in p[3] for p in area) and any("rejected" in p[3] for p in area)
+        assert {p[0] for p in picks} == {"point", "area", "spot", "directional"}
+        assert int(rows[:, 0].sum()) >= len(rr) and 4 <= int(rows[:, 1].sum()) <= int(rows[:, 0].sum()) - 4, rows[:, :2].sum(0)
+        got, _ = o.trace(rays, seeds, depth, (0.392, 0.584, 0.829), 3)
+        assert not np.isnan(rad).any()
+        assert np.array_equal(fbits(got), fbits(rad)), (depth, np.argwhere(fbits(got) != fbits(rad))[:4])
+    # past depth 0 the radiance depends on the draws after the probe: the paths part (many end in the
+    # one sky colour, so a quarter of the 48 being distinct is asked for)
+    assert len({tuple(r) for r in fbits(reference_paths(MIXED, 3)[0])}) >= 12
 
 
 # ---------------------------------------------------------------------- sharded reduce
